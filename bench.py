@@ -6,7 +6,10 @@ One "step" = suggest(RANDOM) for the whole population (device Philox) + improve_
 (phase 1 + gate + phase 2 to convergence, reference defaults) on the rank's restarts + selection of
 the best (objective, max-violation) point -- everything resident in HBM.
 
-    python bench.py --gpus N --steps K --warmup W [--scaling weak|strong]
+    python bench.py --gpus N --steps K --warmup W [--scaling weak|strong] [--dump-outputs DIR]
+
+--dump-outputs DIR: after the timed region, what the last timed step returned goes to DIR/<name>.npy (float64), so that two builds
+can be compared output for output (the inputs depend on the arguments alone).
 
 N > 1: either a launcher provides RANK / LOCAL_RANK / WORLD_SIZE (python -m torch.distributed.run ...)
 or -- plain `python bench.py --gpus N` -- this process becomes rank 0 and starts ranks 1..N-1 itself
@@ -147,6 +150,30 @@ def write_sidecar(path, payload):
     except Exception as ex:
         sys.stderr.write('bench: sidecar %s not written: %r\n' % (path, ex))
         return False
+
+
+# ------------------------------------------------------------------------------------- --dump-outputs
+# per-restart results of a step, as returned by Engine.cd_stream_run (scheme stream) and Engine.cd_fetch (scheme two)
+LAST_STEP_FIELDS = ('f0', 'maxviol', 'sweeps1', 'sweeps2', 'visits2', 'accepted2', 'ran_phase2', 'status1', 'status2')
+DUMP_LIMIT = 64 << 20       # bytes, all files together
+
+
+def dump_outputs(path, rows, best, first_index):
+    """What the last timed step returned, one float64 .npy file per array: every per-restart field of this rank's restarts
+    (restart_index: their global indices) and the step's best point (best_x; best_key = global index, objective, max
+    violation).  Should the per-restart fields pass DUMP_LIMIT, a fixed seeded sample of restarts (in index order) is written."""
+    os.makedirs(path, exist_ok=True)
+    R = len(rows['f0'])
+    idx = np.arange(R)
+    fit = (DUMP_LIMIT - 8 * (len(best[3]) + 3)) // (8 * (len(rows) + 1))
+    if R > fit:
+        idx = np.sort(np.random.RandomState(0).choice(R, fit, replace=False))
+    out = {k: np.asarray(v)[idx] for k, v in rows.items()}
+    out['restart_index'] = first_index + idx
+    out['best_key'] = np.array([best[0], best[1], best[2]], dtype=np.float64)
+    out['best_x'] = np.asarray(best[3])
+    for name, a in out.items():
+        np.save(os.path.join(path, name + '.npy'), np.ascontiguousarray(a, dtype=np.float64))
 
 
 # ------------------------------------------------------------------------------------- secondary records
@@ -831,7 +858,12 @@ def main():
                     help='run the same K steps through scheme `two` and through the other lifecycle kernel as well (sidecar file)')
     ap.add_argument('--no-secondary', action='store_true', help='(default since round 6; accepted for old command lines)')
     ap.add_argument('--sdr-full', action='store_true', help='add the SDP relaxation of configs[4] at FULL size (137.6 GB, about 100 s) to the secondary records')
+    ap.add_argument('--dump-outputs', default='', metavar='DIR',
+                    help='rank 0 writes what the last timed step returned (per-restart results of its restarts, the best point) as '
+                         'DIR/<name>.npy (float64, at most 64 MB in all), after the timed region')
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
     line_fd = claim_stdout()
 
     from qcqp_amd import dist, problems
@@ -869,7 +901,7 @@ def main():
             except EngineError as ex:
                 if ex.code != E_UNSUPPORTED:
                     raise
-    K = max(args.steps, 1)
+    K = args.steps
 
     def allreduce_sum(a):
         return eng.comm_allreduce(a, 'sum')
@@ -955,6 +987,7 @@ def main():
             acc['p2_flops'] += float(out['visits2'].sum()) * 2.0 * n   # algorithmic: 2n flops per visit
             acc['p2_ms'] += cur.kernel_ms(Engine.KERNEL_CD2)
             acc['p1_ms'] += cur.kernel_ms(Engine.KERNEL_CD1)
+            acc['last'] = (out, b)
             best = acc['best']
             if best is None or dist.better_key(b[1], b[2], b[0]) < dist.better_key(best[1], best[2], best[0]):
                 acc['best'], acc['best_step'] = b, k
@@ -999,10 +1032,12 @@ def main():
         best_step = min(range(K), key=lambda k: dist.better_key(keys[k][1], keys[k][2], keys[k][0]) + (k,))
         best = (keys[best_step][0], keys[best_step][1], keys[best_step][2], Xbest[best_step])
         kernel_name, contexts = eng.last_cd_kernel(), 1
+        last_step = (o, (K - 1) * R, (keys[K - 1][0], keys[K - 1][1], keys[K - 1][2], Xbest[K - 1]))
     else:
         acc = measure_two()
         dt, sweeps1, sweeps2, p2_flops, p2_ms, p1_ms = acc['dt'], acc['sweeps1'], acc['sweeps2'], acc['p2_flops'], acc['p2_ms'], acc['p1_ms']
         best, best_step, kernel_name, contexts = acc['best'], acc['best_step'], acc['kernel'], acc['contexts']
+        last_step = (acc['last'][0], 0, acc['last'][1])
     dt = float(eng.comm_allreduce([dt], 'max')[0])
     tot = eng.comm_allreduce([sweeps1, sweeps2, p2_flops, p2_ms], 'sum')
     p2_ms_max = float(eng.comm_allreduce([p2_ms], 'max')[0])
@@ -1162,6 +1197,9 @@ def main():
                 sys.stderr.write('bench: secondary records and comparisons: %s\n' % (args.secondary_out,))
         if args.best_out and scheme == 'stream':
             np.save(args.best_out, np.asarray(Xbest))
+        if args.dump_outputs:
+            o_last, start, b_last = last_step
+            dump_outputs(args.dump_outputs, {k: o_last[k][start:start + R] for k in LAST_STEP_FIELDS}, b_last, first)
         emit_line(line_fd, line)
     if boot is not None:
         boot.close()

@@ -759,6 +759,32 @@ bench.emit_line(fd, '{"value": 1}')
     assert b'banner' in pr.stderr and b'chatter' in pr.stderr
 
 
+def test_bench_dump_outputs_float64_bounded_and_repeatable(tmp_path, monkeypatch):
+    """bench.dump_outputs (--dump-outputs DIR): every per-restart field of the last step and its best point as float64 .npy files;
+    past the size limit a seeded sample of restarts in index order, the same one on every run, with the files under the limit."""
+    sys.path.insert(0, REPO)
+    import bench
+    R, n = 1000, 16
+    rs = np.random.RandomState(5)
+    rows = {k: rs.rand(R) if k in ('f0', 'maxviol') else rs.randint(0, 50, R) for k in bench.LAST_STEP_FIELDS}
+    best = (7, 1.5, 0.0, rs.rand(n))
+    bench.dump_outputs(str(tmp_path / 'full'), rows, best, 100)
+    got = {f[:-4]: np.load(str(tmp_path / 'full' / f)) for f in os.listdir(str(tmp_path / 'full'))}
+    assert set(got) == set(bench.LAST_STEP_FIELDS) | {'restart_index', 'best_key', 'best_x'}
+    assert all(a.dtype == np.float64 for a in got.values())
+    assert all(np.array_equal(got[k], rows[k]) for k in bench.LAST_STEP_FIELDS)
+    assert np.array_equal(got['restart_index'], 100 + np.arange(R))
+    assert np.array_equal(got['best_key'], [7, 1.5, 0.0]) and np.array_equal(got['best_x'], best[3])
+    monkeypatch.setattr(bench, 'DUMP_LIMIT', 40000)
+    for d in ('a', 'b'):
+        bench.dump_outputs(str(tmp_path / d), rows, best, 0)
+    size = sum(os.path.getsize(str(tmp_path / 'a' / f)) - 128 for f in os.listdir(str(tmp_path / 'a')))     # (128-byte .npy headers)
+    assert size <= 40000
+    ia, ib = np.load(str(tmp_path / 'a' / 'restart_index.npy')), np.load(str(tmp_path / 'b' / 'restart_index.npy'))
+    assert 100 < len(ia) < R and np.array_equal(ia, ib) and np.all(np.diff(ia) > 0)
+    assert np.array_equal(np.load(str(tmp_path / 'a' / 'f0.npy')), rows['f0'][ia.astype(np.int64)])
+
+
 def test_objective_factor_found_verified_or_refused():
     """qcqp_amd.lowrank.objective_factor (pivoted Cholesky, NumPy only): a least-squares objective gives a factor of rank rows(A) that
     reproduces P0 entry by entry; an indefinite objective (MAXCUT), a rank above the limit, a matrix that is not PSD by a hair and a
