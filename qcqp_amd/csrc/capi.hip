@@ -204,6 +204,7 @@ struct qcqpmi_ctx {
     double *l2_D = nullptr, *l2_S = nullptr;
     int *l2_abort = nullptr;
     int *l2_cuslot = nullptr;    // [4096] arrival counters per compute unit of cd_life_kernel (zeroed before every launch)
+    double *l2_preslack = nullptr; int64_t l2_preslack_cap = 0;    // [K R] slack of the prebuilt columns (cd_life2_prep_launch)
     // factored objective P0 = L L^T (qcqpmi_cd_set_objective_factor): L (n16 x 16 lr_RB, zero-padded) and its fragment packs
     double *lr_L = nullptr, *lr_G = nullptr, *lr_U = nullptr; int lr_RB = 0;
     int life_version = 0;        // qcqpmi_cd_life_version: 0 = the faster one for the shape, 2 = cd_life_kernel wherever it applies, 1 = cd_phase2_qs_kernel<lifecycle> only
@@ -748,7 +749,7 @@ void qcqpmi_ctx_destroy(qcqpmi_ctx *c) {
     admm_free(c, false);
     for (void *p : c->prob_allocs) (void)hipFree(p);
     void *ptrs[] = {c->d_Fpack, c->d_Frow, c->d_mu, c->d_best_idx, c->d_best_key, c->d_comm, c->d_comm_big,   // d_gP is in prob_allocs
-                    c->dn_G, c->dn_Dg, c->dn_Ft, c->dn_prof, c->dn_state, c->d_planes, c->d_out, c->d_wS, c->d_wY, c->d_ww, c->d_wz, c->af_work, c->d_qnext, c->d_life, c->d_life_prof, c->d_bestK_idx, c->d_bestK_key, c->d_bestK_x, c->l2_scratch, c->l2_D, c->l2_S, c->l2_abort, c->l2_cuslot, c->lr_L, c->lr_G, c->lr_U};
+                    c->dn_G, c->dn_Dg, c->dn_Ft, c->dn_prof, c->dn_state, c->d_planes, c->d_out, c->d_wS, c->d_wY, c->d_ww, c->d_wz, c->af_work, c->d_qnext, c->d_life, c->d_life_prof, c->d_bestK_idx, c->d_bestK_key, c->d_bestK_x, c->l2_scratch, c->l2_D, c->l2_S, c->l2_abort, c->l2_cuslot, c->l2_preslack, c->lr_L, c->lr_G, c->lr_U};
     if (c->h_out) (void)hipHostFree(c->h_out);
     if (c->h_pin) (void)hipHostFree(c->h_pin);
     for (void *p : ptrs) if (p) (void)hipFree(p);
@@ -1597,6 +1598,19 @@ int qcqpmi_cd_stream_run(qcqpmi_ctx *c, int64_t K, int64_t R, int generate, int 
     L.seed = seed; L.seed_stride = seed_stride; L.first_index = first_index; L.first_stride = first_stride; L.viol_tol = viol_tol;
     L.sweeps1 = c->d_sweeps1; L.status1 = c->d_status1; L.ran2 = c->d_flag;
     L.prof = nullptr;
+    // the factored instantiation builds its columns ahead of the launch (cd_life_prep_kernel, every restart of the run at full
+    // occupancy) and its refill only copies them; QCQPMI_L2_PREBUILT=0: the build inside the launch, as before (A / B runs, tests)
+    const char *pre_ev = getenv("QCQPMI_L2_PREBUILT");
+    const bool pre = lr && !(pre_ev && atoi(pre_ev) == 0);
+    L.prebuilt = pre ? 1 : 0; L.preslack = nullptr;
+    if (pre) {
+        if (K * R > c->l2_preslack_cap) {
+            if (c->l2_preslack) { HIPCHK(c, spin_sync(c->stream)); (void)hipFree(c->l2_preslack); c->l2_preslack = nullptr; c->l2_preslack_cap = 0; }
+            if ((rc = dev_alloc(c, &c->l2_preslack, (size_t)(K * R)))) return rc;
+            c->l2_preslack_cap = K * R;
+        }
+        L.preslack = c->l2_preslack;
+    }
     if (c->profile) {      // qcqpmi_debug_profile: tick sums of the launch (qcqpmi_debug_life_profile)
         if (!c->d_life_prof) HIPCHK(c, hipMalloc((void **)&c->d_life_prof, 24 * sizeof(long long)));
         HIPCHK(c, hipMemsetAsync(c->d_life_prof, 0, 24 * sizeof(long long), c->stream));
@@ -1633,9 +1647,10 @@ int qcqpmi_cd_stream_run(qcqpmi_ctx *c, int64_t K, int64_t R, int generate, int 
         qa.Gpack = lr ? c->lr_G : nullptr; qa.Upack = lr ? c->lr_U : nullptr; qa.RB = lr ? c->lr_RB : 0;
         qa.nclass = c->Kreal;
         const double l0 = stnow();
-        (void)hipEventRecord(c->timers[2].beg, c->stream);
+        (void)hipEventRecord(c->timers[2].beg, c->stream);       // (the event window spans the pre-pass too)
         const double l1 = stnow();
-        hipError_t qe = (hipError_t)cd_life2_launch(qa, nmw, cs2, kind, tiles, (int)wgs, c->stream);
+        hipError_t qe = pre ? (hipError_t)cd_life2_prep_launch(c->dp, c->d_life, c->X, K * R, num_iters, tol, c->stream) : hipSuccess;
+        if (qe == hipSuccess) qe = (hipError_t)cd_life2_launch(qa, nmw, cs2, kind, tiles, (int)wgs, c->stream);
         const double l2 = stnow();
         (void)hipEventRecord(c->timers[2].end, c->stream);
         c->timers[2].valid = true;

@@ -71,6 +71,9 @@ int cd_life2_max_wgs(int nmw, int cus, int tiles);
 int cd_life2_tiles(const DevProblem &P, int nmw, int cs, int64_t restarts, int cus, int requested, int lr);
 // masked diagonal blocks + per-block scalars (device, once per problem)
 int cd_life2_pack(const DevProblem &P, double *Dpack, double *Spack, hipStream_t st);
+// the column build of every restart of a run of `life` ahead of the lifecycle launch (sets nothing in `life`: the caller sets
+// life->prebuilt, life->preslack [Rtotal]); X: the population [ceil(Rtotal / 16)][n16][16], start points in (generate = 0) and out
+int cd_life2_prep_launch(const DevProblem &P, const CdLife *life, double *X, int64_t Rtotal, int64_t num_iters, double tol, hipStream_t st);
 int cd_life2_launch(const CdLife2Args &a, int nmw, int cs, int kind, int tiles, int wgs, hipStream_t st);
 const char *cd_life2_name(int nmw, int kind, int tiles, int lr);
 

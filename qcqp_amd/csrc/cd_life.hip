@@ -1225,7 +1225,10 @@ __global__ __launch_bounds__((NMW == 3 && TILES == 1) ? 256 : 512, 2) void cd_li
             __builtin_amdgcn_s_setprio(3);
             LG const CdLife *lf = l2_g(lifep);
             const long long pt0 = lf->prof ? (long long)__builtin_amdgcn_s_memtime() : 0;
-            const int lf_generate = lf->generate, lf_phase1 = lf->phase1;
+            // prebuilt (cd_life_prep_kernel): the column is the restart's point after phase 1 in b.X, its slack, gate and phase-1
+            // counters in global memory -- copy them, nothing else
+            const int lf_pre = LR ? lf->prebuilt : 0;       // (the factored instantiation only: the others keep their code)
+            const int lf_generate = lf->generate && !lf_pre, lf_phase1 = lf->phase1 && !lf_pre;
             const double lf_viol_tol = lf->viol_tol;
             const int e0 = P.cptr[P.krep[0]];
             const double cp = P.cp[e0], cq = P.cq[e0], cr = P.cr[e0];
@@ -1237,7 +1240,7 @@ __global__ __launch_bounds__((NMW == 3 && TILES == 1) ? 256 : 512, 2) void cd_li
                     if (l2_tl(sid, ct, TD)[cc] < 0) for (int64_t j = tid; j < n16; j += NT) Xg[j * 16 + cc] = 0.0;
                     continue;
                 }
-                if (!lf_generate) {
+                if (!lf_generate) {        // (also a prebuilt column)
                     const int id = l2_tl(sid, ct, TD)[cc];
                     LG const double *src = l2_g(a0.b.X) + ((int64_t)(id >> 4) * n16) * 16 + (id & 15);
                     for (int64_t j0 = tid; j0 < n16; j0 += 4 * NT) {
@@ -1358,7 +1361,7 @@ __global__ __launch_bounds__((NMW == 3 && TILES == 1) ? 256 : 512, 2) void cd_li
             __syncthreads();
             for (int c = 0; c < NS; c++) {
                 const int ct = c >> 4, cc = c & 15;
-                if (!l2_tl(snew, ct, TD)[cc]) continue;
+                if (lf_pre || !l2_tl(snew, ct, TD)[cc]) continue;
                 LG const double *Xg = Xg0 + (int64_t)ct * n16 * 16;
                 double v = -QM_INF;
                 for (int64_t i = tid; i < P.n; i += NT) {
@@ -1381,9 +1384,18 @@ __global__ __launch_bounds__((NMW == 3 && TILES == 1) ? 256 : 512, 2) void cd_li
             __syncthreads();
             if (tid < NS && l2_tl(snew, tid >> 4, TD)[tid & 15]) {
                 const int st = tid >> 4, sc = tid & 15;
-                const double mvx = l2_unkey(l2_tl(p1key, st, TD)[sc]);
+                double mvx;
+                if (lf_pre) {
+                    const int id = l2_tl(sid, st, TD)[sc];
+                    mvx = l2_g(lf->preslack)[id];
+                    l2_tl(p1sw, st, TD)[sc] = (int)l2_g(lf->sweeps1)[id];
+                    l2_tl(p1st, st, TD)[sc] = l2_g(lf->status1)[id];
+                    l2_tl(gatep, st, TD)[sc] = l2_g(lf->ran2)[id];
+                } else {
+                    mvx = l2_unkey(l2_tl(p1key, st, TD)[sc]);
+                    l2_tl(gatep, st, TD)[sc] = (mvx < lf_viol_tol && l2_tl(p1st, st, TD)[sc] == 0) ? 1 : 0;
+                }
                 l2_tl(slk, st, TD)[sc] = mvx;
-                l2_tl(gatep, st, TD)[sc] = (mvx < lf_viol_tol && l2_tl(p1st, st, TD)[sc] == 0) ? 1 : 0;
                 L2_STORE_SETS(st, sc, mvx)
             }
             __syncthreads();
@@ -1539,6 +1551,122 @@ __global__ __launch_bounds__((NMW == 3 && TILES == 1) ? 256 : 512, 2) void cd_li
 
 #undef L2_STORE_SETS
 
+// ---- preparation pre-pass (CdLife::prebuilt, single-class kinds): the refill's column build -- start point, phase 1, slack and
+// gate -- for ALL restarts of the run ahead of the lifecycle launch, at full occupancy instead of by four waves between episodes
+// (where it took 19 % of a workgroup's time and left the neighbour's roles unpaired meanwhile).  A workgroup takes one tile of
+// 16 restarts: thread (g, s) = (tid >> 4, tid & 15) owns the coordinate pairs 2 g + 32 k, 2 g + 32 k + 1 of slot s, so that a
+// row of the tile (16 restarts, 128 B) is one access.  Same visits, same termination rule, same exact max reductions as the
+// build: the same bits.  Out: the point after phase 1 in b.X (the refill copies it, write-out overwrites it), sweeps1 / status1 /
+// ran2 at the restart's index (write-out writes the same values again) and the slack in CdLife::preslack.
+constexpr int L2P_NT = 256;
+__global__ __launch_bounds__(L2P_NT) void cd_life_prep_kernel(DevProblem P, const CdLife *life, double *X, int64_t num_iters, double tol) {
+    __shared__ unsigned long long key[16];
+    __shared__ int upd[16], st1[16], fin[16], sw[16], nact;
+    const int tid = threadIdx.x, s = tid & 15, g = tid >> 4;
+    LG const CdLife *lf = l2_g(life);
+    const int64_t id = (int64_t)blockIdx.x * 16 + s;
+    const bool valid = id < lf->Rtotal;
+    const int64_t n = P.n, n16 = P.n16;
+    LG double *Xt = l2_g(X) + (int64_t)blockIdx.x * n16 * 16 + s;        // column s of the tile: coordinate j at Xt[16 j]
+    const double viol_tol = lf->viol_tol;
+    uint64_t sd = 0, gidx = 0;
+    if (valid) {
+        const uint64_t pop = (uint64_t)id / (uint64_t)lf->Rpop, rho = (uint64_t)id % (uint64_t)lf->Rpop;
+        sd = lf->seed + pop * lf->seed_stride;
+        gidx = lf->first_index + pop * lf->first_stride + rho;
+    }
+    if (lf->generate && valid) {
+        for (int64_t j = 2 * g; j < n16; j += 32) {
+            double xo = 0.0;
+            const double xe = (j < n) ? l2_keyed_normal_pair(sd, gidx, (uint64_t)j, &xo) : 0.0;
+            Xt[16 * j] = xe;
+            Xt[16 * (j + 1)] = (j + 1 < n) ? xo : 0.0;
+        }
+    }
+    const int e0 = P.cptr[P.krep[0]];
+    const double cp = P.cp[e0], cq = P.cq[e0], cr = P.cr[e0];
+    const int rel = P.crel[e0];
+    if (tid < 16) { fin[tid] = valid ? 0 : 1; sw[tid] = 0; st1[tid] = 0; }
+    if (lf->phase1) {
+        const bool band2 = cq == 0.0 && rel == RELOP_EQ && cp > 1e-4 && cr < -1e-3;      // the build's choice of visit
+        for (int64_t t = 0; t < num_iters; t++) {
+            if (tid < 16) { key[tid] = l2_key(-QM_INF); upd[tid] = 0; }
+            __syncthreads();
+            if (tid == 0) { int c = 0; for (int k = 0; k < 16; k++) c += fin[k] ? 0 : 1; nact = c; }
+            __syncthreads();
+            if (nact == 0) break;
+            double va = -QM_INF;
+            int moved = 0, stv = 0;
+            if (!fin[s]) {
+                for (int64_t j = 2 * g; j < n; j += 32) {
+                    if (band2) {
+                        const int64_t i2[2] = {j, j + 1};
+                        const bool on2[2] = {true, j + 1 < n};
+                        double x2[2] = {Xt[16 * j], on2[1] ? Xt[16 * (j + 1)] : 1.0};
+                        P1Visit V2[2];
+                        p1_band_visit_n<2>(cp, cq, cr, i2, x2, on2, tol, viol_tol, sd, gidx, t, V2);
+#pragma unroll
+                        for (int k = 0; k < 2; k++)
+                            if (on2[k]) {
+                                if (V2[k].moved) { Xt[16 * i2[k]] = x2[k]; moved = 1; }
+                                if (V2[k].status) stv = V2[k].status;
+                                va = V2[k].vafter > va ? V2[k].vafter : va;
+                            }
+                    } else {
+                        for (int64_t i = j; i < j + 2 && i < n; i++) {
+                            int fl = 0;
+                            double v = 0.0;
+                            const double xi = l2_p1_visit(cp, cq, cr, rel, i, Xt[16 * i], tol, viol_tol, sd, gidx, t, &fl, &v);
+                            if (fl & 1) { Xt[16 * i] = xi; moved = 1; }
+                            if (fl >> 8) stv = -(fl >> 8);
+                            va = v > va ? v : va;
+                        }
+                    }
+                }
+            }
+            // the lanes of a slot within the wave: s, s + 16, s + 32, s + 48
+#pragma unroll
+            for (int o = 16; o <= 32; o <<= 1) {
+                const double w = __shfl_xor(va, o, 64);
+                va = w > va ? w : va;
+                moved |= __shfl_xor(moved, o, 64);
+            }
+            if ((tid & 63) < 16 && !fin[s]) { atomicMax(&key[s], l2_key(va)); if (moved) upd[s] = 1; }
+            if (stv) st1[s] = stv;
+            __syncthreads();
+            if (tid < 16 && !fin[tid]) {
+                sw[tid]++;
+                // done when feasible enough (qcqp.py:111); a sweep without any update is a fixed point of the map
+                if (l2_unkey(key[tid]) < viol_tol || !upd[tid]) fin[tid] = 1;
+            }
+        }
+    }
+    // max violation of the point = the slack of phase 2 (qcqp.py:157), and the gate (qcqp.py:189)
+    __syncthreads();
+    if (tid < 16) key[tid] = l2_key(-QM_INF);
+    __syncthreads();
+    double v = -QM_INF;
+    if (valid)
+        for (int64_t j = 2 * g; j < n; j += 32)
+            for (int64_t i = j; i < j + 2 && i < n; i++) {
+                const double x = Xt[16 * i];
+                const double f = (cp * x + cq) * x + cr;
+                const double w = (rel == RELOP_EQ) ? fabs(f) : (f > 0.0 ? f : 0.0);
+                v = w > v ? w : v;
+            }
+#pragma unroll
+    for (int o = 16; o <= 32; o <<= 1) { const double w = __shfl_xor(v, o, 64); v = w > v ? w : v; }
+    if ((tid & 63) < 16 && valid) atomicMax(&key[s], l2_key(v));
+    __syncthreads();
+    if (tid < 16 && valid) {
+        const double mvx = l2_unkey(key[tid]);
+        l2_g(const_cast<double *>(lf->preslack))[id] = mvx;
+        l2_g(lf->sweeps1)[id] = sw[tid];
+        l2_g(lf->status1)[id] = st1[tid];
+        l2_g(lf->ran2)[id] = (mvx < viol_tol && st1[tid] == 0) ? 1 : 0;
+    }
+}
+
 // strictly upper triangle of the diagonal blocks (zeros elsewhere) and the per-block scalars the chain stages
 __global__ void l2_pack_kernel(DevProblem P, double *Dpack, double *Spack) {
     const int b = blockIdx.x, t = threadIdx.x;            // 256 threads: entry (row t >> 4, column t & 15) of block b
@@ -1597,6 +1725,11 @@ bool cd_life2_factor_ok(const DevProblem &P, int64_t r) {
 int cd_life2_pack_factor(const double *Lrow, double *Gpack, double *Upack, int NB, int RB, hipStream_t st) {
     const int64_t tot = (int64_t)NB * RB * 256;
     hipLaunchKernelGGL(l2_pack_factor_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, Lrow, Gpack, Upack, NB, RB);
+    return (int)hipGetLastError();
+}
+
+int cd_life2_prep_launch(const DevProblem &P, const CdLife *life, double *X, int64_t Rtotal, int64_t num_iters, double tol, hipStream_t st) {
+    hipLaunchKernelGGL(cd_life_prep_kernel, dim3((unsigned)((Rtotal + 15) / 16)), dim3(L2P_NT), 0, st, P, life, X, num_iters, tol);
     return (int)hipGetLastError();
 }
 

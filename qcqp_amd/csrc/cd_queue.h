@@ -43,6 +43,10 @@ struct CdLife {
     uint8_t *ran2;               // [Rtotal] passed the gate (qcqp.py:189)
     long long *prof;             // optional [8]: ticks (s_memtime) summed over the workgroups -- 0 column build, 1 whole launch, 2 episodes,
                                  // 3 columns built, 4 the normals' share of 0, 5 the roles (episodes proper); nullptr: off
+    // cd_life_kernel only: 1 = the columns were built ahead of the launch (cd_life2_prep_launch): b.X holds every restart's point after
+    // phase 1, sweeps1 / status1 / ran2 its phase-1 sweeps, status and gate, preslack [Rtotal] its slack; the refill copies them
+    int prebuilt;
+    const double *preslack;
 };
 
 struct CdQueueArgs {
