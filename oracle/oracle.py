@@ -90,6 +90,8 @@ def lib():
                                        C.c_void_p, _ip]
         L.orc_improve_cd.argtypes = [C.c_void_p, _dp, C.c_int64, C.c_double, C.c_double,
                                      C.c_int, C.c_void_p, _ip, _ip]
+        L.orc_improve_cd_sep.argtypes = L.orc_improve_cd.argtypes
+        L.orc_improve_cd_sep.restype = C.c_int
         L.orc_cd_trace.restype = None
         L.orc_cd_trace.argtypes = [_dp, C.c_int64]
         L.orc_cd_trace_len.restype = C.c_int64
@@ -264,6 +266,19 @@ class Problem:
                                   _i(s1), _i(s2))
         if rc:
             raise RuntimeError('oracle improve_cd failed rc=%d' % rc)
+        return x, s1, s2
+
+    def improve_cd_sep(self, x, num_iters=1000, viol_tol=1e-2, tol=1e-4, phase1=True, rng=None):
+        """improve_cd for separable problems (every constraint touches one coordinate) at O(n) per phase-2 move instead of
+        O(n^2) per visit: the same stats and draws, phase 1 bit-identical, phase 2 within rounding of t1 / t0.
+        Raises RuntimeError (rc=-5) for a coupled problem."""
+        x = _vec(x).copy()
+        s1 = np.zeros(3, dtype=np.int64)
+        s2 = np.zeros(3, dtype=np.int64)
+        rng = rng or Rng(RNG_MT, 0, from_numpy_global=True)
+        rc = lib().orc_improve_cd_sep(self.h, _d(x), num_iters, viol_tol, tol, int(phase1), rng.h, _i(s1), _i(s2))
+        if rc:
+            raise RuntimeError('oracle improve_cd_sep failed rc=%d' % rc)
         return x, s1, s2
 
     def improve_cd_traced(self, x, num_iters=1000, viol_tol=1e-2, tol=1e-4, rng=None):

@@ -414,9 +414,8 @@ static double onevar_eval(double p, double q, double r, double x, int *status) {
     return x * (p * x + q) + r;
 }
 
-int orc_onevar_qcqp(double p0, double q0, double r0, const double *fs3,
-                    const int *relops, int64_t mf, double s, orc_rng *g,
-                    double *xout, double *C_out, int64_t Ccap, int64_t *nC_out) {
+/* The feasible set of onevar_qcqp (utilities.py:244-263): *Cp (malloc'd, 2 doubles per interval) and its size. */
+static int64_t onevar_feasible_set(const double *fs3, const int *relops, int64_t mf, double s, double **Cp) {
     int64_t cap = 4 * mf + 2;
     event_t *ev = (event_t *)malloc(sizeof(event_t) * (size_t)(2 * cap));
     int64_t ne = 0;
@@ -454,11 +453,12 @@ int orc_onevar_qcqp(double p0, double q0, double r0, const double *fs3,
         }
     }
     free(ev);
-    if (nC_out) *nC_out = nC;
-    if (C_out)
-        for (int64_t i = 0; i < nC && i < Ccap; i++) { C_out[2 * i] = C[2 * i]; C_out[2 * i + 1] = C[2 * i + 1]; }
-    if (nC == 0) { free(C); return 0; }
+    *Cp = C;
+    return nC;
+}
 
+/* The choice over a non-empty feasible set C (utilities.py:264-288); frees C. */
+static int onevar_pick(double p0, double q0, double r0, double *C, int64_t nC, orc_rng *g, double *xout) {
     int ret = 1;
     if (p0 == 0.0 && q0 == 0.0) {
         int64_t c = orc_rng_choice(g, nC);
@@ -488,6 +488,18 @@ int orc_onevar_qcqp(double p0, double q0, double r0, const double *fs3,
     else *xout = bestxs[orc_rng_choice(g, nb)];
     free(C); free(bestxs);
     return ret;
+}
+
+int orc_onevar_qcqp(double p0, double q0, double r0, const double *fs3,
+                    const int *relops, int64_t mf, double s, orc_rng *g,
+                    double *xout, double *C_out, int64_t Ccap, int64_t *nC_out) {
+    double *C;
+    int64_t nC = onevar_feasible_set(fs3, relops, mf, s, &C);
+    if (nC_out) *nC_out = nC;
+    if (C_out)
+        for (int64_t i = 0; i < nC && i < Ccap; i++) { C_out[2 * i] = C[2 * i]; C_out[2 * i + 1] = C[2 * i + 1]; }
+    if (nC == 0) { free(C); return 0; }
+    return onevar_pick(p0, q0, r0, C, nC, g, xout);
 }
 
 /* ----------------------------------------------------- coordinate descent */
@@ -743,6 +755,238 @@ int orc_cd_phase2_incremental(const orc_prob *p, const double *P0d, double *x, i
     }
     if (stats) { stats[0] = sweeps; stats[1] = visits; stats[2] = accepted; }
     free(coord); free(cnt); free(list); free(fill); free(fs3); free(relops); free(gv);
+    return rc;
+}
+
+/* ------------------------------------- coordinate descent, separable problems */
+
+/* Every constraint of a separable problem touches one coordinate.  Restated per coordinate, the reference's
+ * arithmetic collapses (x finite): at coordinate i, a constraint on another coordinate has t2 = t1 = 0 and is filtered
+ * out (qcqp.py:115-116, 164-166); a constraint on i has t0 = 0.0 + r bit for bit (every other term of
+ * (P.dot(z)+q).dot(z) is a signed zero), and its value at x is 0.0 + (row_i + q_i) x_i + r, again bit for bit.  So
+ * phase 1 and every max violation cost O(own constraints) instead of O(m n); phase 2 keeps the off-diagonal row sums
+ * of P0 x and f0(x) incrementally (O(row nnz) per accepted move). */
+typedef struct {
+    int64_t *cnt;   /* n + 1: constraints of coordinate i are list[cnt[i] .. cnt[i+1]) */
+    int64_t *list;  /* constraint indices k (1..m), ascending within a coordinate */
+    int64_t *coord; /* m: the coordinate of constraint k at coord[k-1] */
+    int64_t maxc;
+} sep_t;
+
+static void sep_free(sep_t *s) { free(s->cnt); free(s->list); free(s->coord); }
+
+/* -5 if some constraint touches two coordinates or none (same test as orc_cd_phase2_incremental) */
+static int sep_build(const orc_prob *p, sep_t *s) {
+    const int64_t n = p->n, m = p->m;
+    s->coord = (int64_t *)malloc(sizeof(int64_t) * (size_t)(m > 0 ? m : 1));
+    s->cnt = (int64_t *)calloc((size_t)n + 1, sizeof(int64_t));
+    s->list = (int64_t *)malloc(sizeof(int64_t) * (size_t)(m > 0 ? m : 1));
+    for (int64_t k = 1; k <= m; k++) {
+        const quad_t *f = &p->f[k];
+        int64_t c = -1;
+        int ok = 1;
+        for (int64_t i = 0; i < n && ok; i++) {
+            for (int64_t jj = f->ptr[i]; jj < f->ptr[i + 1]; jj++) {
+                if (f->val[jj] == 0.0) continue;
+                if (f->idx[jj] != i || (c >= 0 && c != i)) { ok = 0; break; }
+                c = i;
+            }
+            if (f->q[i] != 0.0) { if (c >= 0 && c != i) ok = 0; c = i; }
+        }
+        if (!ok || c < 0) { sep_free(s); return -5; }
+        s->coord[k - 1] = c;
+        s->cnt[c + 1]++;
+    }
+    for (int64_t i = 0; i < n; i++) s->cnt[i + 1] += s->cnt[i];
+    int64_t *fill = (int64_t *)malloc(sizeof(int64_t) * (size_t)(n > 0 ? n : 1));
+    for (int64_t i = 0; i < n; i++) fill[i] = s->cnt[i];
+    for (int64_t k = 1; k <= m; k++) s->list[fill[s->coord[k - 1]]++] = k;
+    free(fill);
+    s->maxc = 1;
+    for (int64_t i = 0; i < n; i++) if (s->cnt[i + 1] - s->cnt[i] > s->maxc) s->maxc = s->cnt[i + 1] - s->cnt[i];
+    return 0;
+}
+
+/* gather_onevars at coordinate i of a separable problem: the constraints of i, coefficients as orc_onevar_coeffs forms them */
+static int64_t sep_gather(const orc_prob *p, const sep_t *s, const double *x, int64_t i, double *fs3, int *relops) {
+    int64_t mf = 0;
+    for (int64_t e = s->cnt[i]; e < s->cnt[i + 1]; e++) {
+        const quad_t *f = &p->f[s->list[e]];
+        double t2 = 0.0, row = 0.0;
+        for (int64_t jj = f->ptr[i]; jj < f->ptr[i + 1]; jj++) {
+            int64_t j = f->idx[jj];
+            if (j == i) t2 += f->val[jj];
+            else row += f->val[jj] * x[j];
+        }
+        const double t1 = 2.0 * row + f->q[i];
+        if (t2 != 0.0 || t1 != 0.0) {
+            fs3[3 * mf] = t2; fs3[3 * mf + 1] = t1; fs3[3 * mf + 2] = 0.0 + f->r;
+            relops[mf++] = f->relop;
+        }
+    }
+    return mf;
+}
+
+/* orc_max_violation of a separable problem: constraint k evaluates from the row of its coordinate alone */
+static double sep_max_violation(const orc_prob *p, const sep_t *s, const double *x) {
+    double mv = -INFINITY;
+    for (int64_t k = 1; k <= p->m; k++) {
+        const quad_t *f = &p->f[k];
+        const int64_t c = s->coord[k - 1];
+        double row = 0.0;
+        for (int64_t jj = f->ptr[c]; jj < f->ptr[c + 1]; jj++) row += f->val[jj] * x[f->idx[jj]];
+        const double acc = 0.0 + (row + f->q[c]) * x[c];
+        const double v = viol_of(acc + f->r, f->relop);
+        if (v > mv) mv = v;
+    }
+    return mv;
+}
+
+/* 1 if onevar_pick's answer over C may depend on the rounding of r0: the objective's finite endpoint values that come
+ * within a relative 1e-12 of the smallest one sit at two different points (a near tie that r0 is added to). */
+static int onevar_near_tie(double p0, double q0, double r0, const double *C, int64_t nC) {
+    if (p0 == 0.0 && q0 == 0.0) return 0;
+    const double x0 = (p0 > 0.0) ? -q0 / (2.0 * p0) : NAN;
+    for (int64_t i = 0; i < nC; i++)
+        if (C[2 * i] <= x0 && x0 <= C[2 * i + 1]) return 0;
+    double best = INFINITY;
+    for (int64_t e = 0; e < 2 * nC; e++)
+        if (isfinite(C[e])) { const double v = C[e] * (p0 * C[e] + q0) + r0; if (v < best) best = v; }
+    if (!isfinite(best)) return 0;
+    const double tol = 1e-12 * fmax(fabs(best), fabs(r0));
+    double first = NAN;
+    for (int64_t e = 0; e < 2 * nC; e++) {
+        if (!isfinite(C[e])) continue;
+        const double v = C[e] * (p0 * C[e] + q0) + r0;
+        if (fabs(v - best) > tol) continue;
+        if (first != first) first = C[e];
+        else if (C[e] != first) return 1;
+    }
+    return 0;
+}
+
+static int sep_phase1(const orc_prob *p, const sep_t *sp, double *x, int64_t num_iters, double viol_tol, double tol,
+                      orc_rng *g, int64_t *stats) {
+    const int64_t n = p->n;
+    double *fs3 = (double *)malloc(sizeof(double) * 3 * (size_t)sp->maxc);
+    int *relops = (int *)malloc(sizeof(int) * (size_t)sp->maxc);
+    int64_t update_counter = 0, sweeps = 0, visits = 0, accepted = 0;
+    double viol_last = INFINITY;
+    int rc = 0;
+    for (int64_t t = 0; t < num_iters && rc == 0; t++) {
+        if (viol_last < viol_tol) break;
+        sweeps++;
+        for (int64_t i = 0; i < n; i++) {
+            visits++;
+            int64_t mf = sep_gather(p, sp, x, i, fs3, relops);
+            if (mf == 0) { rc = -3; break; }
+            double viol = -INFINITY;
+            for (int64_t k = 0; k < mf; k++) {
+                int st = 0;
+                double v = viol_of(onevar_eval(fs3[3 * k], fs3[3 * k + 1], fs3[3 * k + 2], x[i], &st), relops[k]);
+                if (v > viol) viol = v;
+            }
+            double new_xi = x[i], new_viol = viol;
+            double ss = -tol, es = viol - viol_tol;
+            uint32_t it = 0;
+            while (es - ss > tol) {
+                double s = (ss + es) / 2.0;
+                double xi;
+                rng_ctx(g, (uint32_t)i, (uint32_t)t, it++);
+                int got = orc_onevar_qcqp(0.0, 0.0, 0.0, fs3, relops, mf, s, g, &xi, NULL, 0, NULL);
+                if (got < 0) { rc = got; break; }
+                if (!got) ss = s;
+                else { new_xi = xi; new_viol = s; es = s; }
+            }
+            if (rc) break;
+            if (new_viol < viol) { x[i] = new_xi; update_counter = 0; accepted++; }
+            else {
+                update_counter++;
+                if (update_counter == n) break;
+            }
+        }
+        if (rc) break;
+        viol_last = sep_max_violation(p, sp, x);
+    }
+    if (stats) { stats[0] = sweeps; stats[1] = visits; stats[2] = accepted; }
+    free(fs3); free(relops);
+    return rc;
+}
+
+static int sep_phase2(const orc_prob *p, const sep_t *sp, double *x, int64_t num_iters, double tol, orc_rng *g,
+                      int64_t *stats) {
+    const int64_t n = p->n;
+    const quad_t *f0 = &p->f[0];
+    double *fs3 = (double *)malloc(sizeof(double) * 3 * (size_t)sp->maxc);
+    int *relops = (int *)malloc(sizeof(int) * (size_t)sp->maxc);
+    double *diag = (double *)malloc(sizeof(double) * (size_t)(n > 0 ? n : 1));
+    double *rowx = (double *)malloc(sizeof(double) * (size_t)(n > 0 ? n : 1));   /* sum_{j != i} P0[i,j] x[j] */
+    for (int64_t i = 0; i < n; i++) {
+        double t2 = 0.0;
+        for (int64_t jj = f0->ptr[i]; jj < f0->ptr[i + 1]; jj++) if (f0->idx[jj] == i) t2 += f0->val[jj];
+        diag[i] = t2;
+    }
+    const double viol = sep_max_violation(p, sp, x);
+    int64_t update_counter = 0, sweeps = 0, visits = 0, accepted = 0;
+    int converged = 0, rc = 0;
+    for (int64_t t = 0; t < num_iters && !converged && rc == 0; t++) {
+        sweeps++;
+        /* exact refresh, in orc_onevar_coeffs' / quad_eval_skip's order: no drift carries over from one sweep to the next */
+        for (int64_t i = 0; i < n; i++) {
+            double row = 0.0;
+            for (int64_t jj = f0->ptr[i]; jj < f0->ptr[i + 1]; jj++)
+                if (f0->idx[jj] != i) row += f0->val[jj] * x[f0->idx[jj]];
+            rowx[i] = row;
+        }
+        double fcur = quad_eval_skip(f0, n, x, -1);
+        for (int64_t i = 0; i < n; i++) {
+            visits++;
+            const double xi = x[i], t2 = diag[i];
+            const double t1 = 2.0 * rowx[i] + f0->q[i];
+            double t0 = fcur - xi * (t2 * xi + t1);
+            int64_t mf = sep_gather(p, sp, x, i, fs3, relops);
+            double *C;
+            int64_t nC = onevar_feasible_set(fs3, relops, mf, viol, &C);
+            int got = 0;
+            double new_xi = xi;
+            rng_ctx(g, (uint32_t)i, (uint32_t)t | 0x80000000u, 0);
+            if (nC == 0) free(C);
+            else {
+                if (onevar_near_tie(t2, t1, t0, C, nC)) t0 = quad_eval_skip(f0, n, x, i);
+                got = onevar_pick(t2, t1, t0, C, nC, g, &new_xi);
+            }
+            if (got < 0) { rc = got; break; }
+            if (got && fabs(new_xi - xi) > tol) {
+                const double d = new_xi - xi;
+                for (int64_t jj = f0->ptr[i]; jj < f0->ptr[i + 1]; jj++)   /* symmetric: column i = row i */
+                    if (f0->idx[jj] != i) rowx[f0->idx[jj]] += f0->val[jj] * d;
+                fcur = t0 + new_xi * (t2 * new_xi + t1);
+                x[i] = new_xi; update_counter = 0; accepted++;
+            } else {
+                update_counter++;
+                if (update_counter == n) { converged = 1; break; }
+            }
+        }
+    }
+    if (stats) { stats[0] = sweeps; stats[1] = visits; stats[2] = accepted; }
+    free(fs3); free(relops); free(diag); free(rowx);
+    return rc;
+}
+
+/* orc_improve_cd for separable problems: same stats, same draws (both RNG modes), same error codes; -5 if not separable.
+ * Phase 1 and the gate are bit-identical to the restatement; phase 2 reads t1 / t0 from the incremental sums, refreshed
+ * exactly at every sweep start, and recomputes t0 in the restatement's order where the objective's candidates nearly tie. */
+int orc_improve_cd_sep(const orc_prob *p, double *x, int64_t num_iters, double viol_tol,
+                       double tol, int phase1, orc_rng *g, int64_t *stats1, int64_t *stats2) {
+    int rc = 0;
+    if (stats1) stats1[0] = stats1[1] = stats1[2] = 0;
+    if (stats2) stats2[0] = stats2[1] = stats2[2] = 0;
+    sep_t sp;
+    if (sep_build(p, &sp)) return -5;
+    if (phase1) rc = sep_phase1(p, &sp, x, num_iters, viol_tol, tol, g, stats1);
+    if (!rc && sep_max_violation(p, &sp, x) < viol_tol)
+        rc = sep_phase2(p, &sp, x, num_iters, tol, g, stats2);
+    sep_free(&sp);
     return rc;
 }
 

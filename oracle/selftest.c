@@ -79,6 +79,18 @@ int main(void) {
     (void)orc_rng_choice(g, 3);
     if (orc_improve_cd(p, x, 30, 1e-2, 1e-4, 1, g, s1, s2)) return 12;
     orc_rng_free(g);
+    /* the fast separable driver against the restatement, keyed stream, phase 1 on and off (the second start fails the gate) */
+    for (int ph = 1; ph >= 0; ph--) {
+        int64_t t1[3], t2[3];
+        for (int j = 0; j < N; j++) x[j] = y[j] = orc_keyed_normal(7, 4, (uint64_t)j);
+        g = orc_rng_new(ORC_RNG_KEYED, 99);
+        orc_rng_set_restart(g, 4);
+        if (orc_improve_cd(p, x, 40, 1e-2, 1e-4, ph, g, s1, s2)) return 17;
+        if (orc_improve_cd_sep(p, y, 40, 1e-2, 1e-4, ph, g, t1, t2)) return 18;
+        for (int j = 0; j < 3; j++) if (s1[j] != t1[j] || s2[j] != t2[j]) return 19;
+        for (int j = 0; j < N; j++) if (!(fabs(x[j] - y[j]) <= 1e-12)) { fprintf(stderr, "sep mismatch %d %.17g %.17g\n", j, x[j], y[j]); return 20; }
+        orc_rng_free(g);
+    }
     /* onecons + ADMM phase 1 with the exact eigenpairs of e_k e_k^T: identity basis */
     static double lmb[N * N], Q[N * N * N], out[N];
     for (int k = 0; k < N; k++) for (int j = 0; j < N; j++) {

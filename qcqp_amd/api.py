@@ -270,23 +270,25 @@ class QCQP(object):
         return self._publish(f0, mv)
 
     def _objective_factor(self, enable=True):
-        """Once per problem: P0 = L L^T of low rank (a least-squares objective: rank = rows of A) -> the lifecycle kernel carries
-        L^T X instead of multiplying with P0 (qcqp_amd.lowrank.objective_factor, qcqpmi_cd_set_objective_factor).  Tried for a
-        dense-enough P0 with a positive diagonal of 256 <= n <= 4096; `factor=False` in improve() switches it off."""
+        """Once per problem, the first time it is wanted: P0 = L L^T of low rank (a least-squares objective: rank = rows of A) ->
+        the lifecycle kernel carries L^T X instead of multiplying with P0 (qcqp_amd.lowrank.objective_factor,
+        qcqpmi_cd_set_objective_factor).  Tried for a dense-enough P0 with a positive diagonal of 256 <= n <= 4096; `factor=False`
+        in improve() switches it off for that call."""
         want = bool(enable)
-        state = getattr(self, '_factor_state', None)
-        if state is None:
+        state = getattr(self, '_factor_state', 'off')     # what the engine holds
+        if want and not getattr(self, '_factor_tried', False):
+            # computed the first time it is wanted: a factor=False call before leaves the question open
+            self._factor_tried = True
             L = None
             f0 = self.qcqp_form.f0
             n = self.n
-            if want and 256 <= n <= 4096:
+            if 256 <= n <= 4096:
                 from .lowrank import objective_factor
                 P0 = f0.P.toarray() if hasattr(f0.P, 'toarray') else np.asarray(f0.P)
                 if np.all(np.diag(P0) > 0.0):
                     L = objective_factor(P0, max_rank=min(288, n // 2))
             self._factor_L = L
-            state = self._factor_state = 'off'
-        target = 'on' if (want and self._factor_L is not None) else 'off'
+        target = 'on' if (want and getattr(self, '_factor_L', None) is not None) else 'off'
         if target != state:
             try:
                 self.engine.cd_set_objective_factor(self._factor_L if target == 'on' else None)

@@ -556,9 +556,35 @@ __global__ void zs_update_kernel(double *__restrict__ Xtm, const double *__restr
     if (threadIdx.x == 0) atomicMax(resid_bits, (unsigned long long)__double_as_longlong(red[0]));   // non-negative doubles order like integers
 }
 
+// R = I - M X (tile-major) with every product and sum carried in double-double (TwoProduct by fma, TwoSum): the residual of an
+// inverse that is already at fp64 rounding level, exact to a few units of 1e-32 -- what the refinement step X <- X + X R needs.
+// (An fp64 GEMM cannot give it: its own rounding, ~sqrt(n) eps, is the size of the residual.)  One thread per entry.
+__global__ void zs_resid_dd_kernel(const double *__restrict__ Mtm, const double *__restrict__ Xtm, int64_t n16, double *__restrict__ Rtm) {
+    const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= n16 * n16) return;
+    const int64_t t = idx / (n16 * 16), rem = idx % (n16 * 16), i = rem / 16, j = 16 * t + (rem & 15);
+    double s = (i == j) ? 1.0 : 0.0, e = 0.0;            // s + e = I_ij - sum_k M_ik X_kj
+    for (int64_t k = 0; k < n16; k++) {
+        const double a = Mtm[(k >> 4) * n16 * 16 + i * 16 + (k & 15)];
+        const double b = Xtm[t * n16 * 16 + k * 16 + (j & 15)];
+        const double p = -a * b;
+        const double pe = fma(-a, b, -p);                 // -a b = p + pe exactly
+        const double u = s + p, v = u - s;
+        e += ((s - (u - v)) + (p - v)) + pe;              // s + p = u + (TwoSum error)
+        s = u;
+    }
+    Rtm[idx] = s + e;
+}
+
+__global__ void zs_add_kernel(double *__restrict__ Xtm, const double *__restrict__ Utm, int64_t tot) {
+    const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx < tot) Xtm[idx] += Utm[idx];
+}
+
 // (2 (P0 + rho m I))^-1 on the device, left fragment-packed for the z-update GEMM of qcqpmi_admm_run (Minv = NULL).
 //   X_{k+1} = X_k (2 I - M X_k),  X_0 = I / ||M||_inf  (M symmetric positive definite: converges quadratically once
-//   ||I - M X|| < 1, about log2(cond M) + 6 iterations).  resid_out = max |I - M X| of the last iteration checked.
+//   ||I - M X|| < 1, about log2(cond M) + 6 iterations), then one refinement step with the residual in double-double.
+//   resid_out = (max |I - M X| of the last iteration checked)^2: the estimate for the iterate before the refinement.
 int qcqpmi_admm_zsolver_device(qcqpmi_ctx *c, double rho, int64_t max_iter, double *resid_out, int64_t *iters_out) {
     if (!c) return QCQPMI_EINVAL;
     if (!c->finalized) return fail(c, QCQPMI_ESTATE, "admm_zsolver_device: context not finalized");
@@ -608,6 +634,15 @@ int qcqpmi_admm_zsolver_device(qcqpmi_ctx *c, double rho, int64_t max_iter, doub
             return fail(c, QCQPMI_EREFERENCE, "admm_zsolver_device: no contraction (is P0 + rho m I positive definite?)");
     }
     if (!(resid < 1e-7)) return fail(c, QCQPMI_EREFERENCE, "admm_zsolver_device: not converged after %lld iterations (residual %.3e)", (long long)it, resid);
+    // one refinement step from the converged iterate: X <- X + X (I - M X) with the residual in double-double.  Newton-Schulz in fp64
+    // stops at its own rounding (|I - M X| ~ 1e-15 with entries a few ulps off the exact inverse); the step leaves every entry within
+    // about an ulp of the exact inverse -- the inverse any other accurate solver (LAPACK, the reference's SuperLU) approximates too
+    hipLaunchKernelGGL(zs_pack_sym_kernel, gb, tb, 0, st, (const double *)Xtm.p, Xpk.p, n16);
+    hipLaunchKernelGGL(zs_resid_dd_kernel, gb, tb, 0, st, (const double *)Mtm.p, (const double *)Xtm.p, n16, Ttm.p);
+    HIPCHK(c, hipGetLastError());
+    if ((rc = gemm_pk(c, Xpk.p, Ttm.p, Utm.p, nullptr, KBn, KBn, nt, 1))) return rc;             // U = X R
+    hipLaunchKernelGGL(zs_add_kernel, gb, tb, 0, st, Xtm.p, (const double *)Utm.p, tot);
+    HIPCHK(c, hipGetLastError());
     if (c->ad_Minvpk) { (void)hipFree(c->ad_Minvpk); c->ad_Minvpk = nullptr; }
     if ((rc = dev_alloc(c, &c->ad_Minvpk, (size_t)tot, false))) return rc;
     hipLaunchKernelGGL(zs_pack_sym_kernel, gb, tb, 0, st, (const double *)Xtm.p, c->ad_Minvpk, n16);

@@ -244,3 +244,98 @@ def test_g11_keyed_rng_branch_against_independent_philox_table(orc):
         assert g.choice(1) == 0
         nv = orc.keyed_normal(sd, rr, int(z['elem'][j]))
         assert abs(nv - z['normal'][j]) <= 4e-16 * (1.0 + abs(z['normal'][j])), (j, nv, z['normal'][j])   # libm's log / sin / cos: last-bit slack
+
+
+SEP_CD = ['bls10', 'bls32', 'bls64', 'maxcut12']
+
+
+@pytest.mark.parametrize('name', SEP_CD)
+def test_fast_separable_oracle_against_the_reference_mt(orc, name):
+    """orc_improve_cd_sep (the fast separable oracle the factored-kernel GPU tests use) replays the reference's MT stream
+    call for call: points within 1e-9 of the reference, the same stream position after the run, and bit-identical to the
+    restatement."""
+    z = load_golden('g6_cd_' + name)
+    prob = orc.Problem(funcs_from_npz(z))
+    iters = int(z['num_iters'])
+    for r in range(z['Y0'].shape[1]):
+        np.random.seed(int(z['seed0']) + r)
+        rng = orc.Rng(orc.RNG_MT, 0, from_numpy_global=True)
+        x, s1, s2 = prob.improve_cd_sep(z['Y0'][:, r], num_iters=iters, rng=rng)
+        ref = z['full_x'][:, r]
+        assert np.max(np.abs(x - ref)) <= 1e-9 * (1 + np.max(np.abs(ref))), (name, r)
+        rng.push_numpy()
+        assert np.random.get_state()[2] == int(z['full_pos'][r])
+        np.random.seed(int(z['seed0']) + r)
+        rng = orc.Rng(orc.RNG_MT, 0, from_numpy_global=True)
+        xr, r1, r2 = prob.improve_cd(z['Y0'][:, r], num_iters=iters, rng=rng)
+        assert np.array_equal(x, xr), (name, r)
+        assert list(s1) == list(r1) and list(s2) == list(r2), (name, r)
+
+
+def _sep_families(n, seed):
+    from qcqp_amd import problems
+    rows = max(4, n // 3)   # rank-deficient P0, like the low-rank objectives of the factored kernel
+    return [
+        ('bls', problems.boolean_least_squares(n, rows, seed=seed)[0]),
+        ('box', problems.box_least_squares(n, n, seed=seed)[0]),
+        ('box_noridge', problems.box_least_squares(n, rows, seed=seed, ridge=0.0)[0]),
+        ('disc', problems.box_least_squares(n, n, bound=0.7, seed=seed, ridge=0.0)[0]),
+        ('maxcut_w', problems.maxcut(n, seed=seed, weighted=True)[0]),
+    ] + [(name, problems.multi_class(name, n, seed=seed)) for name in ('box3', 'ann2', 'lin2', 'cut2')]
+
+
+def test_fast_separable_oracle_follows_the_restatement_keyed(orc):
+    """orc_improve_cd_sep against orc_improve_cd on the keyed stream the GPU uses, 257 trajectories over every separable family the
+    kernels take: the same counters (sweeps, visits, accepted moves of both phases), points within 1e-12 relative, and
+    bit-identical wherever phase 2 did not run (phase 1 and the gate are restated bit for bit).  Starts: keyed normals (phase 1 on),
+    and resident starts near the constraint set with and without noise, some of which fail the gate (phase 1 off)."""
+    checked = gate_failed = p2_ran = 0
+    for n in (48, 50, 100, 128, 200):
+        fams = _sep_families(n, seed=n)
+        cases = [(True, 1000, 'normal')]
+        if n <= 128:
+            cases += [(False, 1000, 'near'), (False, 1000, 'noisy')]
+        if n <= 100:
+            cases += [(True, 0, 'normal'), (True, 1, 'normal'), (True, 2, 'normal'), (False, 2, 'near')]
+        if n < 100:
+            cases += [(True, 1000, 'normal'), (False, 1, 'near')]
+        for fi, (fam, funcs) in enumerate(fams):
+            if n == 200 and fam in ('box', 'disc', 'box3', 'lin2'):
+                continue   # slow to converge: seconds per restatement trajectory at this n
+            prob = orc.Problem(funcs)
+            for ci, (phase1, iters, start) in enumerate(cases):
+                r = 100 * fi + ci
+                rs = np.random.RandomState(1000 * n + r)
+                if start == 'normal':
+                    x0 = orc.keyed_normal_matrix(7, n, 1, first_index=r)[:, 0]
+                else:
+                    # a point near the constraint set: the sign pattern of a random normal at the scale of the bounds
+                    x0 = np.sign(rs.randn(n)) * (0.7 if fam == 'disc' else 1.0)
+                    if fam == 'lin2':
+                        x0 = np.where(np.arange(n) % 2 == 0, 0.25, -0.5) + 0.5 * rs.uniform(-1, 1, n)
+                    x0 = x0 + (1e-3 if start == 'near' else 3e-2) * rs.randn(n)
+                out = []
+                for fn in (prob.improve_cd, prob.improve_cd_sep):
+                    rng = orc.Rng(orc.RNG_KEYED, 7)
+                    rng.set_restart(r)
+                    out.append(fn(x0, num_iters=iters, phase1=phase1, rng=rng))
+                (xa, a1, a2), (xb, b1, b2) = out
+                where = (n, fam, phase1, iters, start)
+                assert list(a1) == list(b1) and list(a2) == list(b2), (where, a1, b1, a2, b2)
+                assert np.max(np.abs(xa - xb)) <= 1e-12 * max(1.0, np.max(np.abs(xa))), where
+                if a2[0] == 0:
+                    assert np.array_equal(xa, xb), where
+                    gate_failed += iters > 0
+                else:
+                    p2_ran += 1
+                checked += 1
+    assert checked >= 200 and gate_failed >= 10 and p2_ran >= 100, (checked, gate_failed, p2_ran)
+
+
+@pytest.mark.parametrize('name', ['dense16', 'circle5'])
+def test_fast_separable_oracle_refuses_coupled_problems(orc, name):
+    z = load_golden('g6_cd_' + name)
+    prob = orc.Problem(funcs_from_npz(z))
+    rng = orc.Rng(orc.RNG_KEYED, 1)
+    with pytest.raises(RuntimeError, match='rc=-5'):
+        prob.improve_cd_sep(z['Y0'][:, 0], num_iters=5, rng=rng)
