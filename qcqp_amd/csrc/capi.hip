@@ -1581,7 +1581,7 @@ int qcqpmi_cd_stream_run(qcqpmi_ctx *c, int64_t K, int64_t R, int generate, int 
     if (!use2) {
         if (!eligible || c->life_version != 1)
             return fail(c, QCQPMI_EUNSUPPORTED, "cd_stream_run: the lifecycle kernel needs separable constraints -- at most four classes of coordinates, at most two constraints "
-                        "per coordinate --, a diagonal of P0 that is positive everywhere or zero everywhere, and 48 <= n <= 2304: use qcqpmi_cd_run per population");
+                        "per coordinate --, a diagonal of P0 that is positive everywhere or zero everywhere, and 33 <= n <= 2304: use qcqpmi_cd_run per population");
         const int NBq = (int)(c->n16 / 16);
         cs = (c->dbg & 128) ? ((c->dbg >> 8) & 7) : 4;
         cs = cs > RQ_CSMAX ? RQ_CSMAX : cs;

@@ -65,10 +65,13 @@ def multi_class(name, n, seed=1):
       box3   least squares + ridge; coordinate i carries x^2 <= 1 | x^2 <= 0.49 | x^2 - x/2 - 1/2 <= 0 (= [-1/2, 1]) by i mod 3
       ann2   least squares + ridge; even i: x^2 <= 1 AND -x^2 <= -1/4 (two intervals [-1, -1/2] u [1/2, 1]); odd i: x^2 == 1
       lin2   least squares + ridge; TWO LINEAR constraints per coordinate, x <= u_c and -x <= -l_c, bounds by i mod 2
-      cut2   weighted MAXCUT objective (zero diagonal); even i: x^2 == 1, odd i: x^2 <= 1 (a relaxed vertex)"""
+      cut2   weighted MAXCUT objective (zero diagonal); even i: x^2 == 1, odd i: x^2 <= 1 (a relaxed vertex)
+      box4   least squares + ridge; FOUR classes by i mod 4 (the class table full): x^2 <= 1 | x^2 <= 0.49 | x^2 - x/2 - 1/2 <= 0 |
+             the annulus pair x^2 <= 1 AND -x^2 <= -1/4
+      cut4   weighted MAXCUT objective (zero diagonal); four classes by i mod 4: x^2 == 1 | x^2 <= 1 | x^2 <= 0.49 | the annulus pair"""
     rs = np.random.RandomState(seed)
     funcs = []
-    if name == 'cut2':
+    if name in ('cut2', 'cut4'):
         U = np.triu((rs.uniform(size=(n, n)) < 0.5).astype(float), 1) * np.triu(rs.uniform(0.5, 1.5, size=(n, n)), 1)
         W = U + U.T
         funcs.append((0.25 * W, np.zeros(n), -0.25 * float(W.sum()), None))
@@ -104,6 +107,15 @@ def multi_class(name, n, seed=1):
             quad(i, 0.0, -1.0, lo, '<=')
         elif name == 'cut2':
             quad(i, 1.0, 0.0, -1.0, '==' if i % 2 == 0 else '<=')
+        elif name in ('box4', 'cut4'):
+            c = i % 4
+            if c == 3:
+                quad(i, 1.0, 0.0, -1.0, '<=')
+                quad(i, -1.0, 0.0, 0.25, '<=')
+            elif name == 'box4':
+                quad(i, 1.0, -0.5 if c == 2 else 0.0, (-1.0, -0.49, -0.5)[c], '<=')
+            else:
+                quad(i, 1.0, 0.0, (-1.0, -1.0, -0.49)[c], '==' if c == 0 else '<=')
         else:
             raise KeyError(name)
     return funcs

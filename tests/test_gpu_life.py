@@ -564,7 +564,7 @@ def test_life_kernel_fuzz_several_classes(eng_mod, orc, seed):
     rs = np.random.RandomState(2000 + seed)
     for case in range(8):
         fam = str(rs.choice(['box3', 'ann2', 'lin2', 'cut2']))
-        big = __import__('os').environ.get('QCQP_FUZZ_BIG') == '1'        # a shake-out of the larger instantiations (no oracle there: ~30 s per sweep)
+        big = __import__('os').environ.get('QCQP_FUZZ_BIG') == '1'        # a shake-out of the larger instantiations (the fast separable oracle there)
         n = int(rs.choice([500, 777, 1024, 1040, 1100, 1500, 2000] if big else [48, 50, 64, 77, 100, 128, 130, 200, 256, 300]))
         R = int(rs.choice([1, 15, 16, 17, 100, 300]))
         K = int(rs.choice([1, 2, 3]))
@@ -599,11 +599,11 @@ def test_life_kernel_fuzz_several_classes(eng_mod, orc, seed):
                 assert np.array_equal(o[key][sl], outr[key]), (tag, p, key)
             assert rel(o['f0'][sl], outr['f0']) < 1e-9 and np.max(np.abs(o['maxviol'][sl] - outr['maxviol'])) < 1e-12, (tag, p)
             assert o['best_index'][p] == e.select_best(1e-4)[0], (tag, p)
-            if p == 0 and not big:
+            if p == 0:
                 for r in sorted({0, R - 1}):
                     rng = orc.Rng(orc.RNG_KEYED, sd)
                     rng.set_restart(fi + r)
-                    x, s1, s2 = prob.improve_cd(Xs[:, r], num_iters=iters, phase1=phase1, rng=rng)
+                    x, s1, s2 = (prob.improve_cd_sep if big else prob.improve_cd)(Xs[:, r], num_iters=iters, phase1=phase1, rng=rng)
                     assert rel(X[:, r], x) < 1e-9, (tag, r)
                     assert o['visits2'][r] == s2[1] and o['accepted2'][r] == s2[2], (tag, r)
         es.close()

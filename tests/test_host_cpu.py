@@ -877,7 +877,7 @@ def test_multi_class_families_are_what_the_kinds_take_and_the_oracle_solves_them
     from qcqp_amd import problems
     from qcqp_amd.form import QCQPForm
     n = 24
-    for fam in ('box3', 'ann2', 'lin2', 'cut2'):
+    for fam in ('box3', 'ann2', 'lin2', 'cut2', 'box4', 'cut4'):
         funcs = problems.multi_class(fam, n)
         form = QCQPForm.from_arrays(funcs)
         lists = {}

@@ -281,7 +281,7 @@ def _sep_families(n, seed):
         ('box_noridge', problems.box_least_squares(n, rows, seed=seed, ridge=0.0)[0]),
         ('disc', problems.box_least_squares(n, n, bound=0.7, seed=seed, ridge=0.0)[0]),
         ('maxcut_w', problems.maxcut(n, seed=seed, weighted=True)[0]),
-    ] + [(name, problems.multi_class(name, n, seed=seed)) for name in ('box3', 'ann2', 'lin2', 'cut2')]
+    ] + [(name, problems.multi_class(name, n, seed=seed)) for name in ('box3', 'ann2', 'lin2', 'cut2', 'box4', 'cut4')]
 
 
 def test_fast_separable_oracle_follows_the_restatement_keyed(orc):
@@ -300,7 +300,7 @@ def test_fast_separable_oracle_follows_the_restatement_keyed(orc):
         if n < 100:
             cases += [(True, 1000, 'normal'), (False, 1, 'near')]
         for fi, (fam, funcs) in enumerate(fams):
-            if n == 200 and fam in ('box', 'disc', 'box3', 'lin2'):
+            if n == 200 and fam in ('box', 'disc', 'box3', 'lin2', 'box4'):
                 continue   # slow to converge: seconds per restatement trajectory at this n
             prob = orc.Problem(funcs)
             for ci, (phase1, iters, start) in enumerate(cases):
