@@ -319,13 +319,24 @@ int qcqpmi_debug_life_profile(qcqpmi_ctx *ctx, int64_t *out24);
  * coordinate -- boxes with different bounds, an annulus beside an equality, two linear bounds, MAXCUT with relaxed vertices
  * (qcqp.py:113-141, 160-176 treat every coordinate's list on its own); ONE lifecycle kernel for every shape; with
  * qcqpmi_cd_set_objective_factor the kernel carries L^T X instead of multiplying with P0 and takes n up to 4096.
- * QCQPMI_EUNSUPPORTED otherwise (more than four classes, three or four constraints per coordinate, mixed diagonal signs, coupled
- * constraints, n > 2304 without an objective factor): use
+ * Round 7: ALSO a diagonal of P0 of MIXED sign -- negative entries, or zero in some places and not in others: a box-constrained QP
+ * with an indefinite P0 -- for ONE class with one constraint per coordinate and a bounded feasible set of one or two intervals,
+ * 33 <= n <= 2304, no objective factor (qcqpmi_last_cd_kernel: "cd_life_kernel<3,sgn>" / "cd_life_kernel<7,sgn>"): every coordinate
+ * steps by the sign of its own P0[i,i] (utilities.py:262-288: the vertex if P0[i,i] > 0 and it is feasible, else the best end point).
+ * QCQPMI_EUNSUPPORTED otherwise (more than four classes, three or four constraints per coordinate, mixed diagonal signs together
+ * with several classes or two constraints per coordinate, coupled constraints, n > 2304 without an objective factor): use
  * qcqpmi_cd_run per population; a refused call leaves the resident population untouched.  K R < 2^30 (restart tickets are 32-bit; QCQPMI_EINVAL beyond).
  * Near-ties: a restart whose decision is within rounding of a tie is replayed in the reference's arithmetic like in
  * qcqpmi_cd_run; for a positive diagonal the replay sees the objective RELATIVE to the start of phase 2 (the constant of its
  * scalar objective differs from the reference's by f0 at that start: candidates closer than one ulp of f0 may resolve
- * differently; exact ties do not), for a zero diagonal the absolute objective (evaluated by an extra frozen sweep). */
+ * differently; exact ties do not), for a zero diagonal the absolute objective (evaluated by an extra frozen sweep).  A diagonal of
+ * mixed sign tracks the ABSOLUTE objective like the zero diagonal (the same extra frozen sweep per restart): wherever P0[i,i] <= 0
+ * the reference compares rounded absolute values f0(end point), and a replay that saw a relative objective could resolve candidates
+ * within one ulp of f0 differently there; its coordinates with P0[i,i] > 0 see the absolute value too, i.e. the reference's own
+ * constant.  A decision counts as a near-tie when the vertex of a coordinate with P0[i,i] > 0 is within 1e-7 of the gap from the
+ * gap's midpoint (as for a positive diagonal), or when the two outermost end points' values differ by less than 1e-12 of the
+ * objective's scale (sum |P0| + sum |q0| + |r0|, times the largest squared end point if above 1) times the ratio of their distance
+ * to the narrower interval's width, for P0[i,i] <= 0 (as for a zero diagonal, the secant slope in place of the slope). */
 int qcqpmi_cd_stream_run(qcqpmi_ctx *ctx, int64_t K, int64_t R, int generate, int phase1, int64_t num_iters, double viol_tol,
                          double tol, uint64_t seed, uint64_t seed_stride, uint64_t first_index, uint64_t first_stride,
                          double select_tol, int64_t *sweeps1, int64_t *sweeps2, int64_t *visits2, int64_t *accepted2,
@@ -348,7 +359,8 @@ int qcqpmi_cd_life_version(qcqpmi_ctx *ctx, int version);
  * blocks, the evaluation kernels, every other path); the caller vouches for L L^T = P0 (qcqp_amd.lowrank.objective_factor checks
  * it to 1e-12 of the largest entry).  Takes r <= 288 and 128 <= n <= 4096 (ABI 6), single-class separable constraints on a positive
  * diagonal (QCQPMI_EUNSUPPORTED otherwise; qcqpmi_cd_stream_run then runs as without a factor).  L == NULL or r == 0 removes it;
- * qcqpmi_cd_life_version(ctx, 3) = cd_life_kernel WITHOUT the factor (comparisons). */
+ * qcqpmi_cd_life_version(ctx, 3) = cd_life_kernel WITHOUT the factor (comparisons).  (A diagonal of mixed sign is not PSD: the SGN
+ * kind of qcqpmi_cd_stream_run never runs with a factor.) */
 int qcqpmi_cd_set_objective_factor(qcqpmi_ctx *ctx, const double *L, int64_t r);
 /* Coordinate descent for constraints that couple coordinates IN THE REFERENCE'S SUMMATION ORDER (test / diagnostic mode, any
  * n): every one-variable coefficient (t2, t1, t0) of get_onevar_func (utilities.py:99-105) is formed by row-sequential sums

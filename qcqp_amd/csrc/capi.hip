@@ -109,7 +109,7 @@ struct qcqpmi_ctx {
     bool sep = false;
     int maxc = 0;
     int K = 0;
-    int objclass = 0;  // 1: every P0[i,i] > 0, 2: every P0[i,i] == 0, 0: mixed
+    int objclass = 0;  // 1: every P0[i,i] > 0, 2: every P0[i,i] == 0, 0: mixed (negative entries, or zero in places: cd_life_kernel's SGN kind)
     bool symcls = false;  // one constraint class of the form p x_i^2 + r == 0 (feasible sets mirrored about 0)
     DevProblem dp{};
     std::vector<void *> prob_allocs;
@@ -1545,6 +1545,9 @@ static int cd_life2_reserve(qcqpmi_ctx *c, int nmw, int cus) {
 }
 
 // ---- lifecycle run: K populations of R restarts through ONE persistent slot-queue launch (cd_queue.h, CdLife)
+// Takes (cd_life2_config): separable constraints, up to four classes with up to two constraints per coordinate on a diagonal of P0 that is
+// positive everywhere or zero everywhere; ONE class with one constraint per coordinate on a diagonal of mixed sign (round 7, the SGN
+// kind: no objective factor); 33 <= n <= 2304 (<= 4096 with a factor).  Anything else: QCQPMI_EUNSUPPORTED, nothing touched.
 int qcqpmi_cd_stream_run(qcqpmi_ctx *c, int64_t K, int64_t R, int generate, int phase1, int64_t num_iters, double viol_tol, double tol,
                          uint64_t seed, uint64_t seed_stride, uint64_t first_index, uint64_t first_stride, double select_tol,
                          int64_t *sweeps1, int64_t *sweeps2, int64_t *visits2, int64_t *accepted2, uint8_t *ran_phase2, double *f0,
@@ -1581,7 +1584,9 @@ int qcqpmi_cd_stream_run(qcqpmi_ctx *c, int64_t K, int64_t R, int generate, int 
     if (!use2) {
         if (!eligible || c->life_version != 1)
             return fail(c, QCQPMI_EUNSUPPORTED, "cd_stream_run: the lifecycle kernel needs separable constraints -- at most four classes of coordinates, at most two constraints "
-                        "per coordinate --, a diagonal of P0 that is positive everywhere or zero everywhere, and 33 <= n <= 2304: use qcqpmi_cd_run per population");
+                        "per coordinate --, a diagonal of P0 that is positive everywhere or zero everywhere (a diagonal of mixed sign: ONE class with one constraint "
+                        "per coordinate only; with several classes or two constraints per coordinate it runs the serial path), and 33 <= n <= 2304: use qcqpmi_cd_run "
+                        "per population");
         const int NBq = (int)(c->n16 / 16);
         cs = (c->dbg & 128) ? ((c->dbg >> 8) & 7) : 4;
         cs = cs > RQ_CSMAX ? RQ_CSMAX : cs;

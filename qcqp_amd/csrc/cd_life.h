@@ -19,7 +19,8 @@
 //   * n need not be a multiple of 16 (zero rows / columns up to n16; the padded coordinates are never visited);
 //   * three step kinds: the mirrored band of p x^2 + r == 0 on a positive diagonal (Boolean least squares), any single
 //     class with at most two intervals on a positive diagonal (box / disc / one-sided), and a ZERO diagonal (MAXCUT: the
-//     scalar objective is linear, the minimiser an end point of the feasible set).
+//     scalar objective is linear, the minimiser an end point of the feasible set); and a fourth for a diagonal of mixed sign
+//     (L2_KIND_SGN below: every coordinate steps by the sign of its own P0[i,i]).
 // Per restart the arithmetic is that of the serial path (cd_phase1_sep.h, the blocked Gauss-Seidel step of cd_phase2_q.h,
 // near-ties replayed in the reference's arithmetic through onevar_minimise); results do not depend on the slot, the
 // workgroup, the episode boundaries or the number of populations in the launch.
@@ -34,7 +35,10 @@ namespace qcqpmi {
 // step kinds.  GENK / LINK (round 6): GEN / LIN for problems with SEVERAL constraint classes (coordinates with different
 // constraint lists: up to four classes) and up to two constraints per coordinate -- the slots keep a feasible set per class, the
 // chain looks its columns' classes up per block
-enum { L2_KIND_BAND = 0, L2_KIND_GEN = 1, L2_KIND_LIN = 2, L2_KIND_GENK = 3, L2_KIND_LINK = 4 };
+// SGN: a diagonal of P0 of MIXED sign (a box-constrained QP with an indefinite P0), one class with one constraint per coordinate:
+// the step is the GEN pick where P0[i,i] > 0, the outermost end point on the far side of the vertex where P0[i,i] < 0 (a concave scalar
+// objective), the LIN pick where P0[i,i] == 0; the objective is tracked as an absolute value like LIN's (a frozen sweep first)
+enum { L2_KIND_BAND = 0, L2_KIND_GEN = 1, L2_KIND_LIN = 2, L2_KIND_GENK = 3, L2_KIND_LINK = 4, L2_KIND_SGN = 5 };
 
 struct CdLife2Args {
     DevProblem P;
@@ -48,7 +52,7 @@ struct CdLife2Args {
     int *abort;                  // [0] set by a wave whose wait ran into the watchdog (a bug, never the data): the launch unwinds
     int *cuslot;                 // [4096] zeroed before the launch, or NULL: arrival counter per compute unit (key: XCC, SE, CU of HW_ID) -- the
                                  // second four-wave workgroup of a CU turns its roles by two SIMDs, so that the two chains of a CU do not share a SIMD
-    double fbound;               // sum |P0| + sum |q0| + |r0|: scale of the objective for the near-tie test of the linear kind
+    double fbound;               // sum |P0| + sum |q0| + |r0|: scale of the objective for the near-tie test of the linear and mixed-sign kinds
     // factored objective (P0 = L L^T, L n x r; cd_life2_pack_factor): fragments of L for the products / the updates of Y = L^T X;
     // RB = blocks of 16 rows of Y (0: not factored)
     const double *Gpack, *Upack;
@@ -60,6 +64,8 @@ struct CdLife2Args {
 };
 
 // does the kernel take this problem?  nmw / cs / kind: the instantiation (multiplying waves 3 | 7, chain share, step kind)
+// objclass: 1 = P0[i,i] > 0 everywhere, 2 = zero everywhere, 0 = anything else (mixed signs: the SGN kind, one class with one
+// constraint per coordinate only, never with a factor)
 // factor_rb: blocks of 16 rows of an objective factor the caller WILL hand over (0: none) -- the factored instantiation keeps Y, not X,
 // in registers, so with a factor the kernel also takes 2304 < n <= 4096 (and prefers three multiplying waves from n = 1040 on)
 bool cd_life2_config(const DevProblem &P, int Kreal, int objclass, bool symcls, int factor_rb, int *nmw, int *cs, int *kind);

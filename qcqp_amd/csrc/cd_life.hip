@@ -8,7 +8,7 @@
 // the X tile in a private global tile with a ring of the four blocks committed last in LDS, every multiplying wave
 // computes EVERY product over its own blocks of the contraction, the chain wave stages its own small operands; plus the
 // generalisations: n not a multiple of 16, 1024 < n <= 2048 with six multiplying waves, step kinds for single classes
-// with up to two intervals and for a zero diagonal.
+// with up to two intervals and for a zero diagonal; round 7: a step kind for a diagonal of mixed sign (L2_KIND_SGN, cd_life.h).
 #include "cd_life.h"
 
 #include <cstdio>
@@ -536,7 +536,7 @@ __device__ __attribute__((noinline)) void l2_chain_role(int t_in) {
     constexpr int LRV = LR;                        // factored objective (l2_mfma_lr_role): the ring carries the block's MOVES, no share
     static_assert(!LR || CS == 0, "factored objective: the chain has no share of the contraction");
     static_assert(!MULTI || (TILES == 1 && !LR), "multi-class kinds: one tile per workgroup, no objective factor");
-    constexpr bool PRE = BK == L2_KIND_LIN;        // a restart's phase 2 starts with a frozen sweep that evaluates f0
+    constexpr bool PRE = BK == L2_KIND_LIN || BK == L2_KIND_SGN;        // a restart's phase 2 starts with a frozen sweep that evaluates f0
     const int tile = TILES > 1 ? l2_uni(t_in) : 0; // the tile whose 16 slots this chain steps
     L2_LDS_VIEW(tile)
     (void)ytile; (void)pend; (void)clsb;
@@ -564,6 +564,13 @@ __device__ __attribute__((noinline)) void l2_chain_role(int t_in) {
     // BAND: [-symb, -syma] u [syma, symb], near-tie = vertex within thr of 0
     // GEN : [Ul0, Uh0] (u [Ul1, Uh1]); the vertex is projected onto the interval on its side of the gap's midpoint
     // LIN : the lowest / highest end point against the slope; near-tie = |slope| below tl
+    // SGN : by the sign of P0[i,i] -- positive: GEN; zero: LIN; negative: the scalar objective is concave, its minimum over the set is at
+    //       an OUTERMOST end point, linL or linH: f(linH) - f(linL) = 2 (linH - linL) s with the secant slope s = P0[i,i] (omid - x_i) + g,
+    //       omid their midpoint (s > 0 <=> the vertex lies above omid); near-tie = |s| below tl.  With P0[i,i] == 0 s IS the slope g: one
+    //       expression for both.  tl is LIN's: |s| > tl puts the two outermost candidates 1e-12 of the objective's scale x (linH - linL) /
+    //       wmin apart, and by concavity an inner end point of the picked interval's side exceeds the pick by at least its interval's
+    //       width / (linH - linL) of that -- 1e-12 of the scale again, where the reference's rounded values (utilities.py:275-288) differ
+    //       by 1e-16 of it.
     const double thr = two ? 1e-7 * (Ul1 - Uh0) : 0.0;
     const double syma = two ? Ul1 : 0.0, symb = two ? Uh1 : Uh0;
     const double gmid = two ? 0.5 * (Uh0 + Ul1) : QM_INF;
@@ -579,7 +586,8 @@ __device__ __attribute__((noinline)) void l2_chain_role(int t_in) {
         return (wmin > 0.0) ? 0.5e-12 * scale / wmin : QM_INF;
     };
     double tl = 0.0;
-    if (BK == L2_KIND_LIN && !MULTI) tl = lin_tl(Ul0, Uh0, Ul1, Uh1, two);
+    if ((BK == L2_KIND_LIN || BK == L2_KIND_SGN) && !MULTI) tl = lin_tl(Ul0, Uh0, Ul1, Uh1, two);
+    const double omid = (BK == L2_KIND_SGN) ? 0.5 * (linL + linH) : 0.0;
     struct { int upd_counter, visits, accepted, sweeps, status; bool conv; } S;      // (32-bit in the loop: < 2^31 visits per restart)
     S.upd_counter = (int)cst[0 * 64 + lane]; S.visits = (int)cst[1 * 64 + lane]; S.accepted = (int)cst[2 * 64 + lane];
     S.sweeps = (int)cst[3 * 64 + lane]; S.conv = cst[4 * 64 + lane] != 0; S.status = (int)cst[5 * 64 + lane];
@@ -589,8 +597,8 @@ __device__ __attribute__((noinline)) void l2_chain_role(int t_in) {
     // are all n coordinates at the FINAL point: f0(x) - r0 freshly evaluated from the products the sweep computed
     // anyway.  A restart that stops otherwise (sweep limit, gate not passed) takes one FROZEN sweep (no moves, not
     // counted) that sums the same terms.  fpart tracks the objective through the moves: relative to the start of
-    // phase 2, or -- linear kind, where the reference's end-point comparison works on rounded absolute values --
-    // from f0 evaluated by a frozen sweep before the first real one (`pre`).
+    // phase 2, or -- linear and mixed-sign kinds, where the reference's end-point comparison (every coordinate with
+    // P0[i,i] <= 0) works on rounded absolute values -- from f0 evaluated by a frozen sweep before the first real one (`pre`).
     bool frz = (cst[7 * 64 + lane] & 1) != 0, done = (cst[7 * 64 + lane] & 2) != 0, pre = PRE && (cst[7 * 64 + lane] & 4) != 0;
     // factored objective: a restart's first sweep in its slot LOADS it -- Y = L^T x0 is what the products' own updates make of
     // "every block moves from 0 to x0": no decisions, no counters, the block's moves are the points themselves; the sweeps start
@@ -756,6 +764,13 @@ __device__ __attribute__((noinline)) void l2_chain_role(int t_in) {
             tolev[v] = (act && nv[v] > 0) ? tolv : QM_INF;     // a restart that is not sweeping never moves (the padded coordinates of
                                                                // the last block hold a fixed point of the step: see the column build)
         }
+        // mixed-sign kind: per own column the sign of the diagonal and omid - x (x of a column changes only at its own step)
+        bool posv[4] = {false, false, false, false};
+        double omx[4] = {0.0, 0.0, 0.0, 0.0};
+        if (BK == L2_KIND_SGN) {
+    #pragma unroll
+            for (int v = 0; v < 4; v++) { posv[v] = t2o[v] > 0.0; omx[v] = omid - xo[v]; }
+        }
         L2_TICK(pt_sum)
         // ---- the 16 steps: only what the next step waits for
     #pragma unroll
@@ -770,6 +785,14 @@ __device__ __attribute__((noinline)) void l2_chain_role(int t_in) {
                 const double xv = __builtin_fma(-gb[v], rto[v], xo[v]);
                 const double p0 = fmin(fmax(xv, l0v[v]), h0v[v]), p1 = fmin(fmax(xv, l1v[v]), h1v[v]);
                 pick = (xv > midv[v]) ? p1 : p0;
+            } else if (BK == L2_KIND_SGN) {
+                // both candidates from the same gb: the clamped vertex (off the critical path: one select more than GEN) and the
+                // end point against the secant slope (rto = 0 where the diagonal is 0: the vertex is x itself, never used)
+                const double xv = __builtin_fma(-gb[v], rto[v], xo[v]);
+                const double p0 = fmin(fmax(xv, l0v[v]), h0v[v]), p1 = fmin(fmax(xv, l1v[v]), h1v[v]);
+                const double sc_ = __builtin_fma(t2o[v], omx[v], gb[v]);
+                const double pe = (sc_ > 0.0) ? linL : linH;
+                pick = posv[v] ? ((xv > midv[v]) ? p1 : p0) : pe;
             } else {
                 pick = (gb[v] > 0.0) ? l0v[v] : h1v[v];                           // linear: the end point against the slope
             }
@@ -802,6 +825,13 @@ __device__ __attribute__((noinline)) void l2_chain_role(int t_in) {
                 const double p0 = fmin(fmax(xv, l0v[v]), h0v[v]), p1 = fmin(fmax(xv, l1v[v]), h1v[v]);
                 pick = (xv > midv[v]) ? p1 : p0;
                 far = fabs(xv - midv[v]) > thrv[v];
+            } else if (BK == L2_KIND_SGN) {
+                const double xv = __builtin_fma(-gb[v], rto[v], xo[v]);
+                const double p0 = fmin(fmax(xv, l0v[v]), h0v[v]), p1 = fmin(fmax(xv, l1v[v]), h1v[v]);
+                const double sc_ = __builtin_fma(t2o[v], omx[v], gb[v]);
+                const double pe = (sc_ > 0.0) ? linL : linH;
+                pick = posv[v] ? ((xv > midv[v]) ? p1 : p0) : pe;
+                far = posv[v] ? fabs(xv - midv[v]) > thrv[v] : fabs(sc_) > tlv[v];      // false for NaN as well
             } else {
                 pick = (gb[v] > 0.0) ? l0v[v] : h1v[v];
                 far = fabs(gb[v]) > tlv[v];
@@ -1064,7 +1094,7 @@ __device__ __attribute__((noinline)) void l2_chain_role(int t_in) {
 // NMW: multiplying waves per tile (3: a chain wave + three multiplying waves per tile; 7: eight waves, one per CU, 1024 < n <= 2304
 //      -- the eighth wave multiplies too, beside the chain on SIMD 0)
 // CS : blocks of the contraction the chain wave multiplies itself
-// KIND: L2_KIND_BAND / GEN / LIN (cd_life.h)
+// KIND: L2_KIND_BAND / GEN / LIN / GENK / LINK / SGN (cd_life.h)
 // TILES: tiles of 16 slots per workgroup.  1: four-wave workgroups, two per CU (NMW = 3), or one eight-wave workgroup (NMW = 7).
 //      2 (round 6, NMW = 3 only): ONE eight-wave workgroup per CU runs two tiles -- both chains on SIMD 0, a product stream per
 //      tile on each of SIMDs 1-3, exactly what two TILES = 1 workgroups on a CU do while both are in their roles -- but the
@@ -1085,8 +1115,8 @@ __global__ __launch_bounds__((NMW == 3 && TILES == 1) ? 256 : 512, 2) void cd_li
     constexpr int NW = NT / 64;
     constexpr int NS = 16 * TILES;                 // slots of the workgroup
     constexpr int TD = l2_tile_doubles(NMW, CSU, LR);  // doubles of one tile's LDS block
-    static_assert(!LR || (NMW == 3 && CS == 0 && BK != L2_KIND_LIN), "factored objective: three multiplying waves per tile, no chain share, a positive diagonal");
-    constexpr bool PRE = BK == L2_KIND_LIN;        // a restart's phase 2 starts with a frozen sweep that evaluates f0 (see the chain role)
+    static_assert(!LR || (NMW == 3 && CS == 0 && BK != L2_KIND_LIN && BK != L2_KIND_SGN), "factored objective: three multiplying waves per tile, no chain share, a positive diagonal");
+    constexpr bool PRE = BK == L2_KIND_LIN || BK == L2_KIND_SGN;        // a restart's phase 2 starts with a frozen sweep that evaluates f0 (see the chain role)
     static_assert(TILES == 1 || NMW == 3, "two tiles per workgroup: eight waves = two chains + two x three multiplying waves");
     const DevProblem &P = a.P;
     const int tid0 = threadIdx.x;
@@ -1668,6 +1698,8 @@ __global__ __launch_bounds__(L2P_NT) void cd_life_prep_kernel(DevProblem P, cons
 }
 
 // strictly upper triangle of the diagonal blocks (zeros elsewhere) and the per-block scalars the chain stages
+// (rcp2d is 1 / (2 P0[i,i]) wherever P0[i,i] != 0, negative entries included, and 0 where it is 0: the mixed-sign kind reads
+//  1 / P0[i,i] only where it is positive and P0[i,i] itself elsewhere)
 __global__ void l2_pack_kernel(DevProblem P, double *Dpack, double *Spack) {
     const int b = blockIdx.x, t = threadIdx.x;            // 256 threads: entry (row t >> 4, column t & 15) of block b
     const int64_t n16 = P.n16;
@@ -1698,7 +1730,8 @@ template <int NMW, int CS, int TILES, int LR>
 int l2_launch_kind(const CdLife2Args &a, int kind, int wgs, size_t lds, hipStream_t st) {
     constexpr bool MK = TILES == 1 && !LR;        // the multi-class kinds exist for one tile per workgroup, without an objective factor
     if (!MK && (kind == L2_KIND_GENK || kind == L2_KIND_LINK)) return (int)hipErrorInvalidValue;
-    auto k = kind == L2_KIND_BAND ? cd_life_kernel<NMW, CS, L2_KIND_BAND, TILES, LR> : (kind == L2_KIND_GEN || LR) ? cd_life_kernel<NMW, CS, L2_KIND_GEN, TILES, LR>
+    if (LR && kind == L2_KIND_SGN) return (int)hipErrorInvalidValue;      // a factor needs a PSD P0
+    auto k = kind == L2_KIND_SGN ? cd_life_kernel<NMW, CS, LR ? L2_KIND_GEN : L2_KIND_SGN, TILES, LR> : kind == L2_KIND_BAND ? cd_life_kernel<NMW, CS, L2_KIND_BAND, TILES, LR> : (kind == L2_KIND_GEN || LR) ? cd_life_kernel<NMW, CS, L2_KIND_GEN, TILES, LR>
              : kind == L2_KIND_GENK ? cd_life_kernel<NMW, CS, MK ? L2_KIND_GENK : L2_KIND_GEN, TILES, LR>
              : kind == L2_KIND_LINK ? cd_life_kernel<NMW, CS, MK ? L2_KIND_LINK : L2_KIND_GEN, TILES, LR>
                                     : cd_life_kernel<NMW, CS, LR ? L2_KIND_GEN : L2_KIND_LIN, TILES, LR>;
@@ -1740,7 +1773,9 @@ bool cd_life2_config(const DevProblem &P, int Kreal, int objclass, bool symcls, 
     // coordinate (every real coordinate constrained): GENK / LINK
     if (!P.sep || P.maxc < 1 || P.maxc > 2 || Kreal < 1 || Kreal > L2_KCL) return false;
     const bool multi = P.maxc > 1 || Kreal > 1;
-    if (objclass != 1 && objclass != 2) return false;
+    // objclass 0 = a diagonal of mixed sign (or zero in places): the SGN kind, one class with one constraint per coordinate only
+    if (objclass != 0 && objclass != 1 && objclass != 2) return false;
+    if (objclass == 0 && multi) return false;
     const int NB = (int)P.NB;
     if (NB < 3) return false;
     int w, c;
@@ -1750,7 +1785,7 @@ bool cd_life2_config(const DevProblem &P, int Kreal, int objclass, bool symcls, 
     else if (NB - 4 <= 7 * RQ_MAXU) { w = 7; c = 4; }
     else return false;
     *nmw = w; *cs = c;
-    *kind = multi ? (objclass == 2 ? L2_KIND_LINK : L2_KIND_GENK) : objclass == 2 ? L2_KIND_LIN : (symcls ? L2_KIND_BAND : L2_KIND_GEN);
+    *kind = objclass == 0 ? L2_KIND_SGN : multi ? (objclass == 2 ? L2_KIND_LINK : L2_KIND_GENK) : objclass == 2 ? L2_KIND_LIN : (symcls ? L2_KIND_BAND : L2_KIND_GEN);
     return true;
 }
 
@@ -1789,7 +1824,7 @@ int cd_life2_launch(const CdLife2Args &a, int nmw, int cs, int kind, int tiles, 
     }
     if (wgs < 1) wgs = 1;
     if (lr) {
-        if (nmw != 3 || cs != 0 || kind == L2_KIND_LIN) return (int)hipErrorInvalidValue;
+        if (nmw != 3 || cs != 0 || kind == L2_KIND_LIN || kind == L2_KIND_SGN) return (int)hipErrorInvalidValue;
         return tiles == 2 ? l2_launch_kind<3, 0, 2, 1>(a, kind, wgs, lds, st) : l2_launch_kind<3, 0, 1, 1>(a, kind, wgs, lds, st);
     }
     if (tiles != 1) return (int)hipErrorInvalidValue;
@@ -1806,6 +1841,7 @@ int cd_life2_launch(const CdLife2Args &a, int nmw, int cs, int kind, int tiles, 
 const char *cd_life2_name(int nmw, int kind, int tiles, int lr) {
     if (kind == L2_KIND_GENK) return nmw == 3 ? "cd_life_kernel<3,gen,classes>" : "cd_life_kernel<7,gen,classes>";
     if (kind == L2_KIND_LINK) return nmw == 3 ? "cd_life_kernel<3,lin,classes>" : "cd_life_kernel<7,lin,classes>";
+    if (kind == L2_KIND_SGN) return nmw == 3 ? "cd_life_kernel<3,sgn>" : "cd_life_kernel<7,sgn>";
     if (lr) return tiles == 2 ? (kind == L2_KIND_BAND ? "cd_life_kernel<3,band,2 tiles,factored>" : "cd_life_kernel<3,gen,2 tiles,factored>")
                               : (kind == L2_KIND_BAND ? "cd_life_kernel<3,band,factored>" : "cd_life_kernel<3,gen,factored>");
     if (tiles == 2) return kind == L2_KIND_BAND ? "cd_life_kernel<3,band,2 tiles>" : kind == L2_KIND_GEN ? "cd_life_kernel<3,gen,2 tiles>" : "cd_life_kernel<3,lin,2 tiles>";

@@ -8,6 +8,7 @@ with the objective first (relop ``None``) -- the raw-array form accepted by
 * ``boolean_least_squares``  -- examples/boolean_least_squares.py:6-15
 * ``maxcut``                 -- examples/maxcut.py:9-21
 * ``box_least_squares``      -- the box-constrained sibling of the Boolean family (one interval per coordinate)
+* ``box_qp``                 -- the box-constrained QP with an INDEFINITE objective (a diagonal of mixed sign)
 * ``beamforming``            -- examples/secondary_user_beamforming.py:18-41
 * ``dense_indefinite``       -- SURVEY.md section 8(d) cfg5 generator
 * ``circle_packing``         -- examples/circle_packing.py:6-17 (two variables: centres 2 x N and the radius)
@@ -57,6 +58,43 @@ def box_least_squares(n, m_rows, bound=1.0, seed=1, ridge=0.1):
         P = sp.csr_matrix(([1.0], ([i], [i])), shape=(n, n))
         funcs.append((P, np.zeros(n), -float(bound) ** 2, '<='))
     return funcs, False, dict(A=A, b=b)
+
+
+def box_qp(n, seed=1, lo=-1.0, hi=1.0, zero_every=0, density=1.0, relop='<=', diagonal=None):
+    """minimize x^T P0 x + q0^T x  s.t. (x_i - lo)(x_i - hi) <= 0  -- the box-constrained QP with an indefinite objective, the
+    textbook nonconvex QCQP.  P0 = (G + G^T) / 2 with G ~ N(0, 1): its diagonal is N(0, 1), about half of it negative; q0 =
+    sqrt(n) N(0, 1) (the scale of a row of P0 times a point of the box).  ONE constraint class, one constraint per coordinate.
+      zero_every = k > 0   every k-th diagonal entry of P0 (i = k - 1, 2 k - 1, ...) is set to 0: a diagonal of all three signs
+      density < 1          every off-diagonal pair (i, j), (j, i) is kept with this probability (the diagonal always)
+      relop = '=='         the two-interval sibling (x_i - lo)(x_i - hi) == 0, i.e. x_i in {lo, hi} (x_i^2 == 1 for the box
+                           [-1, 1]): at the slack s phase 1 leaves, the feasible set is one interval around lo and one around hi
+      diagonal             'negative': the diagonal is replaced by -|diagonal|, a concave scalar objective in every coordinate
+                           (zero_every still applies); 'only': the off-diagonal part is dropped (every coordinate on its own)
+    Returns (funcs, maximize, info) like the other generators; info['diag'] is the diagonal of P0."""
+    rs = np.random.RandomState(seed)
+    G = rs.randn(n, n)
+    P0 = (G + G.T) / 2.
+    q0 = np.sqrt(n) * rs.randn(n)
+    if density < 1.0:
+        keep = np.triu(rs.uniform(size=(n, n)) < density, 1)
+        P0 = P0 * (keep + keep.T + np.eye(n, dtype=bool))
+    d = np.diag(P0).copy()
+    if diagonal == 'negative':
+        d = -np.abs(d)
+    elif diagonal == 'only':
+        P0 = np.zeros((n, n))
+    elif diagonal is not None:
+        raise KeyError(diagonal)
+    if zero_every > 0:
+        d[zero_every - 1::zero_every] = 0.0
+    P0[np.arange(n), np.arange(n)] = d
+    funcs = [(P0, q0, 0.0, None)]
+    for i in range(n):
+        P = sp.csr_matrix(([1.0], ([i], [i])), shape=(n, n))
+        qv = np.zeros(n)
+        qv[i] = -(float(lo) + float(hi))
+        funcs.append((P, qv, float(lo) * float(hi), relop))
+    return funcs, False, dict(diag=d)
 
 
 def multi_class(name, n, seed=1):
