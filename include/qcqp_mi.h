@@ -342,6 +342,33 @@ int qcqpmi_cd_stream_run(qcqpmi_ctx *ctx, int64_t K, int64_t R, int generate, in
                          double select_tol, int64_t *sweeps1, int64_t *sweeps2, int64_t *visits2, int64_t *accepted2,
                          uint8_t *ran_phase2, double *f0, double *maxviol, int64_t *best_index, double *best_f0,
                          double *best_maxviol, double *best_x);
+/* MANY SMALL PROBLEMS IN ONE LAUNCH (added within ABI 6: a new symbol, nothing else changes).  B problems that share n <= 64
+ * and ONE set of separable constraint lists -- those of this context, created and finalized as usual with any objective as
+ * function 0 (every class and up to four constraints per coordinate, as qcqpmi_cd_run takes them) -- and differ in their objective:
+ * P0s [B][n][n] (each symmetric, any diagonal sign, any definiteness), q0s [B][n], r0s [B].  A frame of MIMO detection problems is
+ * the example: thousands of Boolean least squares instances with n = 8 .. 64, P0_b = A_b^T A_b, q0_b = -2 A_b^T b_b, x_i^2 == 1.
+ * Every problem gets R restarts.  Restart (b, r) IS the restart r that a context holding the constraints and objective b produces by
+ *     qcqpmi_pop_randn(R, seed + b seed_stride, first_index)        (generate = 0: the uploaded starts X0 [B][R][n] instead)
+ *     qcqpmi_cd_run(phase1, num_iters, viol_tol, tol, seed + b seed_stride, first_index):
+ * the same keyed draws by the global restart index first_index + r (normals, tie draws, the zero-objective draw), the same phase 1,
+ * gate, phase 2, counters and status codes; the moves agree to the rounding of the row sums (P0 x)_i (summed in index order here, on
+ * the matrix cores there).  A result depends on (objective b, its seed, the global index) alone: not on B, not on the problems
+ * beside b, not on the number of workgroups or the order in which the work is dealt out -- bit for bit.
+ * One persistent launch of cd_small_kernel (csrc/cd_small.hip): one wavefront per (problem, restart), lane = coordinate, P0_b staged
+ * in LDS once per workgroup.  Outputs, any may be NULL: per restart [B R] (problem-major) the arrays of qcqpmi_cd_run, the status
+ * codes of qcqpmi_cd_status (a restart with a code != 0 reports f0 = maxviol = +inf and never wins; the call itself succeeds) and the
+ * final points X [B][R][n]; per problem [B] the best restart (index within the problem; QCQPForm.better ordering with bucket width
+ * select_tol, ties -> lowest index, like qcqpmi_select_best), its objective, max violation and point best_x [B][n].
+ * QCQPMI_EUNSUPPORTED: constraints that are not separable, n > 64.  QCQPMI_EINVAL: B < 1, R < 1, B R >= 2^30, a missing input, a
+ * P0_b that is not symmetric.  The call works in buffers of its own: the resident population, its evaluation and its status codes
+ * stay as they were, whether the call succeeds or is refused.  qcqpmi_last_cd_kernel: "cd_small_kernel<1>" (at most one constraint
+ * per coordinate) / "cd_small_kernel<4>". */
+int qcqpmi_cd_small_batch_run(qcqpmi_ctx *ctx, int64_t B, const double *P0s, const double *q0s, const double *r0s, int64_t R,
+                              int generate, const double *X0, int phase1, int64_t num_iters, double viol_tol, double tol,
+                              uint64_t seed, uint64_t seed_stride, uint64_t first_index, double select_tol, int64_t *sweeps1,
+                              int64_t *sweeps2, int64_t *visits2, int64_t *accepted2, uint8_t *ran_phase2, int *status1,
+                              int *status2, double *f0, double *maxviol, double *X, int64_t *best_index, double *best_f0,
+                              double *best_maxviol, double *best_x);
 /* Device and pinned-host buffers for a qcqpmi_cd_stream_run(K, R) to come (population, per-restart outputs, per-population
  * winners): allocation only, so that a timed or latency-sensitive run does not start with hipMalloc / hipHostMalloc.  A
  * resident population smaller than K R points is dropped (like any reallocation of the population). */

@@ -1,0 +1,106 @@
+"""QCQPBatch: many SMALL problems that share their constraints, solved in one launch.
+
+A frame of MIMO detection problems is thousands of independent Boolean least squares instances of 8 .. 64 variables: every
+instance has its own objective and all of them the constraints x_i^2 == 1.  ``QCQP`` holds one problem per context; this class
+holds B of them on ONE context and runs suggest(RANDOM) + improve(COORD_DESCENT) for all B x R restarts through one persistent
+kernel (``Engine.cd_small_batch_run``, qcqpmi_cd_small_batch_run).  Problem b's results are those of
+``QCQP(Problem(funcs_b))`` with suggest(RANDOM, num_samples=R, seed=seed + b seed_stride, first_index=...) followed by
+improve(COORD_DESCENT, ..., seed=seed + b seed_stride, first_index=...).
+
+    from qcqp_amd.batch import QCQPBatch
+    from qcqp_amd import problems, settings as s
+    batch = QCQPBatch(problems.boolean_least_squares_batch(B=4096, n=32, m=48, seed=1))
+    batch.suggest(s.RANDOM, num_samples=64, seed=7)
+    f, v = batch.improve(s.COORD_DESCENT)          # (B,), (B,): the best restart of every problem
+    batch.x                                        # (B, n)
+"""
+import numpy as np
+import scipy.sparse as sp
+
+from . import settings as s
+from .engine import Engine
+from .form import QCQPForm
+
+
+def _dense(P):
+    return np.asarray(P.toarray() if sp.issparse(P) else P, dtype=np.float64)
+
+
+def _same_constraints(fa, fb):
+    if len(fa) != len(fb):
+        return False
+    for (Pa, qa, ra, oa), (Pb, qb, rb, ob) in zip(fa[1:], fb[1:]):
+        if oa != ob or float(ra) != float(rb):
+            return False
+        if not np.array_equal(np.asarray(qa, dtype=np.float64).ravel(), np.asarray(qb, dtype=np.float64).ravel()):
+            return False
+        if Pa is not Pb and not np.array_equal(_dense(Pa), _dense(Pb)):
+            return False
+    return True
+
+
+class QCQPBatch(object):
+    """``funcs_list`` = [funcs_0, ..., funcs_{B-1}], every funcs_b = [(P, q, r, relop), ...] in minimise form with the objective
+    first (what qcqp_amd.problems returns).  All problems must have the same n (<= 64) and the same constraints."""
+
+    def __init__(self, funcs_list, device=0):
+        funcs_list = [list(f) for f in funcs_list]
+        if not funcs_list:
+            raise Exception("QCQPBatch: empty list of problems")
+        n = int(np.asarray(funcs_list[0][0][1]).size)
+        for b, funcs in enumerate(funcs_list):
+            nb = int(np.asarray(funcs[0][1]).size)
+            if nb != n:
+                raise Exception("QCQPBatch: problem %d has n = %d, problem 0 has n = %d" % (b, nb, n))
+            if b > 0 and not _same_constraints(funcs_list[0], funcs):
+                raise Exception("QCQPBatch: the constraints of problem %d differ from those of problem 0" % b)
+        self.B, self.n = len(funcs_list), n
+        self.P0s = np.empty((self.B, n, n))
+        self.q0s = np.empty((self.B, n))
+        self.r0s = np.empty(self.B)
+        for b, funcs in enumerate(funcs_list):
+            P = _dense(funcs[0][0])
+            self.P0s[b] = (P + P.T) / 2.          # like get_qcqp_form (utilities.py:333)
+            self.q0s[b] = np.asarray(funcs[0][1], dtype=np.float64).ravel()
+            self.r0s[b] = float(funcs[0][2])
+        self.engine = Engine(QCQPForm.from_arrays(funcs_list[0]), device=device)
+        self._suggested = None
+        self.x = None
+        self.population_f = None
+        self.population_v = None
+        self.best_index = None
+        self.last_stats = None
+
+    def suggest(self, method=s.RANDOM, num_samples=1, seed=0, first_index=0, seed_stride=1):
+        """R = num_samples random starts per problem: problem b draws the keyed normals (seed + b seed_stride, first_index + r).
+        The points are drawn inside the launch of improve(); nothing runs here."""
+        if method != s.RANDOM:
+            raise Exception("QCQPBatch.suggest is defined for the RANDOM method")
+        if int(num_samples) < 1:
+            raise Exception("QCQPBatch.suggest: num_samples must be positive")
+        self._suggested = (int(num_samples), int(seed), int(first_index), int(seed_stride))
+
+    def improve(self, method=s.COORD_DESCENT, num_iters=1000, viol_tol=1e-2, tol=1e-4, phase1=True, seed=None):
+        """improve(COORD_DESCENT) of every suggested start of every problem; returns (f (B,), v (B,)) of the best restart per
+        problem (QCQPForm.better, ties -> lowest index) and sets .x (B, n), .population_f / .population_v (B, R), .best_index,
+        .last_stats.  seed: the seed of suggest() (a problem's normals and its draws come from ONE keyed stream)."""
+        if method != s.COORD_DESCENT:
+            raise Exception("QCQPBatch.improve is defined for the COORD_DESCENT method")
+        if self._suggested is None:
+            raise Exception("QCQPBatch.improve: call suggest(RANDOM, num_samples=R, seed=...) first")
+        R, sd, first_index, stride = self._suggested
+        if seed is not None and int(seed) != sd:
+            raise Exception("QCQPBatch.improve: seed %d differs from the seed of suggest (%d); the batch runs one keyed stream per problem"
+                            % (int(seed), sd))
+        out = self.engine.cd_small_batch_run(self.P0s, self.q0s, self.r0s, R, phase1=phase1, num_iters=num_iters, viol_tol=viol_tol,
+                                             tol=tol, seed=sd, seed_stride=stride, first_index=first_index, want_x=False)
+        self.x = out['best_x']
+        self.best_index = out['best_index']
+        self.population_f, self.population_v = out['f0'], out['maxviol']
+        failed = int(np.count_nonzero((out['status1'] != 0) | (out['status2'] != 0)))
+        self.last_stats = dict(out, method=method, num_problems=self.B, num_restarts=R, failed_restarts=failed,
+                               kernel=self.engine.last_cd_kernel())
+        return out['best_f0'], out['best_maxviol']
+
+    def close(self):
+        self.engine.close()

@@ -20,6 +20,7 @@
 #include "admm_fused.h"
 #include "cd_queue.h"
 #include "cd_life.h"
+#include "cd_small.h"
 #include "gemm_pk.h"
 #include "cd_general.h"
 #include "cd_dense.h"
@@ -213,6 +214,10 @@ struct qcqpmi_ctx {
     bool cd_ref_order = false;   // qcqpmi_cd_reference_order: coupled constraints in the reference's summation order
     bool force_generic = false;  // debug/tests: run the general phase-2 kernel even when the pipelined one applies
     std::vector<int> last_st1, last_st2;   // per-restart status codes of the last coordinate-descent run (qcqpmi_cd_status)
+    // qcqpmi_cd_small_batch_run: ONE device buffer for the objectives, starts, per-restart outputs, points and winners of a call
+    // (grown on demand; the resident population and its buffers are never used by that call)
+    char *sb_work = nullptr;
+    size_t sb_work_cap = 0;
 };
 
 namespace {
@@ -749,7 +754,7 @@ void qcqpmi_ctx_destroy(qcqpmi_ctx *c) {
     admm_free(c, false);
     for (void *p : c->prob_allocs) (void)hipFree(p);
     void *ptrs[] = {c->d_Fpack, c->d_Frow, c->d_mu, c->d_best_idx, c->d_best_key, c->d_comm, c->d_comm_big,   // d_gP is in prob_allocs
-                    c->dn_G, c->dn_Dg, c->dn_Ft, c->dn_prof, c->dn_state, c->d_planes, c->d_out, c->d_wS, c->d_wY, c->d_ww, c->d_wz, c->af_work, c->d_qnext, c->d_life, c->d_life_prof, c->d_bestK_idx, c->d_bestK_key, c->d_bestK_x, c->l2_scratch, c->l2_D, c->l2_S, c->l2_abort, c->l2_cuslot, c->l2_preslack, c->lr_L, c->lr_G, c->lr_U};
+                    c->dn_G, c->dn_Dg, c->dn_Ft, c->dn_prof, c->dn_state, c->d_planes, c->d_out, c->d_wS, c->d_wY, c->d_ww, c->d_wz, c->af_work, c->d_qnext, c->d_life, c->d_life_prof, c->d_bestK_idx, c->d_bestK_key, c->d_bestK_x, c->l2_scratch, c->l2_D, c->l2_S, c->l2_abort, c->l2_cuslot, c->l2_preslack, c->lr_L, c->lr_G, c->lr_U, c->sb_work};
     if (c->h_out) (void)hipHostFree(c->h_out);
     if (c->h_pin) (void)hipHostFree(c->h_pin);
     for (void *p : ptrs) if (p) (void)hipFree(p);
@@ -1723,6 +1728,116 @@ int qcqpmi_cd_stream_run(qcqpmi_ctx *c, int64_t K, int64_t R, int generate, int 
         stm[5] = stnow();
         fprintf(stderr, "cd_stream_run timing (ms): set-up %.3f, launch + kernel %.3f, fetch %.3f, status %.3f, best %.3f\n", stm[1] - stm[0], stm[2] - stm[1],
                 stm[3] - stm[2], stm[4] - stm[3], stm[5] - stm[4]);
+    }
+    return 0;
+}
+
+// ---- B small problems (n <= 64) that share the context's separable constraints, R restarts each, in ONE launch of cd_small_kernel
+// (csrc/cd_small.hip).  Works in a buffer of its own: the resident population, its evaluation and its status codes are not touched,
+// whether the call succeeds or is refused.
+int qcqpmi_cd_small_batch_run(qcqpmi_ctx *c, int64_t B, const double *P0s, const double *q0s, const double *r0s, int64_t R, int generate,
+                              const double *X0, int phase1, int64_t num_iters, double viol_tol, double tol, uint64_t seed,
+                              uint64_t seed_stride, uint64_t first_index, double select_tol, int64_t *sweeps1, int64_t *sweeps2,
+                              int64_t *visits2, int64_t *accepted2, uint8_t *ran_phase2, int *status1, int *status2, double *f0,
+                              double *maxviol, double *X, int64_t *best_index, double *best_f0, double *best_maxviol, double *best_x) {
+    int rc = check_ready(c, false);
+    if (rc) return rc;
+    if (!c->sep) return fail(c, QCQPMI_EUNSUPPORTED, "cd_small_batch_run: the constraints are not separable (a constraint couples coordinates, or a coordinate carries more than 4)");
+    if (c->n > CD_SMALL_MAXN) return fail(c, QCQPMI_EUNSUPPORTED, "cd_small_batch_run: n = %lld, the small-problem kernel takes n <= %d (one lane per coordinate)", (long long)c->n, CD_SMALL_MAXN);
+    if (B < 1 || R < 1 || num_iters < 0 || !(tol > 0.0) || !P0s || !q0s || !r0s || (!generate && !X0))
+        return fail(c, QCQPMI_EINVAL, "cd_small_batch_run: bad B / R / num_iters / tol, or a missing input array");
+    if (B >= (1LL << 30) || R >= (1LL << 30) || B * R >= (1LL << 30)) return fail(c, QCQPMI_EINVAL, "cd_small_batch_run: B R = %lld restarts, at most 2^30 - 1 per call", (long long)(B * R));
+    HIPCHK(c, hipSetDevice(c->device));
+    const int64_t n = c->n, T = B * R;
+    // ---- carve the work buffer (every piece 256-byte aligned)
+    size_t off = 0;
+    auto take = [&off](size_t bytes) { const size_t o = off; off += (bytes + 255) / 256 * 256; return o; };
+    const size_t oP = take((size_t)B * n * n * 8), oq = take((size_t)B * n * 8), or0 = take((size_t)B * 8);
+    const size_t oX0 = take(generate ? 0 : (size_t)T * n * 8), oX = take((size_t)T * n * 8);
+    const size_t oout = take((size_t)T * 57);      // 4 x int64, 2 x double, 2 x int, 1 x uint8 per restart, array after array
+    const size_t oticket = take(2 * sizeof(int));
+    const size_t obi = take((size_t)B * 2 * sizeof(int64_t)), obk = take((size_t)B * 2 * sizeof(double)), obx = take((size_t)B * n * 8);
+    if (off > c->sb_work_cap) {
+        HIPCHK(c, spin_sync(c->stream));
+        if (c->sb_work) (void)hipFree(c->sb_work);
+        c->sb_work = nullptr; c->sb_work_cap = 0;
+        HIPCHK(c, hipMalloc((void **)&c->sb_work, off));
+        c->sb_work_cap = off;
+    }
+    char *w = c->sb_work;
+    HIPCHK(c, hipMemcpyAsync(w + oP, P0s, (size_t)B * n * n * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(w + oq, q0s, (size_t)B * n * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(w + or0, r0s, (size_t)B * 8, hipMemcpyHostToDevice, c->stream));
+    if (!generate) HIPCHK(c, hipMemcpyAsync(w + oX0, X0, (size_t)T * n * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemsetAsync(w + oticket, 0, 2 * sizeof(int), c->stream));
+    CdSmallArgs a;
+    a.P = c->dp; a.B = B; a.R = R;
+    a.P0s = (const double *)(w + oP); a.q0s = (const double *)(w + oq); a.r0s = (const double *)(w + or0);
+    a.X0 = generate ? nullptr : (const double *)(w + oX0);
+    a.generate = generate ? 1 : 0; a.phase1 = phase1 ? 1 : 0; a.num_iters = num_iters; a.viol_tol = viol_tol; a.tol = tol;
+    a.seed = seed; a.seed_stride = seed_stride; a.first_index = first_index;
+    a.ticket = (int *)(w + oticket);
+    char *o = w + oout;
+    a.sweeps1 = (int64_t *)o; a.sweeps2 = (int64_t *)(o + 8 * T); a.visits2 = (int64_t *)(o + 16 * T); a.accepted2 = (int64_t *)(o + 24 * T);
+    a.f0 = (double *)(o + 32 * T); a.maxviol = (double *)(o + 40 * T);
+    a.status1 = (int *)(o + 48 * T); a.status2 = (int *)(o + 52 * T); a.ran2 = (uint8_t *)(o + 56 * T);
+    a.X = (double *)(w + oX);
+    // tickets: whole problems when there are enough of them to fill the device, else chunks of at least 4 restarts (one per wave)
+    const int maxc = c->maxc <= 1 ? 1 : 4;
+    int wgs = cd_small_workgroups(n, maxc, B * R, c->device);
+    if (wgs < 1) return fail(c, QCQPMI_EHIP, "cd_small_batch_run: occupancy query failed: %s", hipGetErrorString((hipError_t)(-wgs)));
+    int64_t chunks = B >= wgs ? 1 : (wgs + B - 1) / B;
+    if (chunks > (R + 3) / 4) chunks = (R + 3) / 4;
+    a.RC = (R + chunks - 1) / chunks;
+    a.chunks = (R + a.RC - 1) / a.RC;
+    if (wgs > B * a.chunks) wgs = (int)(B * a.chunks);
+    (void)hipEventRecord(c->timers[2].beg, c->stream);
+    hipError_t qe = (hipError_t)cd_small_launch(a, maxc, wgs, c->stream);
+    (void)hipEventRecord(c->timers[2].end, c->stream);
+    c->timers[2].valid = true;
+    if (qe != hipSuccess) return fail(c, QCQPMI_EHIP, "cd_small_batch_run: %s", hipGetErrorString(qe));
+    c->last_cd2_kernel = cd_small_name(maxc);
+    const bool want_best = best_index || best_f0 || best_maxviol || best_x;
+    if (want_best) {       // QCQPForm.better folded over every problem's restarts, ties -> lowest index: one workgroup per problem
+        hipLaunchKernelGGL(select_best_kernel, dim3((unsigned)B), dim3(1024), 0, c->stream, (const double *)a.f0, (const double *)a.maxviol, R,
+                           select_tol, (int64_t *)(w + obi), (double *)(w + obk));
+        HIPCHK(c, hipGetLastError());
+        if (best_x) {
+            HIPCHK(c, hipMemsetAsync(w + obx, 0, (size_t)B * n * 8, c->stream));
+            qe = (hipError_t)cd_small_gather_launch(a.X, n, R, B, (const int64_t *)(w + obi), (double *)(w + obx), c->stream);
+            if (qe != hipSuccess) return fail(c, QCQPMI_EHIP, "cd_small_batch_run: %s", hipGetErrorString(qe));
+        }
+    }
+    std::vector<char> hout((size_t)T * 57);
+    std::vector<int64_t> bidx(want_best ? (size_t)B * 2 : 0);
+    std::vector<double> bkey(want_best ? (size_t)B * 2 : 0);
+    int flags[2] = {0, 0};
+    HIPCHK(c, hipMemcpyAsync(flags, w + oticket, sizeof(flags), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, spin_sync(c->stream));
+    if (flags[1]) return fail(c, QCQPMI_EINVAL, "cd_small_batch_run: an objective matrix P0_b is not symmetric (or holds a NaN)");
+    HIPCHK(c, hipMemcpyAsync(hout.data(), o, hout.size(), hipMemcpyDeviceToHost, c->stream));
+    if (X) HIPCHK(c, hipMemcpyAsync(X, a.X, (size_t)T * n * 8, hipMemcpyDeviceToHost, c->stream));
+    if (want_best) {
+        HIPCHK(c, hipMemcpyAsync(bidx.data(), w + obi, bidx.size() * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(bkey.data(), w + obk, bkey.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        if (best_x) HIPCHK(c, hipMemcpyAsync(best_x, w + obx, (size_t)B * n * 8, hipMemcpyDeviceToHost, c->stream));
+    }
+    HIPCHK(c, spin_sync(c->stream));
+    const char *h = hout.data();
+    const size_t n8 = (size_t)T * 8;
+    if (sweeps1) memcpy(sweeps1, h, n8);
+    if (sweeps2) memcpy(sweeps2, h + n8, n8);
+    if (visits2) memcpy(visits2, h + 2 * n8, n8);
+    if (accepted2) memcpy(accepted2, h + 3 * n8, n8);
+    if (f0) memcpy(f0, h + 4 * n8, n8);
+    if (maxviol) memcpy(maxviol, h + 5 * n8, n8);
+    if (status1) memcpy(status1, h + 6 * n8, (size_t)T * 4);
+    if (status2) memcpy(status2, h + 6 * n8 + (size_t)T * 4, (size_t)T * 4);
+    if (ran_phase2) memcpy(ran_phase2, h + 7 * n8, (size_t)T);
+    for (int64_t b = 0; b < B && want_best; b++) {
+        if (best_index) best_index[b] = bidx[(size_t)2 * b];
+        if (best_f0) best_f0[b] = bkey[(size_t)2 * b];
+        if (best_maxviol) best_maxviol[b] = bkey[(size_t)2 * b + 1];
     }
     return 0;
 }

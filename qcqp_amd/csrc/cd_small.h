@@ -1,0 +1,48 @@
+// Small-problem batch kernel: interface between capi.hip and cd_small.hip (own translation unit).
+//
+// improve_coord_descent (qcqp.py:181-192) for B problems of n <= 64 variables that share ONE set of separable constraint lists
+// and differ in their objective (P0_b, q0_b, r0_b) -- a frame of MIMO detection problems: thousands of Boolean least squares
+// instances of n = 8..64 -- R restarts each, inside ONE persistent launch (qcqpmi_cd_small_batch_run).  Restart (b, r) is the
+// restart r that qcqpmi_pop_randn(R, seed + b seed_stride, first_index) + qcqpmi_cd_run(seed + b seed_stride, first_index) produce on
+// a context that holds the constraints and objective b: the keyed draws go by the GLOBAL restart index first_index + r, so a
+// result depends on nothing but (objective b, seed of b, global index) -- not on B, the neighbours, the workgroups or the order
+// in which the work is dealt out.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include "kernels.h"
+
+namespace qcqpmi {
+
+constexpr int CD_SMALL_MAXN = 64;        // lane = coordinate: one wavefront holds a point
+
+struct CdSmallArgs {
+    DevProblem P;                // n and the shared per-coordinate constraint lists (cptr / cp / cq / cr / crel); its objective is not read
+    int64_t B, R;
+    int64_t RC, chunks;          // a ticket = (problem, RC consecutive restarts); chunks = tickets per problem
+    const double *P0s;           // [B][n][n] symmetric
+    const double *q0s;           // [B][n]
+    const double *r0s;           // [B]
+    const double *X0;            // [B][R][n] start points (generate == 0), else unused
+    int generate, phase1;
+    int64_t num_iters;
+    double viol_tol, tol;
+    uint64_t seed, seed_stride, first_index;
+    int *ticket;                 // [0] zeroed before the launch: next ticket; [1] set when some P0_b is not symmetric
+    // per restart [B R]
+    int64_t *sweeps1, *sweeps2, *visits2, *accepted2;
+    uint8_t *ran2;
+    int *status1, *status2;
+    double *f0, *maxviol;
+    double *X;                   // [B][R][n] final points
+};
+
+size_t cd_small_lds_bytes(int64_t n);
+// workgroups of the launch (persistent: at most what the device holds at once), or < 0: -hipError_t
+int cd_small_workgroups(int64_t n, int maxc, int64_t tickets, int device);
+int cd_small_launch(const CdSmallArgs &a, int maxc, int wgs, hipStream_t st);
+const char *cd_small_name(int maxc);
+// the winners' points: out[b][0..n) = X[b][idx[2 b]][0..n)  (idx as select_best_kernel leaves it; < 0: row left as it is)
+int cd_small_gather_launch(const double *X, int64_t n, int64_t R, int64_t B, const int64_t *idx, double *out, hipStream_t st);
+
+}  // namespace qcqpmi

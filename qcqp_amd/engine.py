@@ -212,6 +212,41 @@ class Engine(object):
         out['status1'], out['status2'] = st1, st2
         return out
 
+    def cd_small_batch_run(self, P0s, q0s, r0s, R, X0=None, phase1=True, num_iters=1000, viol_tol=1e-2, tol=1e-4, seed=0,
+                           seed_stride=1, first_index=0, select_tol=1e-4, want_x=True):
+        """B small problems (n <= 64) that share this context's separable constraints and differ in their objective -- P0s (B, n, n)
+        symmetric, q0s (B, n), r0s (B,) -- with R restarts each in ONE launch (qcqpmi_cd_small_batch_run).  Restart (b, r) is restart r
+        of randn(R, seed + b seed_stride, first_index) + cd_run(seed + b seed_stride, first_index) on a context that holds objective b.
+        X0 (B, R, n): start points instead of the keyed normals.  Returns the dictionary of cd_run with arrays of shape (B, R), X
+        (B, R, n) if want_x, and per problem best_index / best_f0 / best_maxviol (B,) and best_x (B, n).  The resident population is
+        not touched."""
+        P0s = np.ascontiguousarray(P0s, dtype=np.float64)
+        q0s = np.ascontiguousarray(q0s, dtype=np.float64)
+        r0s = np.ascontiguousarray(r0s, dtype=np.float64).ravel()
+        B, R, n = int(P0s.shape[0]) if P0s.ndim == 3 else 0, int(R), self.n
+        if P0s.shape != (B, n, n) or q0s.shape != (B, n) or r0s.shape != (B,):
+            raise ValueError('cd_small_batch_run: expected P0s (B, n, n), q0s (B, n), r0s (B,) with n = %d' % n)
+        if X0 is not None:
+            X0 = np.ascontiguousarray(X0, dtype=np.float64)
+            if X0.shape != (B, R, n):
+                raise ValueError('cd_small_batch_run: expected X0 of shape (B, R, n)')
+        T = B * R
+        out = dict(sweeps1=np.zeros(T, dtype=np.int64), sweeps2=np.zeros(T, dtype=np.int64), visits2=np.zeros(T, dtype=np.int64),
+                   accepted2=np.zeros(T, dtype=np.int64), ran_phase2=np.zeros(T, dtype=np.uint8), status1=np.zeros(T, dtype=np.int32),
+                   status2=np.zeros(T, dtype=np.int32), f0=np.empty(T), maxviol=np.empty(T), X=np.empty((B, R, n)) if want_x else None,
+                   best_index=np.zeros(B, dtype=np.int64), best_f0=np.empty(B), best_maxviol=np.empty(B), best_x=np.zeros((B, n)))
+        c_intp = C.POINTER(C.c_int)
+        self._chk(self.L.qcqpmi_cd_small_batch_run(self.h, B, _dp(P0s), _dp(q0s), _dp(r0s), R, 0 if X0 is not None else 1, _dp(X0),
+                                                   int(bool(phase1)), int(num_iters), float(viol_tol), float(tol), int(seed), int(seed_stride),
+                                                   int(first_index), float(select_tol), _ip(out['sweeps1']), _ip(out['sweeps2']),
+                                                   _ip(out['visits2']), _ip(out['accepted2']), _bp(out['ran_phase2']),
+                                                   out['status1'].ctypes.data_as(c_intp), out['status2'].ctypes.data_as(c_intp),
+                                                   _dp(out['f0']), _dp(out['maxviol']), _dp(out['X']), _ip(out['best_index']),
+                                                   _dp(out['best_f0']), _dp(out['best_maxviol']), _dp(out['best_x'])))
+        for k in ('sweeps1', 'sweeps2', 'visits2', 'accepted2', 'ran_phase2', 'status1', 'status2', 'f0', 'maxviol'):
+            out[k] = out[k].reshape(B, R)
+        return out
+
     # the same run in stages (see qcqpmi_cd_run_stage): cd_begin and cd_phase2 only enqueue work on this context's stream
     def cd_begin(self, phase1=True, num_iters=1000, viol_tol=1e-2, tol=1e-4, seed=0, first_index=0):
         """Phase 1 + evaluation + gate of the resident population, asynchronous."""

@@ -9,6 +9,7 @@ with the objective first (relop ``None``) -- the raw-array form accepted by
 * ``maxcut``                 -- examples/maxcut.py:9-21
 * ``box_least_squares``      -- the box-constrained sibling of the Boolean family (one interval per coordinate)
 * ``box_qp``                 -- the box-constrained QP with an INDEFINITE objective (a diagonal of mixed sign)
+* ``boolean_least_squares_batch`` / ``box_qp_batch`` -- B small problems with shared constraints (qcqp_amd.batch.QCQPBatch)
 * ``beamforming``            -- examples/secondary_user_beamforming.py:18-41
 * ``dense_indefinite``       -- SURVEY.md section 8(d) cfg5 generator
 * ``circle_packing``         -- examples/circle_packing.py:6-17 (two variables: centres 2 x N and the radius)
@@ -95,6 +96,36 @@ def box_qp(n, seed=1, lo=-1.0, hi=1.0, zero_every=0, density=1.0, relop='<=', di
         qv[i] = -(float(lo) + float(hi))
         funcs.append((P, qv, float(lo) * float(hi), relop))
     return funcs, False, dict(diag=d)
+
+
+def boolean_least_squares_batch(B, n, m, seed=1, shared_A=False):
+    """B Boolean least squares problems of n variables and m rows with the SAME constraints x_i^2 == 1 -- a frame of MIMO detection
+    problems, one instance per subcarrier and symbol: minimize ||A_b x - b_b||^2.  Problem b draws (A_b, b_b) from
+    RandomState(seed + b) in the order of boolean_least_squares, so problem b IS boolean_least_squares(n, m, seed + b);
+    shared_A=True: one channel matrix A (that of problem 0) for the whole frame, only the received vectors b_b differ.
+    Returns a list of B funcs lists (objective first) for qcqp_amd.batch.QCQPBatch; the constraint tuples are shared objects."""
+    cons = boolean_least_squares(n, m, seed=seed)[0][1:]
+    A0 = np.random.RandomState(seed).randn(m, n)
+    out = []
+    for b in range(int(B)):
+        rs = np.random.RandomState(seed + b)
+        A = rs.randn(m, n)
+        bv = rs.randn(m, 1)
+        if shared_A:
+            A = A0
+        P0 = A.T.dot(A)
+        P0 = (P0 + P0.T) / 2.
+        out.append([(P0, (-2. * A.T.dot(bv)).ravel(), float(bv.T.dot(bv)[0, 0]), None)] + cons)
+    return out
+
+
+def box_qp_batch(n, seeds, **kwargs):
+    """The small-n variant of box_qp for a batch: problem b is box_qp(n, seed=seeds[b], **kwargs) -- its own indefinite objective --
+    and all of them share the constraint tuples of the first (the constraints of box_qp do not depend on the seed).  Returns a
+    list of funcs lists for qcqp_amd.batch.QCQPBatch."""
+    seeds = [int(sd) for sd in np.atleast_1d(seeds)]
+    cons = box_qp(n, seed=seeds[0], **kwargs)[0][1:]
+    return [[box_qp(n, seed=sd, **kwargs)[0][0]] + cons for sd in seeds]
 
 
 def multi_class(name, n, seed=1):
