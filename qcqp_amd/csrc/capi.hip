@@ -1,5 +1,5 @@
 // C ABI of libqcqp_mi.so (declared in include/qcqp_mi.h): context, problem upload, population
-// management, launches of the kernels in kernels.hip, HIP-event timing, lazy RCCL.
+// management, launches of the kernels in kernels_impl.h, HIP-event timing, lazy RCCL.
 #include <dlfcn.h>
 #include <unistd.h>
 #include <hip/hip_runtime.h>
@@ -15,7 +15,7 @@
 #include <vector>
 
 #include "../../include/qcqp_mi.h"
-#include "kernels.hip"
+#include "kernels_impl.h"
 #include "admm.h"
 #include "admm_fused.h"
 #include "cd_queue.h"

@@ -21,6 +21,7 @@
 // Phase 1 runs the reference's bisection on the slack around B-C.
 #pragma once
 #include "cd_dense.h"
+#include "dev_util.h"
 
 namespace qcqpmi {
 
@@ -91,17 +92,6 @@ __device__ inline Seg2 mw_feasible_intervals(double p, double q, double r, int r
 
 struct MwBounds { double Lg, Hg; bool anyempty; };
 
-// order-preserving map double -> u64 (the reductions over the threads of a restart are integer LDS atomics: two instructions
-// per wave instead of a DPP tree per wave plus a second level through LDS)
-__device__ inline unsigned long long mw_key(double x) {
-    const unsigned long long b = (unsigned long long)__double_as_longlong(x);
-    return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
-}
-__device__ inline double mw_unkey(unsigned long long k) {
-    const unsigned long long b = (k >> 63) ? (k & 0x7fffffffffffffffull) : ~k;
-    return __longlong_as_double((long long)b);
-}
-
 // workgroup barrier for LDS traffic only: the wave's LDS operations are complete (they retire in order), then s_barrier.
 __device__ __attribute__((always_inline)) inline void mw_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
@@ -134,14 +124,14 @@ __device__ __attribute__((always_inline)) inline MwBounds mw_bounds_and_gaps(con
         // wave level in registers (DPP), one LDS atomic per wave
         const double Lw = dn_wave_max(L), Hw = dn_wave_min(H);
         if ((tid & 63) == 0) {
-            if (Lw > -QM_INF) atomicMax(W.kL, mw_key(Lw));
-            if (Hw < QM_INF) atomicMin(W.kH, mw_key(Hw));
+            if (Lw > -QM_INF) atomicMax(W.kL, ordered_key(Lw));
+            if (Hw < QM_INF) atomicMin(W.kH, ordered_key(Hw));
         }
     }
     if (empty) W.red[1] = 1;
     mw_barrier();
     MwBounds o;
-    o.Lg = mw_unkey(*W.kL); o.Hg = mw_unkey(*W.kH); o.anyempty = W.red[1] != 0;
+    o.Lg = ordered_unkey(*W.kL); o.Hg = ordered_unkey(*W.kH); o.anyempty = W.red[1] != 0;
     // multiplicity of Hg (the serial thread adds the base interval (-inf, +inf), one more interval ending at +inf)
     if (mH > 0 && H == o.Hg) atomicAdd(&W.red[0], mH);
     pf.tick(2);
@@ -167,7 +157,7 @@ __device__ inline int mw_segments(const MwLds &W, const MwBounds &fs) {
     int ng = W.bi[3], ovf = 0;
     const int mHg = ((fs.Hg == QM_INF) ? 1 : 0) + W.red[0];
     W.bi[3] = 0; W.red[0] = 0; W.red[1] = 0;
-    *W.kL = mw_key(-QM_INF); *W.kH = mw_key(QM_INF);
+    *W.kL = ordered_key(-QM_INF); *W.kH = ordered_key(QM_INF);
     if (ng > DN_GC) { ovf = 1; ng = DN_GC; }
     int ns = 0;
     if (!fs.anyempty && fs.Lg <= fs.Hg) ns = dn_sweep_segments(W.gapa, W.gapb, ng, W.seglo, W.seghi, fs.Lg, fs.Hg, mHg, &ovf);
@@ -248,7 +238,7 @@ __global__ __launch_bounds__(MW_TMAX) void dense_chain_mw_kernel(DenseChainArgs 
     for (int k = tid; k < m1; k += T) W.F[k] = Ftr[k];
     if (tid < 16) { W.xb[tid] = Xt[(16 * (int64_t)b + tid) * 16 + r]; W.dlt[tid] = 0.0; }
     if (tid < 8) { W.bi[tid] = 0; W.red[tid] = 0; }
-    if (tid == 0) { *W.kL = mw_key(-QM_INF); *W.kH = mw_key(QM_INF); *W.kV = mw_key(-QM_INF); }
+    if (tid == 0) { *W.kL = ordered_key(-QM_INF); *W.kH = ordered_key(QM_INF); *W.kV = ordered_key(-QM_INF); }
     // per-restart state: identical in every thread
     bool live = a.S.live[gr] != 0, on = true;
     int64_t upd = a.S.upd[gr], visits = a.S.visits[gr], accepted = a.S.accepted[gr];
@@ -419,14 +409,14 @@ __global__ __launch_bounds__(MW_TMAX) void dense_chain_mw_kernel(DenseChainArgs 
             // ---- B / C. smallest achievable slack by bisection (qcqp.py:117-131)
             {
                 const double vw = dn_wave_max(vloc);
-                if (lane == 0 && vw > -QM_INF) atomicMax(W.kV, mw_key(vw));
+                if (lane == 0 && vw > -QM_INF) atomicMax(W.kV, ordered_key(vw));
             }
             if (inv) W.red[2] = 1;
             mw_barrier();
-            const double viol = mw_unkey(*W.kV);
+            const double viol = ordered_unkey(*W.kV);
             const bool anyinv = W.red[2] != 0;
             mw_barrier();     // every thread has read the words ...
-            if (serial) { *W.kV = mw_key(-QM_INF); W.red[2] = 0; }      // ... before they are reset for the next coordinate
+            if (serial) { *W.kV = ordered_key(-QM_INF); W.red[2] = 0; }      // ... before they are reset for the next coordinate
             if (!anyinv) { status = -3; live = false; on = false; }   // ValueError (qcqp.py:117)
             else {
                 double new_viol = viol, ss = -a.tol, es = viol - a.viol_tol;

@@ -16,69 +16,12 @@
 
 #include "onevar.h"
 #include "cd_phase1_sep.h"
-
-namespace qcqpmi {
-typedef double v4d __attribute__((ext_vector_type(4)));
-template <typename XPtr>
-__device__ inline v4d block_rows_times_X(const double *__restrict__ Ab, XPtr Xs, int kk0, int kk1, int lane, v4d acc) {
-    const int xoff = (lane >> 4) * 16 + (lane & 15);
-    for (int kk = kk0; kk < kk1; kk++) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(Ab[(int64_t)kk * 64 + lane], Xs[kk * 64 + xoff], acc, 0, 0, 0);
-    return acc;
-}
-}  // namespace qcqpmi
-
-#include "cd_phase2_q.h"      // rq_quad_*, RqOwn, rq_block / rq_slot, the LDS flag protocol, RQ_PFU / RQ_RND / RQ_PERS / RQ_MAXU
+#include "cd_chain.h"
+#include "cd_roles.h"      // rq_quad_*, RqOwn, rq_block / rq_slot, rq_load_A / rq_product, the LDS flag protocol, RQ_PFU / RQ_RND / RQ_PERS / RQ_MAXU
 
 namespace qcqpmi {
 namespace {
 
-#define LG __attribute__((address_space(1)))
-template <class T>
-__device__ __attribute__((always_inline)) inline LG T *l2_g(T *p) { return (LG T *)p; }
-__device__ inline int l2_load_int(LG const int *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ inline int l2_add(LG int *p, int v) { return __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-__device__ inline unsigned long long l2_key(double x) {
-    const unsigned long long b = (unsigned long long)__double_as_longlong(x);
-    return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
-}
-__device__ inline double l2_unkey(unsigned long long k) {
-    const unsigned long long b = (k >> 63) ? (k & 0x7fffffffffffffffull) : ~k;
-    return __longlong_as_double((long long)b);
-}
-__device__ inline double l2_wave_max(double v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) { const double w = __shfl_xor(v, o, 64); v = w > v ? w : v; }
-    return v;
-}
-
-// the scalar code of a restart's start -- same expressions as cd_queue.hip (which has to CALL them: inlined they spilled the
-// product loop of its multiplying waves; here the roles are functions of their own and the kernel body is free to inline)
-__device__ __attribute__((always_inline)) inline double l2_keyed_normal_pair(uint64_t seed, uint64_t restart, uint64_t elem, double *odd) {
-    const U4 o = philox4x32_10((uint32_t)(elem >> 1), (uint32_t)(elem >> 33), 0xA5A50000u, (uint32_t)restart, (uint32_t)seed,
-                               (uint32_t)(seed >> 32) ^ (uint32_t)(restart >> 32));
-    const double u1 = (((double)(o.x >> 5) * 67108864.0 + (double)(o.y >> 6)) + 0.5) / 9007199254740992.0;
-    const double u2 = u53(o.z, o.w);
-    const double rad = sqrt(-2.0 * log(u1));
-    const double ang = 6.283185307179586476925286766559 * u2;
-    *odd = rad * sin(ang);
-    return rad * cos(ang);
-}
-__device__ __attribute__((always_inline)) inline double l2_p1_visit(double p, double q, double r, int relop, int64_t i, double x, double tol,
-                                                        double viol_tol, uint64_t seed, uint64_t restart, int64_t t, int *flags,
-                                                        double *vafter) {
-    P1Visit V;
-    if (q == 0.0 && relop == RELOP_EQ && p > 1e-4) {
-        p1_band_visit(p, q, r, i, x, tol, viol_tol, seed, restart, t, V);
-    } else {
-        const double cp[1] = {p}, cq[1] = {q}, cr[1] = {r};
-        const int crel[1] = {relop};
-        p1_sep_visit_core<1>(1, cp, cq, cr, crel, i, x, tol, viol_tol, seed, restart, t, V);
-    }
-    *flags = (V.moved ? 1 : 0) | ((-V.status) << 8);
-    *vafter = V.vafter;
-    return x;
-}
 constexpr int L2_WD = 1 << 21;        // polls before a wait gives up (a wait is a few hundred polls at most)
 enum { L2_ABORT = 3 };                // sync word: a watchdog fired in this workgroup
 
@@ -90,37 +33,6 @@ __device__ __attribute__((always_inline)) inline RqOwn l2_own(int NB, int CS, in
     if (m < 0) { o.first = rest; o.stride = 1; o.nu = CS; }
     else { o.first = m; o.stride = NMW; o.nu = m < rest ? (rest - m + NMW - 1) / NMW : 0; }
     return o;
-}
-
-// chain share: A fragments (pair-packed) of the owned blocks for block row bn -> registers
-template <int NU>
-__device__ __attribute__((always_inline)) inline void l2_load_A(v2d_ (&ar)[2 * NU], LG const double *Apack2, int KS, const RqOwn &o, int lane, int bn) {
-#pragma unroll
-    for (int U = 0; U < NU; U++) {
-        LG const v2d_ *ap = (LG const v2d_ *)Apack2 + ((int64_t)bn * (KS / 2) + 2 * rq_block(o, U)) * 64;
-        ar[2 * U] = ap[(unsigned)lane];
-        ar[2 * U + 1] = ap[64u + (unsigned)lane];
-    }
-}
-template <int NU>
-__device__ __attribute__((always_inline)) inline v4d_ l2_product(v2d_ (&ar)[2 * NU], const double (&bq)[4 * NU], LG const double *Apack2, int KS,
-                                                                 const RqOwn &o, int lane, int hs, int hs2, int bn2, v4d_ acc0) {
-    v4d_ acc = acc0, acc1 = {0.0, 0.0, 0.0, 0.0}, acc2 = acc1, acc3 = acc1;
-#pragma unroll
-    for (int U = 0; U < NU; U++) {
-        if (U < o.nu && U != hs && U != hs2) {   // wave-uniform
-            acc = __builtin_amdgcn_mfma_f64_16x16x4f64(ar[2 * U][0], bq[4 * U], acc, 0, 0, 0);
-            acc1 = __builtin_amdgcn_mfma_f64_16x16x4f64(ar[2 * U][1], bq[4 * U + 1], acc1, 0, 0, 0);
-            acc2 = __builtin_amdgcn_mfma_f64_16x16x4f64(ar[2 * U + 1][0], bq[4 * U + 2], acc2, 0, 0, 0);
-            acc3 = __builtin_amdgcn_mfma_f64_16x16x4f64(ar[2 * U + 1][1], bq[4 * U + 3], acc3, 0, 0, 0);
-        }
-        {
-            LG const v2d_ *ap = (LG const v2d_ *)Apack2 + ((int64_t)bn2 * (KS / 2) + 2 * rq_block(o, U)) * 64;
-            ar[2 * U] = ap[(unsigned)lane];
-            ar[2 * U + 1] = ap[64u + (unsigned)lane];
-        }
-    }
-    return (acc + acc1) + (acc2 + acc3);
 }
 
 // ---- dynamic LDS of a workgroup (doubles), the same view in the kernel and in the role functions.  Shared words first:
@@ -542,13 +454,13 @@ __device__ __attribute__((noinline)) void l2_chain_role(int t_in) {
     (void)ytile; (void)pend; (void)clsb;
     (void)slk; (void)snew; (void)p1key; (void)p1upd; (void)p1fin; (void)p1sw; (void)p1st; (void)gatep; (void)simdof; (void)p1cols; (void)jn;
     const int lane = threadIdx.x & 63, r = lane >> 2, gq = lane & 3;
-    LG const double *Apk = l2_g(l2_uni(par->Apack));
-    LG const double *Apk2 = l2_g(l2_uni(par->Apack2));
-    LG const double *Dpk = l2_g(l2_uni(par->Dpack));
-    LG const double *Spk = l2_g(l2_uni(par->Spack));
-    LG double *Xg = l2_g(l2_uni(par->Xg));
-    LG const int *pnext = l2_g(l2_uni(par->next));
-    LG const int *clsg = l2_g(l2_uni(par->cls));
+    GLB const double *Apk = glb(l2_uni(par->Apack));
+    GLB const double *Apk2 = glb(l2_uni(par->Apack2));
+    GLB const double *Dpk = glb(l2_uni(par->Dpack));
+    GLB const double *Spk = glb(l2_uni(par->Spack));
+    GLB double *Xg = glb(l2_uni(par->Xg));
+    GLB const int *pnext = glb(l2_uni(par->next));
+    GLB const int *clsg = glb(l2_uni(par->cls));
     unsigned long long *pprof = l2_uni(par->prof);
     const int pRtotal = l2_uni(par->Rtotal);
     const int NB = l2_uni(par->NB), KS = l2_uni(par->KS), nlast = l2_uni(par->nlast);
@@ -648,7 +560,7 @@ __device__ __attribute__((noinline)) void l2_chain_role(int t_in) {
         }
         carry = c1;
         if (CS > 0) {
-            l2_load_A<CSU>(arC, Apk2, KS, cown, lane, 0);
+            rq_load_A<CSU>(arC, Apk2, KS, cown, lane, 0);
             double bqC[4 * CSU];
     #pragma unroll
             for (int U = 0; U < CSU; U++) {
@@ -660,7 +572,7 @@ __device__ __attribute__((noinline)) void l2_chain_role(int t_in) {
             for (int U = 0; U < CSU; U++)
     #pragma unroll
                 for (int q = 0; q < 4; q++) cshare[U * 256 + q * 64 + lane] = bqC[4 * U + q];
-            c0 = l2_product<CSU>(arC, bqC, Apk2, KS, cown, lane, rq_slot(cown, bl1), rq_slot(cown, bl2), 1, c0);
+            c0 = rq_product<CSU>(arC, bqC, Apk2, KS, cown, lane, rq_slot(cown, bl1), rq_slot(cown, bl2), 1, c0);
         }
     #pragma unroll
         for (int v = 0; v < 4; v++) fixp[v * 64 + (lane & 15) * 4 + (lane >> 4)] = c0[v];
@@ -696,8 +608,8 @@ __device__ __attribute__((noinline)) void l2_chain_role(int t_in) {
     #pragma unroll
         for (int v = 0; v < 4; v++) xon[v] = Xg[(16 * (int64_t)bn + 4 * v + gq) * 16 + r];
         {   // A fragments of this block's k-steps in the next two block rows (the chain's contribution to both)
-            LG const double *ap = Apk + ((int64_t)bn * KS + 4 * b) * 64 + lane;
-            LG const double *ap2 = Apk + ((int64_t)bn2 * KS + 4 * b) * 64 + lane;
+            GLB const double *ap = Apk + ((int64_t)bn * KS + 4 * b) * 64 + lane;
+            GLB const double *ap2 = Apk + ((int64_t)bn2 * KS + 4 * b) * 64 + lane;
     #pragma unroll
             for (int u = 0; u < 4; u++) { afix[u] = ap[u * 64]; afix2[u] = ap2[u * 64]; }
         }
@@ -977,7 +889,7 @@ __device__ __attribute__((noinline)) void l2_chain_role(int t_in) {
                 const unsigned long long finm = __builtin_amdgcn_ballot_w64(fin);
                 if (finm == ~0ull) break;
                 if (finm != 0ull) {
-                    const bool more = l2_load_int(pnext) < pRtotal;
+                    const bool more = glb_load_int(pnext) < pRtotal;
                     if (more) break;
                 }
             }
@@ -1006,7 +918,7 @@ __device__ __attribute__((noinline)) void l2_chain_role(int t_in) {
             if (tile == 0) {
                 const int both = mine | verdict, all = mine & verdict;
                 bool stop = !(both & 1) || (all & 2);
-                if (!stop && (both & 4)) stop = l2_load_int(pnext) < pRtotal;
+                if (!stop && (both & 4)) stop = glb_load_int(pnext) < pRtotal;
                 rq_sync_write(jw, 0, tag | (stop ? 1 : 0), lane);
                 verdict = stop ? 1 : 0;
             }
@@ -1036,7 +948,7 @@ __device__ __attribute__((noinline)) void l2_chain_role(int t_in) {
                 for (int U = 0; U < CSU; U++)
     #pragma unroll
                     for (int q = 0; q < 4; q++) bqC[4 * U + q] = cshare[U * 256 + q * 64 + lane];
-                acc = l2_product<CSU>(arC, bqC, Apk2, KS, cown, lane, us, rq_slot(cown, bprev), bn2, acc);
+                acc = rq_product<CSU>(arC, bqC, Apk2, KS, cown, lane, us, rq_slot(cown, bprev), bn2, acc);
             }
     #pragma unroll
             for (int v = 0; v < 4; v++) fixp[v * 64 + (lane & 15) * 4 + (lane >> 4)] = acc[v];
@@ -1139,7 +1051,7 @@ __global__ __launch_bounds__((NMW == 3 && TILES == 1) ? 256 : 512, 2) void cd_li
             if (MULTI && C_.n > 2) T2.slow[16 * k_ + (sc_)] = 1;                                                                         \
         }                                                                                                                                \
     }
-    LG double *Xg0 = l2_g(a0.scratch) + (int64_t)blockIdx.x * TILES * n16 * 16;       // this workgroup's X tiles [tile][j][16]
+    GLB double *Xg0 = glb(a0.scratch) + (int64_t)blockIdx.x * TILES * n16 * 16;       // this workgroup's X tiles [tile][j][16]
 
     // ---- roles by hardware SIMD.  The dispatcher deals the waves of a workgroup round robin over the four SIMDs starting
     // wherever the CU's pointer stands (measured, tools/ubench/ubench5.hip: wave w of a four-wave workgroup is NOT on SIMD w).
@@ -1154,7 +1066,7 @@ __global__ __launch_bounds__((NMW == 3 && TILES == 1) ? 256 : 512, 2) void cd_li
         if (a0.cuslot) {
             const unsigned hw = __builtin_amdgcn_s_getreg(4 | (0 << 6) | (31 << 11)), xcc = __builtin_amdgcn_s_getreg(20 | (0 << 6) | (31 << 11));
             // key: XCC, then HW_ID's SE_ID[15:13] and SH_ID[12] (four bits), then CU_ID[11:8]: one counter per compute unit
-            arrival = l2_add(l2_g(a0.cuslot) + (((xcc & 15) << 8) | (((hw >> 12) & 15) << 4) | ((hw >> 8) & 15)), 1);
+            arrival = glb_add(glb(a0.cuslot) + (((xcc & 15) << 8) | (((hw >> 12) & 15) << 4) | ((hw >> 8) & 15)), 1);
         }
         simdof[8] = (arrival & 1) ? (a0.rotmode == 2 ? 16 + 1 : 2) : 0;      // >= 16: a turn among the multiplying SIMDs only
     }
@@ -1164,7 +1076,7 @@ __global__ __launch_bounds__((NMW == 3 && TILES == 1) ? 256 : 512, 2) void cd_li
         for (int f = 0; f < 10; f++) cs_[f * 64 + (tid0 & 63)] = (f == 4) ? 1 : 0;
     }
     if (tid0 < NS) { l2_tl(sid, tid0 >> 4, TD)[tid0 & 15] = -1; l2_tl(sfin, tid0 >> 4, TD)[tid0 & 15] = 0; }
-    LG const CdLife *lf0 = l2_g(a0.life);
+    GLB const CdLife *lf0 = glb(a0.life);
     const long long life_t0 = (tid0 == 0 && lf0->prof) ? (long long)__builtin_amdgcn_s_memtime() : 0;
     __syncthreads();
     int role, rtile = 0;                           // role: 0 chain, 1 .. NMW multiplying wave role - 1; rtile: the tile it works for
@@ -1224,8 +1136,8 @@ __global__ __launch_bounds__((NMW == 3 && TILES == 1) ? 256 : 512, 2) void cd_li
             const int st = tid >> 4, sc = tid & 15;          // slot sc of tile st
             int id = l2_tl(sid, st, TD)[sc], nw = 0;
             if (id < 0) {
-                LG const CdLife *lf = l2_g(lifep);
-                const int idx = l2_add(l2_g(a0.b.next), 1);
+                GLB const CdLife *lf = glb(lifep);
+                const int idx = glb_add(glb(a0.b.next), 1);
                 if (idx < (int)lf->Rtotal) {
                     id = idx; nw = 1;
                     const uint64_t pop = (uint64_t)idx / (uint64_t)lf->Rpop, rho = (uint64_t)idx % (uint64_t)lf->Rpop;
@@ -1253,7 +1165,7 @@ __global__ __launch_bounds__((NMW == 3 && TILES == 1) ? 256 : 512, 2) void cd_li
             // (priority over the neighbour workgroup's product streams: a double-precision instruction of the build otherwise
             //  waits for a whole matrix instruction of the other stream every time -- the build is latency, the streams have slack)
             __builtin_amdgcn_s_setprio(3);
-            LG const CdLife *lf = l2_g(lifep);
+            GLB const CdLife *lf = glb(lifep);
             const long long pt0 = lf->prof ? (long long)__builtin_amdgcn_s_memtime() : 0;
             // prebuilt (cd_life_prep_kernel): the column is the restart's point after phase 1 in b.X, its slack, gate and phase-1
             // counters in global memory -- copy them, nothing else
@@ -1265,14 +1177,14 @@ __global__ __launch_bounds__((NMW == 3 && TILES == 1) ? 256 : 512, 2) void cd_li
             const int rel = P.crel[e0];
             for (int c = 0; c < NS; c++) {
                 const int ct = c >> 4, cc = c & 15;
-                LG double *Xg = Xg0 + (int64_t)ct * n16 * 16;
+                GLB double *Xg = Xg0 + (int64_t)ct * n16 * 16;
                 if (!l2_tl(snew, ct, TD)[cc]) {
                     if (l2_tl(sid, ct, TD)[cc] < 0) for (int64_t j = tid; j < n16; j += NT) Xg[j * 16 + cc] = 0.0;
                     continue;
                 }
                 if (!lf_generate) {        // (also a prebuilt column)
                     const int id = l2_tl(sid, ct, TD)[cc];
-                    LG const double *src = l2_g(a0.b.X) + ((int64_t)(id >> 4) * n16) * 16 + (id & 15);
+                    GLB const double *src = glb(a0.b.X) + ((int64_t)(id >> 4) * n16) * 16 + (id & 15);
                     for (int64_t j0 = tid; j0 < n16; j0 += 4 * NT) {
                         double t4[4];
 #pragma unroll
@@ -1298,12 +1210,12 @@ __global__ __launch_bounds__((NMW == 3 && TILES == 1) ? 256 : 512, 2) void cd_li
                     ch = __builtin_amdgcn_readfirstlane(ch);
                     if (ch >= ncolg * nchg) break;
                     const int c = p1cols[ch / nchg], ct = c >> 4, cc = c & 15;
-                    LG double *Xg = Xg0 + (int64_t)ct * n16 * 16;
+                    GLB double *Xg = Xg0 + (int64_t)ct * n16 * 16;
                     const int64_t j = (int64_t)(ch % nchg) * 128 + 2 * lane;
                     const uint64_t sd = l2_tl(sseed, ct, TD)[cc], gidx = l2_tl(sfirst, ct, TD)[cc] + (uint64_t)l2_tl(sid, ct, TD)[cc];
                     if (j < n16) {
                         double xo = 0.0;
-                        const double xe = (j < P.n) ? l2_keyed_normal_pair(sd, gidx, (uint64_t)j, &xo) : 0.0;
+                        const double xe = (j < P.n) ? keyed_normal_pair(sd, gidx, (uint64_t)j, &xo) : 0.0;
                         Xg[j * 16 + cc] = xe;
                         Xg[(j + 1) * 16 + cc] = (j + 1 < P.n) ? xo : 0.0;
                     }
@@ -1327,7 +1239,7 @@ __global__ __launch_bounds__((NMW == 3 && TILES == 1) ? 256 : 512, 2) void cd_li
                         for (int k = 0; k < NS; k++) if (l2_tl(snew, k >> 4, TD)[k & 15] && !l2_tl(p1fin, k >> 4, TD)[k & 15]) p1cols[cnt++] = k;
                         ctl[4] = cnt; ctl[5] = 0;
                     }
-                    if (tid < NS) { l2_tl(p1key, tid >> 4, TD)[tid & 15] = l2_key(-QM_INF); l2_tl(p1upd, tid >> 4, TD)[tid & 15] = 0; }
+                    if (tid < NS) { l2_tl(p1key, tid >> 4, TD)[tid & 15] = ordered_key(-QM_INF); l2_tl(p1upd, tid >> 4, TD)[tid & 15] = 0; }
                     __syncthreads();
                     const int ncol1 = ctl[4];
                     if (ncol1 == 0) break;
@@ -1337,7 +1249,7 @@ __global__ __launch_bounds__((NMW == 3 && TILES == 1) ? 256 : 512, 2) void cd_li
                         ch = __builtin_amdgcn_readfirstlane(ch);
                         if (ch >= ncol1 * nch) break;
                         const int c = p1cols[ch / nch], ct = c >> 4, cc = c & 15;
-                        LG double *Xg = Xg0 + (int64_t)ct * n16 * 16;
+                        GLB double *Xg = Xg0 + (int64_t)ct * n16 * 16;
                         const uint64_t sd = l2_tl(sseed, ct, TD)[cc], gidx = l2_tl(sfirst, ct, TD)[cc] + (uint64_t)l2_tl(sid, ct, TD)[cc];
                         double va = -QM_INF;
                         int fl = 0;
@@ -1365,15 +1277,15 @@ __global__ __launch_bounds__((NMW == 3 && TILES == 1) ? 256 : 512, 2) void cd_li
                                     va = V.vafter;
                                     if (V.moved) Xg[i * 16 + cc] = xi;
                                 } else {
-                                    const double xi = l2_p1_visit(cp, cq, cr, rel, i, Xg[i * 16 + cc], a.tol, lf_viol_tol, sd, gidx, t, &fl, &va);
+                                    const double xi = p1_class_visit(cp, cq, cr, rel, i, Xg[i * 16 + cc], a.tol, lf_viol_tol, sd, gidx, t, &fl, &va);
                                     if (fl & 1) Xg[i * 16 + cc] = xi;
                                 }
                             }
                         }
-                        const double vmax = l2_wave_max(va);
+                        const double vmax = wave_max(va);
                         const bool anyupd = __builtin_amdgcn_ballot_w64((fl & 1) != 0) != 0ull;
                         const int st = (fl >> 8) ? -(fl >> 8) : 0;
-                        if (lane == 0) { atomicMax(&l2_tl(p1key, ct, TD)[cc], l2_key(vmax)); if (anyupd) l2_tl(p1upd, ct, TD)[cc] = 1; }
+                        if (lane == 0) { atomicMax(&l2_tl(p1key, ct, TD)[cc], ordered_key(vmax)); if (anyupd) l2_tl(p1upd, ct, TD)[cc] = 1; }
                         if (st) l2_tl(p1st, ct, TD)[cc] = st;
                     }
                     __syncthreads();
@@ -1381,18 +1293,18 @@ __global__ __launch_bounds__((NMW == 3 && TILES == 1) ? 256 : 512, 2) void cd_li
                         const int st = tid >> 4, sc = tid & 15;
                         l2_tl(p1sw, st, TD)[sc]++;
                         // done when feasible enough (qcqp.py:111); a sweep without any update is a fixed point of the map
-                        if (l2_unkey(l2_tl(p1key, st, TD)[sc]) < lf_viol_tol || !l2_tl(p1upd, st, TD)[sc]) l2_tl(p1fin, st, TD)[sc] = 1;
+                        if (ordered_unkey(l2_tl(p1key, st, TD)[sc]) < lf_viol_tol || !l2_tl(p1upd, st, TD)[sc]) l2_tl(p1fin, st, TD)[sc] = 1;
                     }
                     __syncthreads();
                 }
             }
             if (lf->prof && tid == 0) atomicAdd((unsigned long long *)lf->prof + 17, (unsigned long long)((long long)__builtin_amdgcn_s_memtime() - pt0));
-            if (tid < NS) l2_tl(p1key, tid >> 4, TD)[tid & 15] = l2_key(-QM_INF);
+            if (tid < NS) l2_tl(p1key, tid >> 4, TD)[tid & 15] = ordered_key(-QM_INF);
             __syncthreads();
             for (int c = 0; c < NS; c++) {
                 const int ct = c >> 4, cc = c & 15;
                 if (lf_pre || !l2_tl(snew, ct, TD)[cc]) continue;
-                LG const double *Xg = Xg0 + (int64_t)ct * n16 * 16;
+                GLB const double *Xg = Xg0 + (int64_t)ct * n16 * 16;
                 double v = -QM_INF;
                 for (int64_t i = tid; i < P.n; i += NT) {
                     const double x = Xg[i * 16 + cc];
@@ -1408,8 +1320,8 @@ __global__ __launch_bounds__((NMW == 3 && TILES == 1) ? 256 : 512, 2) void cd_li
                         v = w > v ? w : v;
                     }
                 }
-                v = l2_wave_max(v);
-                if (lane == 0) atomicMax(&l2_tl(p1key, ct, TD)[cc], l2_key(v));
+                v = wave_max(v);
+                if (lane == 0) atomicMax(&l2_tl(p1key, ct, TD)[cc], ordered_key(v));
             }
             __syncthreads();
             if (tid < NS && l2_tl(snew, tid >> 4, TD)[tid & 15]) {
@@ -1417,12 +1329,12 @@ __global__ __launch_bounds__((NMW == 3 && TILES == 1) ? 256 : 512, 2) void cd_li
                 double mvx;
                 if (lf_pre) {
                     const int id = l2_tl(sid, st, TD)[sc];
-                    mvx = l2_g(lf->preslack)[id];
-                    l2_tl(p1sw, st, TD)[sc] = (int)l2_g(lf->sweeps1)[id];
-                    l2_tl(p1st, st, TD)[sc] = l2_g(lf->status1)[id];
-                    l2_tl(gatep, st, TD)[sc] = l2_g(lf->ran2)[id];
+                    mvx = glb(lf->preslack)[id];
+                    l2_tl(p1sw, st, TD)[sc] = (int)glb(lf->sweeps1)[id];
+                    l2_tl(p1st, st, TD)[sc] = glb(lf->status1)[id];
+                    l2_tl(gatep, st, TD)[sc] = glb(lf->ran2)[id];
                 } else {
-                    mvx = l2_unkey(l2_tl(p1key, st, TD)[sc]);
+                    mvx = ordered_unkey(l2_tl(p1key, st, TD)[sc]);
                     l2_tl(gatep, st, TD)[sc] = (mvx < lf_viol_tol && l2_tl(p1st, st, TD)[sc] == 0) ? 1 : 0;
                 }
                 l2_tl(slk, st, TD)[sc] = mvx;
@@ -1488,7 +1400,7 @@ __global__ __launch_bounds__((NMW == 3 && TILES == 1) ? 256 : 512, 2) void cd_li
             }
         }
         __syncthreads();
-        if (tid == 0 && l2_g(lifep)->prof) *(long long *)(ctl + 6) = (long long)__builtin_amdgcn_s_memtime();
+        if (tid == 0 && glb(lifep)->prof) *(long long *)(ctl + 6) = (long long)__builtin_amdgcn_s_memtime();
 
         // ================================================================ episode: the roles
         if (role > 0) {
@@ -1498,14 +1410,14 @@ __global__ __launch_bounds__((NMW == 3 && TILES == 1) ? 256 : 512, 2) void cd_li
 
         __syncthreads();
         if (sy[L2_ABORT] || (TILES > 1 && l2_tl((int *)sy, 1, TD)[L2_ABORT])) {       // a wait gave up: unwind (the host reports it)
-            if (tid == 0) __hip_atomic_store(l2_g(a0.abort), 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (tid == 0) __hip_atomic_store(glb(a0.abort), 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             break;
         }
-        if (tid == 0 && l2_g(lifep)->prof)
+        if (tid == 0 && glb(lifep)->prof)
         {
             const long long now_ = (long long)__builtin_amdgcn_s_memtime();
-            atomicAdd((unsigned long long *)l2_g(lifep)->prof + 5, (unsigned long long)(now_ - *(long long *)(ctl + 6)));
-            atomicAdd((unsigned long long *)l2_g(lifep)->prof + 20, (unsigned long long)(now_ - *(long long *)(ctl + 8)));    // from the chain's last interval to the barrier
+            atomicAdd((unsigned long long *)glb(lifep)->prof + 5, (unsigned long long)(now_ - *(long long *)(ctl + 6)));
+            atomicAdd((unsigned long long *)glb(lifep)->prof + 20, (unsigned long long)(now_ - *(long long *)(ctl + 8)));    // from the chain's last interval to the barrier
         }
         // ================================================================ write out the slots that finished
         {
@@ -1518,7 +1430,7 @@ __global__ __launch_bounds__((NMW == 3 && TILES == 1) ? 256 : 512, 2) void cd_li
             // loads in flight per thread (the tile lives in L2: a dependent load-store pair per row costs a round trip each, and with
             // one thread column per slot 14 of 16 threads had nothing to do); the max violation per column through LDS keys
             if (tid == 0) { int cnt = 0; for (int k = 0; k < NS; k++) if (l2_tl(sfin, k >> 4, TD)[k & 15]) p1cols[cnt++] = k; ctl[4] = cnt; }
-            if (tid < NS) l2_tl(p1key, tid >> 4, TD)[tid & 15] = l2_key(-QM_INF);
+            if (tid < NS) l2_tl(p1key, tid >> 4, TD)[tid & 15] = ordered_key(-QM_INF);
             __syncthreads();
             const int nfin = ctl[4];
             const int64_t items = (int64_t)nfin * n16;
@@ -1537,7 +1449,7 @@ __global__ __launch_bounds__((NMW == 3 && TILES == 1) ? 256 : 512, 2) void cd_li
                     if (w < items) {
                         const int col = p1cols[w / n16], id = l2_tl(sid, col >> 4, TD)[col & 15];
                         const int64_t i = w % n16;
-                        l2_g(a0.b.X)[((int64_t)(id >> 4) * n16 + i) * 16 + (id & 15)] = xv8[u];
+                        glb(a0.b.X)[((int64_t)(id >> 4) * n16 + i) * 16 + (id & 15)] = xv8[u];
                         if (i < P.n) {
                             if (MULTI) {
                                 double vv = -QM_INF;
@@ -1545,11 +1457,11 @@ __global__ __launch_bounds__((NMW == 3 && TILES == 1) ? 256 : 512, 2) void cd_li
                                     const double w_ = viol_of((P.cp[e] * xv8[u] + P.cq[e]) * xv8[u] + P.cr[e], P.crel[e]);
                                     vv = w_ > vv ? w_ : vv;
                                 }
-                                atomicMax(&l2_tl(p1key, col >> 4, TD)[col & 15], l2_key(vv));
+                                atomicMax(&l2_tl(p1key, col >> 4, TD)[col & 15], ordered_key(vv));
                             } else {
                                 const double f = (cp * xv8[u] + cq) * xv8[u] + cr;
                                 const double vv = (rel == RELOP_EQ) ? fabs(f) : (f > 0.0 ? f : 0.0);
-                                atomicMax(&l2_tl(p1key, col >> 4, TD)[col & 15], l2_key(vv));
+                                atomicMax(&l2_tl(p1key, col >> 4, TD)[col & 15], ordered_key(vv));
                             }
                         }
                     }
@@ -1558,15 +1470,15 @@ __global__ __launch_bounds__((NMW == 3 && TILES == 1) ? 256 : 512, 2) void cd_li
             __syncthreads();
             if (tid < NS && l2_tl(sfin, tid >> 4, TD)[tid & 15]) {
                 const int st = tid >> 4, sc = tid & 15;
-                const double mx = l2_unkey(l2_tl(p1key, st, TD)[sc]);
+                const double mx = ordered_unkey(l2_tl(p1key, st, TD)[sc]);
                 const int id = l2_tl(sid, st, TD)[sc];
-                l2_g(a0.b.visits)[id] = l2_tl(ovis, st, TD)[sc]; l2_g(a0.b.accepted)[id] = l2_tl(oacc, st, TD)[sc]; l2_g(a0.b.sweeps)[id] = l2_tl(oswp, st, TD)[sc];
-                l2_g(a0.b.status)[id] = l2_tl(ost, st, TD)[sc];
-                if (a0.b.f0out) l2_g(a0.b.f0out)[id] = l2_tl(of0, st, TD)[sc];
-                if (a0.b.mvout) l2_g(a0.b.mvout)[id] = mx;
-                LG const CdLife *lf = l2_g(lifep);
-                l2_g(lf->sweeps1)[id] = l2_tl(p1sw, st, TD)[sc]; l2_g(lf->status1)[id] = l2_tl(p1st, st, TD)[sc];
-                l2_g(lf->ran2)[id] = (uint8_t)l2_tl(gatep, st, TD)[sc];
+                glb(a0.b.visits)[id] = l2_tl(ovis, st, TD)[sc]; glb(a0.b.accepted)[id] = l2_tl(oacc, st, TD)[sc]; glb(a0.b.sweeps)[id] = l2_tl(oswp, st, TD)[sc];
+                glb(a0.b.status)[id] = l2_tl(ost, st, TD)[sc];
+                if (a0.b.f0out) glb(a0.b.f0out)[id] = l2_tl(of0, st, TD)[sc];
+                if (a0.b.mvout) glb(a0.b.mvout)[id] = mx;
+                GLB const CdLife *lf = glb(lifep);
+                glb(lf->sweeps1)[id] = l2_tl(p1sw, st, TD)[sc]; glb(lf->status1)[id] = l2_tl(p1st, st, TD)[sc];
+                glb(lf->ran2)[id] = (uint8_t)l2_tl(gatep, st, TD)[sc];
                 l2_tl(sid, st, TD)[sc] = -1; l2_tl(sfin, st, TD)[sc] = 0;
             }
             __syncthreads();
@@ -1593,11 +1505,11 @@ __global__ __launch_bounds__(L2P_NT) void cd_life_prep_kernel(DevProblem P, cons
     __shared__ unsigned long long key[16];
     __shared__ int upd[16], st1[16], fin[16], sw[16], nact;
     const int tid = threadIdx.x, s = tid & 15, g = tid >> 4;
-    LG const CdLife *lf = l2_g(life);
+    GLB const CdLife *lf = glb(life);
     const int64_t id = (int64_t)blockIdx.x * 16 + s;
     const bool valid = id < lf->Rtotal;
     const int64_t n = P.n, n16 = P.n16;
-    LG double *Xt = l2_g(X) + (int64_t)blockIdx.x * n16 * 16 + s;        // column s of the tile: coordinate j at Xt[16 j]
+    GLB double *Xt = glb(X) + (int64_t)blockIdx.x * n16 * 16 + s;        // column s of the tile: coordinate j at Xt[16 j]
     const double viol_tol = lf->viol_tol;
     uint64_t sd = 0, gidx = 0;
     if (valid) {
@@ -1608,7 +1520,7 @@ __global__ __launch_bounds__(L2P_NT) void cd_life_prep_kernel(DevProblem P, cons
     if (lf->generate && valid) {
         for (int64_t j = 2 * g; j < n16; j += 32) {
             double xo = 0.0;
-            const double xe = (j < n) ? l2_keyed_normal_pair(sd, gidx, (uint64_t)j, &xo) : 0.0;
+            const double xe = (j < n) ? keyed_normal_pair(sd, gidx, (uint64_t)j, &xo) : 0.0;
             Xt[16 * j] = xe;
             Xt[16 * (j + 1)] = (j + 1 < n) ? xo : 0.0;
         }
@@ -1620,7 +1532,7 @@ __global__ __launch_bounds__(L2P_NT) void cd_life_prep_kernel(DevProblem P, cons
     if (lf->phase1) {
         const bool band2 = cq == 0.0 && rel == RELOP_EQ && cp > 1e-4 && cr < -1e-3;      // the build's choice of visit
         for (int64_t t = 0; t < num_iters; t++) {
-            if (tid < 16) { key[tid] = l2_key(-QM_INF); upd[tid] = 0; }
+            if (tid < 16) { key[tid] = ordered_key(-QM_INF); upd[tid] = 0; }
             __syncthreads();
             if (tid == 0) { int c = 0; for (int k = 0; k < 16; k++) c += fin[k] ? 0 : 1; nact = c; }
             __syncthreads();
@@ -1646,7 +1558,7 @@ __global__ __launch_bounds__(L2P_NT) void cd_life_prep_kernel(DevProblem P, cons
                         for (int64_t i = j; i < j + 2 && i < n; i++) {
                             int fl = 0;
                             double v = 0.0;
-                            const double xi = l2_p1_visit(cp, cq, cr, rel, i, Xt[16 * i], tol, viol_tol, sd, gidx, t, &fl, &v);
+                            const double xi = p1_class_visit(cp, cq, cr, rel, i, Xt[16 * i], tol, viol_tol, sd, gidx, t, &fl, &v);
                             if (fl & 1) { Xt[16 * i] = xi; moved = 1; }
                             if (fl >> 8) stv = -(fl >> 8);
                             va = v > va ? v : va;
@@ -1661,19 +1573,19 @@ __global__ __launch_bounds__(L2P_NT) void cd_life_prep_kernel(DevProblem P, cons
                 va = w > va ? w : va;
                 moved |= __shfl_xor(moved, o, 64);
             }
-            if ((tid & 63) < 16 && !fin[s]) { atomicMax(&key[s], l2_key(va)); if (moved) upd[s] = 1; }
+            if ((tid & 63) < 16 && !fin[s]) { atomicMax(&key[s], ordered_key(va)); if (moved) upd[s] = 1; }
             if (stv) st1[s] = stv;
             __syncthreads();
             if (tid < 16 && !fin[tid]) {
                 sw[tid]++;
                 // done when feasible enough (qcqp.py:111); a sweep without any update is a fixed point of the map
-                if (l2_unkey(key[tid]) < viol_tol || !upd[tid]) fin[tid] = 1;
+                if (ordered_unkey(key[tid]) < viol_tol || !upd[tid]) fin[tid] = 1;
             }
         }
     }
     // max violation of the point = the slack of phase 2 (qcqp.py:157), and the gate (qcqp.py:189)
     __syncthreads();
-    if (tid < 16) key[tid] = l2_key(-QM_INF);
+    if (tid < 16) key[tid] = ordered_key(-QM_INF);
     __syncthreads();
     double v = -QM_INF;
     if (valid)
@@ -1686,14 +1598,14 @@ __global__ __launch_bounds__(L2P_NT) void cd_life_prep_kernel(DevProblem P, cons
             }
 #pragma unroll
     for (int o = 16; o <= 32; o <<= 1) { const double w = __shfl_xor(v, o, 64); v = w > v ? w : v; }
-    if ((tid & 63) < 16 && valid) atomicMax(&key[s], l2_key(v));
+    if ((tid & 63) < 16 && valid) atomicMax(&key[s], ordered_key(v));
     __syncthreads();
     if (tid < 16 && valid) {
-        const double mvx = l2_unkey(key[tid]);
-        l2_g(const_cast<double *>(lf->preslack))[id] = mvx;
-        l2_g(lf->sweeps1)[id] = sw[tid];
-        l2_g(lf->status1)[id] = st1[tid];
-        l2_g(lf->ran2)[id] = (mvx < viol_tol && st1[tid] == 0) ? 1 : 0;
+        const double mvx = ordered_unkey(key[tid]);
+        glb(const_cast<double *>(lf->preslack))[id] = mvx;
+        glb(lf->sweeps1)[id] = sw[tid];
+        glb(lf->status1)[id] = st1[tid];
+        glb(lf->ran2)[id] = (mvx < viol_tol && st1[tid] == 0) ? 1 : 0;
     }
 }
 

@@ -1,5 +1,5 @@
 // One coordinate visit of coordinate-descent PHASE 1 (qcqp.py:113-136) for separable constraints -- shared by
-// cd_phase1_sep_kernel (kernels.hip: one launch per population) and by the lifecycle mode of the slot-queue kernel
+// cd_phase1_sep_kernel (kernels_impl.h: one launch per population) and by the lifecycle mode of the slot-queue kernel
 // (cd_queue.hip: a restart's suggest + phase 1 + gate + phase 2 inside one persistent launch), so that both make the same
 // moves bit for bit.
 //
@@ -310,6 +310,24 @@ __device__ inline void p1_band_visit_n(double p, double q, double r, const int64
         if (on[k] && new_viol < viol[k]) { xi[k] = new_xi; V[k].moved = true; }
         V[k].vafter = fabs((p * xi[k] + q) * xi[k] + r);
     }
+}
+
+// one visit of coordinate i (value x) of a problem whose coordinates all carry the one constraint (p, q, r, relop);
+// returns the new value, *flags: bit 0 moved, bits 8.. = -status; *vafter: the constraint's violation afterwards
+__device__ __attribute__((always_inline)) inline double p1_class_visit(double p, double q, double r, int relop, int64_t i, double x, double tol,
+                                                                        double viol_tol, uint64_t seed, uint64_t restart, int64_t t, int *flags,
+                                                                        double *vafter) {
+    P1Visit V;
+    if (q == 0.0 && relop == RELOP_EQ && p > 1e-4) {
+        p1_band_visit(p, q, r, i, x, tol, viol_tol, seed, restart, t, V);      // the class of the headline family, resolved by hand
+    } else {
+        const double cp[1] = {p}, cq[1] = {q}, cr[1] = {r};
+        const int crel[1] = {relop};
+        p1_sep_visit_core<1>(1, cp, cq, cr, crel, i, x, tol, viol_tol, seed, restart, t, V);
+    }
+    *flags = (V.moved ? 1 : 0) | ((-V.status) << 8);
+    *vafter = V.vafter;
+    return x;
 }
 
 template <int MAXC>

@@ -35,26 +35,10 @@
 // literally (onevar_minimise in onevar.h).
 #pragma once
 #include <stdint.h>
-#include "cd_phase2.h"
+#include "cd_chain.h"
+#include "mfma_block.h"
 
 namespace qcqpmi {
-
-typedef double v2d_ __attribute__((ext_vector_type(2)));
-
-// acc += Apack[b][kk] * X rows for kk in [kk0, kk1) streaming the A fragments from L2
-// (fallback for k-steps that do not fit the register prefetch, n > 16 * 3 * PFU).
-template <typename XPtr>
-__device__ inline v4d_ mfma_range(const double *__restrict__ Ab, XPtr Xs, int kk0, int kk1, int lane,
-                                  v4d_ acc) {
-    const double *ap = Ab + (int64_t)kk0 * 64 + lane;
-    XPtr xp = Xs + kk0 * 64 + (lane >> 4) * 16 + (lane & 15);
-    for (int k = kk0; k < kk1; k++) {
-        acc = __builtin_amdgcn_mfma_f64_16x16x4f64(ap[0], xp[0], acc, 0, 0, 0);
-        ap += 64;
-        xp += 64;
-    }
-    return acc;
-}
 
 constexpr int RS_NMW = 6;    // mfma waves: 1,2,3,5,6,7 (two per SIMD; wave 4 shares the chain's SIMD and idles)
 constexpr int RS_PFU = 11;   // units (blocks of 16 coordinates) whose A fragments live in registers

@@ -19,95 +19,48 @@
 
 #include "onevar.h"
 #include "cd_phase1_sep.h"
-
-namespace qcqpmi {
-// (cd_phase2.h, which the role helpers come with, expects the MFMA building block of kernels.hip to be declared)
-typedef double v4d __attribute__((ext_vector_type(4)));
-template <typename XPtr>
-__device__ inline v4d block_rows_times_X(const double *__restrict__ Ab, XPtr Xs, int kk0, int kk1, int lane, v4d acc) {
-    const int xoff = (lane >> 4) * 16 + (lane & 15);
-    for (int kk = kk0; kk < kk1; kk++) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(Ab[(int64_t)kk * 64 + lane], Xs[kk * 64 + xoff], acc, 0, 0, 0);
-    return acc;
-}
-}  // namespace qcqpmi
-
-#include "cd_phase2_q.h"
+#include "cd_chain.h"
+#include "cd_roles.h"
 
 namespace qcqpmi {
 namespace {
 
-__device__ inline int qs_load_int(const int *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ inline double qs_load_d(const double *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-// pointers typed as global memory: a generic pointer makes the compiler emit FLAT loads / stores / atomics, which count against
-// the LDS counter as well -- and the roles of this kernel synchronise through LDS words (measured in round 3: 30 % slower)
-#define QG __attribute__((address_space(1)))
 struct CdBatchG {
-    QG double *X;
-    QG const double *f0cur, *slack;
-    QG const uint8_t *flag;
-    QG int64_t *visits, *accepted, *sweeps;
-    QG int *status;
-    QG double *f0out, *mvout;
+    GLB double *X;
+    GLB const double *f0cur, *slack;
+    GLB const uint8_t *flag;
+    GLB int64_t *visits, *accepted, *sweeps;
+    GLB int *status;
+    GLB double *f0out, *mvout;
     int64_t R;
     uint64_t seed, first_index;
-    QG int *next;
+    GLB int *next;
 };
-template <class T>
-__device__ __attribute__((always_inline)) inline QG T *qs_g(T *p) { return (QG T *)p; }
 __device__ __attribute__((always_inline)) inline CdBatchG qs_batch(const CdBatch &t) {
     CdBatchG b;
-    b.X = qs_g(t.X); b.f0cur = qs_g(t.f0cur); b.slack = qs_g(t.slack); b.flag = qs_g(t.flag);
-    b.visits = qs_g(t.visits); b.accepted = qs_g(t.accepted); b.sweeps = qs_g(t.sweeps); b.status = qs_g(t.status);
-    b.f0out = qs_g(t.f0out); b.mvout = qs_g(t.mvout); b.next = qs_g(t.next);
+    b.X = glb(t.X); b.f0cur = glb(t.f0cur); b.slack = glb(t.slack); b.flag = glb(t.flag);
+    b.visits = glb(t.visits); b.accepted = glb(t.accepted); b.sweeps = glb(t.sweeps); b.status = glb(t.status);
+    b.f0out = glb(t.f0out); b.mvout = glb(t.mvout); b.next = glb(t.next);
     b.R = t.R; b.seed = t.seed; b.first_index = t.first_index;
     return b;
-}
-__device__ inline int qs_load_int(QG const int *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ inline double qs_load_d(QG const double *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ inline int qs_add(QG int *p, int v) { return __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-// order-preserving map double -> u64 and back (LDS integer atomics as max-reductions over the threads)
-__device__ inline unsigned long long qs_key(double x) {
-    const unsigned long long b = (unsigned long long)__double_as_longlong(x);
-    return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
-}
-__device__ inline double qs_unkey(unsigned long long k) {
-    const unsigned long long b = (k >> 63) ? (k & 0x7fffffffffffffffull) : ~k;
-    return __longlong_as_double((long long)b);
-}
-__device__ inline double qs_wave_max(double v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) { const double w = __shfl_xor(v, o, 64); v = w > v ? w : v; }
-    return v;
 }
 
 // Lifecycle mode: the heavy scalar code of a restart's start -- Box-Muller normals, the phase-1 visit (bisection, Philox,
 // square roots) -- as REAL FUNCTION CALLS.  Inlined into the kernel they cost it 150 VGPR spills in the multiplying waves'
 // product loop (the kernel sits exactly at the 256-register limit there); called, they have register allocations of their own.
-__device__ __attribute__((noinline)) double qs_keyed_normal(uint64_t seed, uint64_t restart, uint64_t elem) {
-    return keyed_normal(seed, restart, elem);
-}
-// the normals of the element pair (elem, elem + 1), elem even: keyed_normal's own expressions (philox.h) -- the two share the
-// counter block elem >> 1, the radius and the angle; the even element takes the cosine, the odd one the sine -- evaluated once
+// the normals of the element pair (elem, elem + 1), elem even (philox.h)
 __device__ __attribute__((noinline)) double qs_keyed_normal_pair(uint64_t seed, uint64_t restart, uint64_t elem, double *odd) {
-    const U4 o = philox4x32_10((uint32_t)(elem >> 1), (uint32_t)(elem >> 33), 0xA5A50000u, (uint32_t)restart, (uint32_t)seed,
-                               (uint32_t)(seed >> 32) ^ (uint32_t)(restart >> 32));
-    const double u1 = (((double)(o.x >> 5) * 67108864.0 + (double)(o.y >> 6)) + 0.5) / 9007199254740992.0;
-    const double u2 = u53(o.z, o.w);
-    const double rad = sqrt(-2.0 * log(u1));
-    const double ang = 6.283185307179586476925286766559 * u2;
-    *odd = rad * sin(ang);
-    return rad * cos(ang);
+    return keyed_normal_pair(seed, restart, elem, odd);
 }
-// one phase-1 visit of coordinate i (value x) of a problem whose coordinates all carry the one constraint (p, q, r, relop);
-// returns the new value, *flags: bit 0 moved, bits 8.. = -status; *vafter: the constraint's violation afterwards
+// one phase-1 visit of coordinate i of the single class: the body of p1_class_visit (cd_phase1_sep.h), statement for statement.
+// It is restated, not called: through the call the compiler allocates this function's registers differently (same instructions,
+// other register numbers), and no kernel's code may change without being measured again.  Keep the two in step.
 __device__ __attribute__((noinline)) double qs_p1_visit(double p, double q, double r, int relop, int64_t i, double x, double tol,
                                                         double viol_tol, uint64_t seed, uint64_t restart, int64_t t, int *flags,
                                                         double *vafter) {
     P1Visit V;
     if (q == 0.0 && relop == RELOP_EQ && p > 1e-4) {
-        p1_band_visit(p, q, r, i, x, tol, viol_tol, seed, restart, t, V);      // the class of the headline family, resolved by hand
+        p1_band_visit(p, q, r, i, x, tol, viol_tol, seed, restart, t, V);
     } else {
         const double cp[1] = {p}, cq[1] = {q}, cr[1] = {r};
         const int crel[1] = {relop};
@@ -216,8 +169,8 @@ __global__ __launch_bounds__(512) void cd_phase2_qs_kernel(CdQueueArgs a0) {
             int id = sid[tid], nw = 0;
             if (id < 0 && LIFE) {
                 // lifecycle mode: the queue is a counter over all restarts of the run; the column is built below
-                QG const CdLife *lf = qs_g(lifep);
-                const int idx = qs_add(qs_g(a0.b.next), 1);
+                GLB const CdLife *lf = glb(lifep);
+                const int idx = glb_add(glb(a0.b.next), 1);
                 if (idx < (int)lf->Rtotal) {
                     id = idx; nw = 1;
                     const uint64_t pop = (uint64_t)idx / (uint64_t)lf->Rpop, rho = (uint64_t)idx % (uint64_t)lf->Rpop;
@@ -227,7 +180,7 @@ __global__ __launch_bounds__(512) void cd_phase2_qs_kernel(CdQueueArgs a0) {
             } else if (id < 0) {
                 const CdBatchG B = qs_batch(a0.b);
                 for (;;) {
-                    const int idx = qs_add(B.next, 1);      // (runs past R by at most 16 per workgroup and episode: harmless)
+                    const int idx = glb_add(B.next, 1);      // (runs past R by at most 16 per workgroup and episode: harmless)
                     if (idx >= (int)B.R) break;
                     if (B.flag[idx]) {                      // passed the gate of improve_coord_descent (qcqp.py:189)
                         id = idx; nw = 1;
@@ -261,7 +214,7 @@ __global__ __launch_bounds__(512) void cd_phase2_qs_kernel(CdQueueArgs a0) {
             // ---- lifecycle mode: build the columns of the restarts just taken -- suggest(RANDOM) (qcqp.py:381-382: keyed
             // normals, the stream of randn_tiles_kernel), phase 1 (qcqp.py:101-149 through p1_sep_visit: the moves of
             // cd_phase1_sep_kernel bit for bit), the max violation = slack of phase 2 (qcqp.py:157) and the gate (qcqp.py:189)
-            QG const CdLife *lf = qs_g(lifep);
+            GLB const CdLife *lf = glb(lifep);
             const long long pt0 = lf->prof ? (long long)__builtin_amdgcn_s_memtime() : 0;
             const int lf_generate = lf->generate, lf_phase1 = lf->phase1;
             const double lf_viol_tol = lf->viol_tol;
@@ -282,7 +235,7 @@ __global__ __launch_bounds__(512) void cd_phase2_qs_kernel(CdQueueArgs a0) {
                         Xs[(j + 1) * 16 + c] = xo;
                     }
                 } else {
-                    QG const double *src = qs_g(a0.b.X) + ((int64_t)(sid[c] >> 4) * n16) * 16 + (sid[c] & 15);
+                    GLB const double *src = glb(a0.b.X) + ((int64_t)(sid[c] >> 4) * n16) * 16 + (sid[c] & 15);
                     for (int64_t j = tid; j < n16; j += 512) Xs[j * 16 + c] = src[j * 16];
                 }
             }
@@ -291,7 +244,7 @@ __global__ __launch_bounds__(512) void cd_phase2_qs_kernel(CdQueueArgs a0) {
             if (lf_phase1) {
                 for (int64_t t = 0; t < a.num_iters; t++) {
                     if (tid == 0) { int cnt = 0; for (int k = 0; k < 16; k++) cnt += (snew[k] && !p1fin[k]) ? 1 : 0; ctl[4] = cnt; }
-                    if (tid < 16) { p1key[tid] = qs_key(-QM_INF); p1upd[tid] = 0; }
+                    if (tid < 16) { p1key[tid] = ordered_key(-QM_INF); p1upd[tid] = 0; }
                     __syncthreads();
                     if (ctl[4] == 0) break;
                     for (int c = 0; c < 16; c++) {
@@ -321,8 +274,8 @@ __global__ __launch_bounds__(512) void cd_phase2_qs_kernel(CdQueueArgs a0) {
                             if (fl & 1) { Xs[i * 16 + c] = xi; upd = 1; }
                             vmax = va > vmax ? va : vmax;
                         }
-                        vmax = qs_wave_max(vmax);
-                        if (lane == 0) atomicMax(&p1key[c], qs_key(vmax));
+                        vmax = wave_max(vmax);
+                        if (lane == 0) atomicMax(&p1key[c], ordered_key(vmax));
                         if (upd) p1upd[c] = 1;
                         if (st) p1st[c] = st;
                     }
@@ -330,12 +283,12 @@ __global__ __launch_bounds__(512) void cd_phase2_qs_kernel(CdQueueArgs a0) {
                     if (tid < 16 && snew[tid] && !p1fin[tid]) {
                         p1sw[tid]++;
                         // done when feasible enough (qcqp.py:111); a sweep without any update is a fixed point of the map
-                        if (qs_unkey(p1key[tid]) < lf_viol_tol || !p1upd[tid]) p1fin[tid] = 1;
+                        if (ordered_unkey(p1key[tid]) < lf_viol_tol || !p1upd[tid]) p1fin[tid] = 1;
                     }
                     __syncthreads();
                 }
             }
-            if (tid < 16) p1key[tid] = qs_key(-QM_INF);
+            if (tid < 16) p1key[tid] = ordered_key(-QM_INF);
             __syncthreads();
             for (int c = 0; c < 16; c++) {
                 if (!snew[c]) continue;
@@ -346,12 +299,12 @@ __global__ __launch_bounds__(512) void cd_phase2_qs_kernel(CdQueueArgs a0) {
                     const double w = (rel == RELOP_EQ) ? fabs(f) : (f > 0.0 ? f : 0.0);
                     v = w > v ? w : v;
                 }
-                v = qs_wave_max(v);
-                if (lane == 0) atomicMax(&p1key[c], qs_key(v));
+                v = wave_max(v);
+                if (lane == 0) atomicMax(&p1key[c], ordered_key(v));
             }
             __syncthreads();
             if (tid < 16 && snew[tid]) {
-                const double mvx = qs_unkey(p1key[tid]);
+                const double mvx = ordered_unkey(p1key[tid]);
                 slk[tid] = mvx;
                 gatep[tid] = (mvx < lf_viol_tol && p1st[tid] == 0) ? 1 : 0;
                 FeasSet<MAXC> C;
@@ -373,7 +326,7 @@ __global__ __launch_bounds__(512) void cd_phase2_qs_kernel(CdQueueArgs a0) {
             const int id = sid[col];
             if (snew[col]) {
                 // eight loads in flight per thread
-                QG const double *src = qs_g(a0.b.X) + ((int64_t)(id >> 4) * n16) * 16 + (id & 15);
+                GLB const double *src = glb(a0.b.X) + ((int64_t)(id >> 4) * n16) * 16 + (id & 15);
                 for (int64_t j0 = tid >> 4; j0 < n16; j0 += 32 * 8) {
                     double pv[8];
 #pragma unroll
@@ -408,7 +361,7 @@ __global__ __launch_bounds__(512) void cd_phase2_qs_kernel(CdQueueArgs a0) {
             }
         }
         __syncthreads();
-        if (LIFE && tid == 0 && qs_g(lifep)->prof) *(long long *)(ctl + 6) = (long long)__builtin_amdgcn_s_memtime();     // (stashed in LDS: not a register of the chain wave)
+        if (LIFE && tid == 0 && glb(lifep)->prof) *(long long *)(ctl + 6) = (long long)__builtin_amdgcn_s_memtime();     // (stashed in LDS: not a register of the chain wave)
 
         // ================================================================ episode: the roles of cd_phase2_q_kernel
         if (wave == 4) {
@@ -807,7 +760,7 @@ __global__ __launch_bounds__(512) void cd_phase2_qs_kernel(CdQueueArgs a0) {
                     const unsigned long long finm = __builtin_amdgcn_ballot_w64(fin);
                     if (finm == ~0ull) break;
                     if (finm != 0ull) {
-                        const bool more = qs_load_int(qs_g(a0.b.next)) < (LIFE ? (int)qs_g(lifep)->Rtotal : (int)a0.b.R);
+                        const bool more = glb_load_int(glb(a0.b.next)) < (LIFE ? (int)glb(lifep)->Rtotal : (int)a0.b.R);
                         if (more) break;
                     }
                 }
@@ -852,8 +805,8 @@ __global__ __launch_bounds__(512) void cd_phase2_qs_kernel(CdQueueArgs a0) {
         }
 
         __syncthreads();
-        if (LIFE && tid == 0 && qs_g(lifep)->prof)
-            atomicAdd((unsigned long long *)qs_g(lifep)->prof + 5, (unsigned long long)((long long)__builtin_amdgcn_s_memtime() - *(long long *)(ctl + 6)));
+        if (LIFE && tid == 0 && glb(lifep)->prof)
+            atomicAdd((unsigned long long *)glb(lifep)->prof + 5, (unsigned long long)((long long)__builtin_amdgcn_s_memtime() - *(long long *)(ctl + 6)));
         // ================================================================ write out the slots that finished
         {
             // max violation of the final points, same expression as eval_kernel: (p x + q) x + r of the one constraint
@@ -864,7 +817,7 @@ __global__ __launch_bounds__(512) void cd_phase2_qs_kernel(CdQueueArgs a0) {
             const int col = tid & 15, slot = tid >> 4;
             double v = -QM_INF;
             if (sfin[col]) {
-                QG double *dst = qs_g(a0.b.X) + ((int64_t)(sid[col] >> 4) * n16) * 16 + (sid[col] & 15);
+                GLB double *dst = glb(a0.b.X) + ((int64_t)(sid[col] >> 4) * n16) * 16 + (sid[col] & 15);
                 for (int64_t i = slot; i < n16; i += 32) {
                     const double x = Xs[i * 16 + col];
                     dst[i * 16] = x;
@@ -888,9 +841,9 @@ __global__ __launch_bounds__(512) void cd_phase2_qs_kernel(CdQueueArgs a0) {
                     if (B.f0out) B.f0out[id] = of0[tid];
                     if (B.mvout) B.mvout[id] = m;
                     if (LIFE) {
-                        QG const CdLife *lf = qs_g(lifep);
-                        qs_g(lf->sweeps1)[id] = p1sw[tid]; qs_g(lf->status1)[id] = p1st[tid];
-                        qs_g(lf->ran2)[id] = (uint8_t)gatep[tid];
+                        GLB const CdLife *lf = glb(lifep);
+                        glb(lf->sweeps1)[id] = p1sw[tid]; glb(lf->status1)[id] = p1st[tid];
+                        glb(lf->ran2)[id] = (uint8_t)gatep[tid];
                     }
                 }
                 sid[tid] = -1; sfin[tid] = 0;
@@ -898,8 +851,8 @@ __global__ __launch_bounds__(512) void cd_phase2_qs_kernel(CdQueueArgs a0) {
             __syncthreads();
         }
     }
-    if (LIFE && tid0 == 0 && qs_g(a0.life)->prof)
-        atomicAdd((unsigned long long *)qs_g(a0.life)->prof + 1, (unsigned long long)((long long)__builtin_amdgcn_s_memtime() - life_t0));
+    if (LIFE && tid0 == 0 && glb(a0.life)->prof)
+        atomicAdd((unsigned long long *)glb(a0.life)->prof + 1, (unsigned long long)((long long)__builtin_amdgcn_s_memtime() - life_t0));
 }
 
 }  // namespace

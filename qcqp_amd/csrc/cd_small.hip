@@ -8,12 +8,12 @@
 //   suggest(RANDOM)   lane j draws the keyed normal (seed_b, first_index + r, j) of qcqpmi_pop_randn;
 //   phase 1           every lane visits its own coordinate through p1_sep_visit (cd_phase1_sep.h) -- a sweep is element-wise for
 //                     separable constraints --, the sweep's max violation and "any update" are wave reductions; the loop and
-//                     its two exits are those of cd_phase1_sep_kernel (kernels.hip);
+//                     its two exits are those of cd_phase1_sep_kernel (kernels_impl.h);
 //   gate              max violation of the point (a wave maximum of the lanes' own constraints) < viol_tol, qcqp.py:189;
 //   phase 2           the lanes hold x, the OFF-DIAGONAL row sums h_j = sum_{k != j} P0[j][k] x_k and the feasible set of their
-//                     coordinate at the slack the phase fixes (compute_set, cd_phase2.h).  A visit of coordinate i broadcasts lane
+//                     coordinate at the slack the phase fixes (compute_set, cd_chain.h).  A visit of coordinate i broadcasts lane
 //                     i's values (v_readlane), every lane makes the scalar decision in the reference's arithmetic
-//                     (onevar_minimise, onevar.h; chain_commit, cd_phase2.h) and an accepted move is a rank-one update along
+//                     (onevar_minimise, onevar.h; chain_commit, cd_chain.h) and an accepted move is a rank-one update along
 //                     column i: h_j += P0[i][j] delta.  P0 is symmetric, so column i is read as ROW i of the LDS image -- lane j
 //                     reads word i n + j: consecutive doubles, no bank conflict (64 dwords per half-wave);
 //   every sweep       h and the objective are recomputed exactly (no drift from one sweep to the next), each sum in ascending
@@ -26,24 +26,11 @@
 
 #include "onevar.h"
 #include "cd_phase1_sep.h"
-
-namespace qcqpmi {
-// cd_phase2.h's matrix-core kernel (a template that is not instantiated here) names this building block of kernels.hip
-typedef double v4d_ __attribute__((ext_vector_type(4)));
-template <typename XPtr>
-__device__ v4d_ block_rows_times_X(const double *__restrict__ Ab, XPtr Xs, int kk0, int kk1, int lane, v4d_ acc);
-}  // namespace qcqpmi
-
-#include "cd_phase2.h"      // compute_set, ChainState, chain_commit, readlane_d
+#include "cd_chain.h"      // compute_set, ChainState, chain_commit, readlane_d
+#include "dev_util.h"
 
 namespace qcqpmi {
 namespace {
-
-__device__ inline double sm_wave_max(double v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) { const double w = __shfl_xor(v, o, 64); v = w > v ? w : v; }
-    return v;
-}
 
 // max violation of coordinate i's own constraints at xi (the expression of eval_kernel; -inf without a constraint)
 __device__ inline double sm_coord_viol(const DevProblem &P, int i, double xi) {
@@ -105,7 +92,7 @@ __device__ inline void sm_restart(const CdSmallArgs &a, const double *Ps, const 
                     vmax = V.vafter;
                 }
             }
-            const double v = sm_wave_max(vmax);
+            const double v = wave_max(vmax);
             const bool u = __builtin_amdgcn_ballot_w64(upd) != 0ull;
             // done when feasible enough (qcqp.py:111); a sweep without an update is a fixed point
             fin = v < a.viol_tol || !u;
@@ -115,7 +102,7 @@ __device__ inline void sm_restart(const CdSmallArgs &a, const double *Ps, const 
     }
 
     // ---- gate (qcqp.py:189); the max violation is also the slack phase 2 fixes (qcqp.py:157)
-    const double slack = sm_wave_max(on ? sm_coord_viol(P, lane, x) : -QM_INF);
+    const double slack = wave_max(on ? sm_coord_viol(P, lane, x) : -QM_INF);
     const bool ran2 = st1 == 0 && slack < a.viol_tol;
 
     // ---- phase 2 (qcqp.py:152-178)
@@ -159,7 +146,7 @@ __device__ inline void sm_restart(const CdSmallArgs &a, const double *Ps, const 
     // ---- results: objective and max violation of the final point; a restart on which the reference raises never wins
     double hh;
     double f = sm_refresh(Ps, qs, r0, n, lane, x, hh);
-    double mv = sm_wave_max(on ? sm_coord_viol(P, lane, x) : -QM_INF);
+    double mv = wave_max(on ? sm_coord_viol(P, lane, x) : -QM_INF);
     if (st1 != 0 || S.status != 0) { f = QM_INF; mv = QM_INF; }
     if (lane == 0) {
         a.sweeps1[o] = sweeps1; a.sweeps2[o] = S.sweeps; a.visits2[o] = S.visits; a.accepted2[o] = S.accepted;

@@ -10,15 +10,16 @@
 //                     (qcqp.py:152-178)
 //   select_best       lexicographic (violation bucket, objective) argmin (utilities.py:135-146)
 //
+// Not a translation unit: capi.hip includes this file (the launches live there).
+//
 // Work decomposition: one workgroup owns one TILE of 16 candidates (see kernels.h); the 16x16
 // fp64 MFMA tile is (16 coordinates of a block) x (16 candidates).
 #include "kernels.h"
 #include "onevar.h"
 #include "cd_phase1_sep.h"
+#include "mfma_block.h"
 
 namespace qcqpmi {
-
-typedef double v4d __attribute__((ext_vector_type(4)));
 
 // ----------------------------------------------------------------------------- layout kernels
 
@@ -73,34 +74,6 @@ __global__ void randn_tiles_kernel(double *__restrict__ Xt, int64_t n, int64_t n
     Xt[idx] = (r < R && j < n) ? keyed_normal(seed, first_index + (uint64_t)r, (uint64_t)j) : 0.0;
 }
 
-// ------------------------------------------------------------------------ MFMA building block
-
-// acc(16 rows of block b) x (16 candidates) += Apack[b][kk0..kk1) * Xt rows.  XT may point to LDS
-// or global memory; rows are 16 doubles.
-template <typename XPtr>
-__device__ inline v4d block_rows_times_X(const double *__restrict__ Ab, XPtr Xs, int kk0, int kk1,
-                                         int lane, v4d acc) {
-    const int xoff = (lane >> 4) * 16 + (lane & 15);
-    int kk = kk0;
-    for (; kk + 8 <= kk1; kk += 8) {
-        double a[8], b[8];
-#pragma unroll
-        for (int u = 0; u < 8; u++) {
-            a[u] = Ab[(int64_t)(kk + u) * 64 + lane];
-            b[u] = Xs[(kk + u) * 64 + xoff];
-        }
-#pragma unroll
-        for (int u = 0; u < 8; u++)
-            acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a[u], b[u], acc, 0, 0, 0);
-    }
-    for (; kk < kk1; kk++) {
-        double a = Ab[(int64_t)kk * 64 + lane];
-        double b = Xs[kk * 64 + xoff];
-        acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, acc, 0, 0, 0);
-    }
-    return acc;
-}
-
 // X = mu 1^T + F * Xi   with F packed like P0 (Apack layout) and Xi tile-major.
 // One workgroup per tile; wave w computes row blocks b = w, w+4, ...
 __global__ __launch_bounds__(256) void affine_tiles_kernel(const double *__restrict__ Fpack,
@@ -112,7 +85,7 @@ __global__ __launch_bounds__(256) void affine_tiles_kernel(const double *__restr
     const double *Xs = Xi + (int64_t)blockIdx.x * n16 * 16;
     double *Xo = Xt + (int64_t)blockIdx.x * n16 * 16;
     for (int64_t b = wave; b < NB; b += 4) {
-        v4d acc = {0.0, 0.0, 0.0, 0.0};
+        v4d_ acc = {0.0, 0.0, 0.0, 0.0};
         acc = block_rows_times_X(Fpack + b * KS * 64, Xs, 0, (int)KS, lane, acc);
 #pragma unroll
         for (int v = 0; v < 4; v++) {
@@ -148,11 +121,11 @@ __global__ __launch_bounds__(256) void eval_kernel(EvalArgs a) {
             for (int p = 0; p < a.nplanes; p++) facc += a.planes[(int64_t)p * a.Rpad + tile * 16 + tid];
     }
     for (int64_t b0 = 4 * wave; b0 < P.NB && !a.planes; b0 += 16) {
-        v4d acc[4];
+        v4d_ acc[4];
         const double *Ab[4];
 #pragma unroll
         for (int u = 0; u < 4; u++) {
-            acc[u] = v4d{0.0, 0.0, 0.0, 0.0};
+            acc[u] = v4d_{0.0, 0.0, 0.0, 0.0};
             const int64_t bb = (b0 + u < P.NB) ? b0 + u : P.NB - 1;   // tail: recompute the last block, ignored below
             Ab[u] = P.Apack + bb * P.KS * 64 + lane;
         }

@@ -63,4 +63,17 @@ __host__ __device__ inline double keyed_normal(uint64_t seed, uint64_t restart, 
     return (elem & 1) ? rad * sin(ang) : rad * cos(ang);
 }
 
+// the normals of the element pair (elem, elem + 1), elem even: keyed_normal's own expressions -- the two share the counter
+// block elem >> 1, the radius and the angle; the even element takes the cosine, the odd one the sine -- evaluated once
+__host__ __device__ __attribute__((always_inline)) inline double keyed_normal_pair(uint64_t seed, uint64_t restart, uint64_t elem, double *odd) {
+    const U4 o = philox4x32_10((uint32_t)(elem >> 1), (uint32_t)(elem >> 33), 0xA5A50000u, (uint32_t)restart, (uint32_t)seed,
+                               (uint32_t)(seed >> 32) ^ (uint32_t)(restart >> 32));
+    const double u1 = (((double)(o.x >> 5) * 67108864.0 + (double)(o.y >> 6)) + 0.5) / 9007199254740992.0;
+    const double u2 = u53(o.z, o.w);
+    const double rad = sqrt(-2.0 * log(u1));
+    const double ang = 6.283185307179586476925286766559 * u2;
+    *odd = rad * sin(ang);
+    return rad * cos(ang);
+}
+
 }  // namespace qcqpmi

@@ -839,6 +839,51 @@ def test_build_units_cover_every_source_file():
             os.utime(hdr, (st.st_atime, st.st_mtime))
 
 
+def test_every_header_compiles_on_its_own(tmp_path):
+    """A header that needs something its includer happens to provide forces every new includer to fake it (cd_phase2.h once named
+    a function of the file that included it: three units carried stand-in definitions).  Each csrc/*.h is compiled alone, device
+    side, syntax only, with the build's flags; the .inc files are fragments of capi.hip by design."""
+    from concurrent.futures import ThreadPoolExecutor
+    from qcqp_amd import _build
+    hipcc = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
+    if not os.path.exists(hipcc):
+        pytest.skip('no hipcc')
+    flags = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-ffp-contract=off', '-I' + os.path.join(REPO, 'include'), '-I' + _build.SRC]
+    headers = sorted(f for f in os.listdir(_build.SRC) if f.endswith('.h'))
+    assert headers
+
+    def check(h):
+        src = tmp_path / (h + '.hip')
+        src.write_text('#include "%s"\n' % h)
+        p = subprocess.run([hipcc] + flags + ['--cuda-device-only', '-fsyntax-only', str(src)], stdout=subprocess.PIPE, stderr=subprocess.PIPE)
+        return h, p.returncode, p.stderr.decode()
+
+    with ThreadPoolExecutor(max_workers=8) as ex:
+        bad = [(h, err) for h, rc, err in ex.map(check, headers) if rc != 0]
+    assert not bad, bad
+
+
+def test_hip_files_are_exactly_the_translation_units():
+    """.hip means "compiled on its own": a file that another one includes is a header and is named like one."""
+    from qcqp_amd import _build
+    assert sorted(f for f in os.listdir(_build.SRC) if f.endswith('.hip')) == sorted(_build.TRANSLATION_UNITS)
+
+
+def test_shared_device_helpers_are_defined_once():
+    """The helpers several kernel files use have ONE definition under csrc/ (they used to be copied under per-file prefixes: a
+    fix had to be made in two or three places and nothing failed when one was missed)."""
+    from qcqp_amd import _build
+    names = ['block_rows_times_X', 'keyed_normal_pair', 'ordered_key', 'ordered_unkey', 'wave_max', 'p1_class_visit']
+    text = {f: open(os.path.join(_build.SRC, f)).read() for f in os.listdir(_build.SRC) if f.endswith(('.hip', '.h', '.inc'))}
+    for name in names:
+        # a line that starts the definition: qualifiers and a return type at the start of the line, then NAME( -- a call sits
+        # indented inside a body
+        start = re.compile(r'^(?:__host__ |__device__ |__attribute__\(\(\w+\)\) |inline |static )+[\w:<> ]*?[\w>] \*?%s\(' % name, re.M)
+        where = sorted(f for f, t in text.items() if start.search(t))
+        assert len(where) == 1, (name, where)
+        assert len(start.findall(text[where[0]])) == 1, (name, where)
+
+
 def test_host_thread_budget_follows_the_cgroup_quota_and_the_ranks(monkeypatch):
     """qcqp_amd/_threads.py (round 6: a 256-thread BLAS pool in a container with 16 cores of quota got the host thread that waits for
     the GPU throttled -- profiles/r06_timed_region.md): usable cores = min(affinity, quota), the BLAS pools get half of a rank's share
