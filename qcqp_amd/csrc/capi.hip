@@ -511,8 +511,10 @@ template <int MAXC>
 int launch_cd(qcqpmi_ctx *c, const CdArgs &a1, bool phase1, bool &used_lds, bool *used_rs = nullptr) {
     if (used_rs) *used_rs = false;
     if (!phase1) c->last_cd2_kernel = "cd_phase2_kernel";
+    const bool cd_debug = getenv("QCQPMI_CD_DEBUG") != nullptr;     // tests: one line per launch with the template arguments chosen below
     dim3 grid((unsigned)(c->Rpad / 16)), block(256);
     if (phase1) {
+        if (cd_debug) fprintf(stderr, "launch_cd: cd_phase1_sep_kernel MAXC %d\n", MAXC);
         tic(c, 1);
         hipLaunchKernelGGL(cd_phase1_sep_kernel<MAXC>, grid, dim3(P1_THREADS), 0, c->stream, a1);
         toc(c, 1);
@@ -540,6 +542,7 @@ int launch_cd(qcqpmi_ctx *c, const CdArgs &a1, bool phase1, bool &used_lds, bool
             CdQueueArgs qa;
             qa.P = dp; qa.num_iters = a1.num_iters; qa.tol = a1.tol; qa.life = nullptr; qa.life_on = 0;
             cd_queue_fill_batch(c, qa.b, a1.seed, a1.first_index);
+            if (cd_debug) fprintf(stderr, "launch_cd: cd_phase2_qs_kernel CS %d\n", cs);
             int cus = 0;
             HIPCHK(c, hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device));
             (void)hipEventRecord(c->timers[2].beg, c->stream);
@@ -558,6 +561,7 @@ int launch_cd(qcqpmi_ctx *c, const CdArgs &a1, bool phase1, bool &used_lds, bool
             if (prof_) k = cs == 0 ? cd_phase2_q_kernel<0, true> : cs == 2 ? cd_phase2_q_kernel<2, true> : cs == 4 ? cd_phase2_q_kernel<4, true> : cd_phase2_q_kernel<6, true>;
             else k = cs == 0 ? cd_phase2_q_kernel<0, false> : cs == 2 ? cd_phase2_q_kernel<2, false> : cs == 4 ? cd_phase2_q_kernel<4, false> : cd_phase2_q_kernel<6, false>;
             HIPCHK(c, hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)q_lds));
+            if (cd_debug) fprintf(stderr, "launch_cd: cd_phase2_q_kernel CS %d\n", cs);
             tic(c, 2);
             hipLaunchKernelGGL(k, grid, dim3(512), q_lds, c->stream, a1, dp.Apack, dp.Apack2, dp.P0, dp.q0, dp.rcp2d);
             toc(c, 2);
@@ -583,6 +587,7 @@ int launch_cd(qcqpmi_ctx *c, const CdArgs &a1, bool phase1, bool &used_lds, bool
         else k = full_ ? (sym_ ? cd_phase2_rs_kernel<XL, FA, true, true, false> : cd_phase2_rs_kernel<XL, FA, true, false, false>) \
                        : (sym_ ? cd_phase2_rs_kernel<XL, FA, false, true, false> : cd_phase2_rs_kernel<XL, FA, false, false, false>); \
         HIPCHK(c, hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)rs_lds)); \
+        if (cd_debug) fprintf(stderr, "launch_cd: cd_phase2_rs_kernel XL %d FA %d FULL %d SYM %d\n", (int)XL, FA, (int)full_, (int)sym_); \
         tic(c, 2);                                                                                  \
         hipLaunchKernelGGL(k, grid, block512, rs_lds, c->stream, a1, dp.Apack, dp.Apack2, dp.P0, dp.q0, dp.rcp2d); \
         toc(c, 2);                                                                                  \
@@ -613,6 +618,7 @@ int launch_cd(qcqpmi_ctx *c, const CdArgs &a1, bool phase1, bool &used_lds, bool
     do {                                                                                            \
         auto k = cd_phase2_kernel<MAXC, XL, CL, FA, UN>;                                                \
         HIPCHK(c, hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
+        if (cd_debug) fprintf(stderr, "launch_cd: cd_phase2_kernel MAXC %d XL %d CL %d FA %d UN %d\n", MAXC, (int)XL, (int)CL, FA, (int)UN); \
         tic(c, 2);                                                                                  \
         hipLaunchKernelGGL(k, grid, block, lds, c->stream, a1, dp.Apack, dp.P0, dp.q0, dp.rcp2d, dp.cls);      \
         toc(c, 2);                                                                                  \
