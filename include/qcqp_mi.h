@@ -369,6 +369,29 @@ int qcqpmi_cd_small_batch_run(qcqpmi_ctx *ctx, int64_t B, const double *P0s, con
                               int64_t *sweeps2, int64_t *visits2, int64_t *accepted2, uint8_t *ran_phase2, int *status1,
                               int *status2, double *f0, double *maxviol, double *X, int64_t *best_index, double *best_f0,
                               double *best_maxviol, double *best_x);
+/* SUGGEST(SDR) FOR MANY SMALL PROBLEMS IN ONE LAUNCH (added within ABI 6: a new symbol, nothing else changes).  The batch of
+ * qcqpmi_cd_small_batch_run -- B objectives P0s [B][n][n] (each symmetric), q0s [B][n], r0s [B] over this context's constraints, n <= 64
+ * -- for the UNIT-DIAGONAL family: every coordinate carries exactly one constraint p x_i^2 + r == 0 with d_i = -r / p > 0 and no linear
+ * term (Boolean least squares, MAXCUT, x_i^2 == d_i).  With N = n + 1 and s = sqrt(d), problem b's relaxation is
+ *     minimise <C_b, X>  s.t.  X_ii = 1, X PSD,   C_b[:n,:n] = P0_b o s s^T, C_b[:n,n] = C_b[n,:n] = q0_b o s / 2, C_b[n,n] = r0_b,
+ * solved in the form X = V V^T (V: N x 64, unit rows) by the mixing method of qcqpmi_sdr_solve_unitdiag (cyclic updates, the sweep
+ * objective tracked by the exact decrease of every update, stop at |delta_sweep| <= tol (1 + |f|) or max_sweeps, a row whose g_i is
+ * zero stays as it is) -- one wavefront per problem, V_b and C_b in its LDS, no wave waits for another (sdr_small_kernel,
+ * csrc/sdr_small.hip).  The same launch forms the multipliers y_i = -v_i . (C_b v)_i and draws S >= 0 samples per problem,
+ *     x = s o (V_n u + V_n (xi - u (u . xi))),   u = v_n,  V_n = rows 0..n-1,  xi_k = keyed normal (seed_b, first_index + sigma, k), k < 64:
+ * x ~ N(mu, Sigma) with mu = s o V_n u and Sigma = F F^T, F = diag(s) V_n (I - u u^T) -- the pair of suggest(SDR) (qcqp.py:394-396)
+ * without a decomposition (I - u u^T is a projector).  seed_b = seed + b seed_stride.  Start: row i of V0 = the keyed normals
+ * (seed_b, 2^64 - 1 - i, k), k < 64, divided by the root of their sum of squares (summed as a binary tree over adjacent k); or V0s
+ * [B][N][64], taken as it is.  The reference hands the relaxation to a third-party solver: parity unpinned by construction, validated
+ * by the certificate (lambda_min(C_b + diag(y_b)), qcqp_amd.sdr.certify_batch).  A problem's result depends on (P0_b, q0_b, r0_b, d,
+ * seed_b, first_index) alone -- not on B, the problems beside it, the workgroups or the dealing order: bit for bit.
+ * Outputs, any may be NULL: V [B][N][64], primal [B] (<C_b, V V^T> recomputed at the end), y [B][N], sweeps [B], X [B][S][n].
+ * QCQPMI_EUNSUPPORTED: constraints outside the family, n > 64.  QCQPMI_EINVAL: B < 1, S < 0, B S >= 2^30, a missing input, a P0_b that is
+ * not symmetric.  The call works in a buffer of its own: the resident population, its evaluation, its status codes and
+ * qcqpmi_last_cd_kernel stay as they were, whether the call succeeds or is refused. */
+int qcqpmi_sdr_small_batch(qcqpmi_ctx *ctx, int64_t B, const double *P0s, const double *q0s, const double *r0s, int64_t S,
+                           int max_sweeps, double tol, uint64_t seed, uint64_t seed_stride, uint64_t first_index,
+                           const double *V0s, double *V, double *primal, double *y, int64_t *sweeps, double *X);
 /* Device and pinned-host buffers for a qcqpmi_cd_stream_run(K, R) to come (population, per-restart outputs, per-population
  * winners): allocation only, so that a timed or latency-sensitive run does not start with hipMalloc / hipHostMalloc.  A
  * resident population smaller than K R points is dropped (like any reallocation of the population). */

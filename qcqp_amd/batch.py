@@ -3,7 +3,9 @@
 A frame of MIMO detection problems is thousands of independent Boolean least squares instances of 8 .. 64 variables: every
 instance has its own objective and all of them the constraints x_i^2 == 1.  ``QCQP`` holds one problem per context; this class
 holds B of them on ONE context and runs suggest(RANDOM) + improve(COORD_DESCENT) for all B x R restarts through one persistent
-kernel (``Engine.cd_small_batch_run``, qcqpmi_cd_small_batch_run).  Problem b's results are those of
+kernel (``Engine.cd_small_batch_run``, qcqpmi_cd_small_batch_run).  suggest(SDR) -- for constraints x_i^2 == d_i -- solves the
+semidefinite relaxation of all B problems and draws their samples in one launch as well (``Engine.sdr_small_batch``,
+qcqpmi_sdr_small_batch) and publishes the certified bounds in ``sdr_bound``; improve() then starts from the samples.  Problem b's results are those of
 ``QCQP(Problem(funcs_b))`` with suggest(RANDOM, num_samples=R, seed=seed + b seed_stride, first_index=...) followed by
 improve(COORD_DESCENT, ..., seed=seed + b seed_stride, first_index=...).
 
@@ -13,10 +15,13 @@ improve(COORD_DESCENT, ..., seed=seed + b seed_stride, first_index=...).
     batch.suggest(s.RANDOM, num_samples=64, seed=7)
     f, v = batch.improve(s.COORD_DESCENT)          # (B,), (B,): the best restart of every problem
     batch.x                                        # (B, n)
+    batch.suggest(s.SDR, num_samples=64, seed=7)   # the SDR detector: batch.sdr_bound (B,), samples of N(mu_b, Sigma_b)
+    f, v = batch.improve(s.COORD_DESCENT)
 """
 import numpy as np
 import scipy.sparse as sp
 
+from . import sdr as _sdr
 from . import settings as s
 from .engine import Engine
 from .form import QCQPForm
@@ -63,21 +68,41 @@ class QCQPBatch(object):
             self.P0s[b] = (P + P.T) / 2.          # like get_qcqp_form (utilities.py:333)
             self.q0s[b] = np.asarray(funcs[0][1], dtype=np.float64).ravel()
             self.r0s[b] = float(funcs[0][2])
-        self.engine = Engine(QCQPForm.from_arrays(funcs_list[0]), device=device)
+        self.form = QCQPForm.from_arrays(funcs_list[0])
+        self.engine = Engine(self.form, device=device)
         self._suggested = None
+        self._starts = None          # (B, R, n): the samples of suggest(SDR); None: improve() draws the keyed normals itself
+        self.sdr_bound = None
+        self.sdr_info = None
         self.x = None
         self.population_f = None
         self.population_v = None
         self.best_index = None
         self.last_stats = None
 
-    def suggest(self, method=s.RANDOM, num_samples=1, seed=0, first_index=0, seed_stride=1):
-        """R = num_samples random starts per problem: problem b draws the keyed normals (seed + b seed_stride, first_index + r).
-        The points are drawn inside the launch of improve(); nothing runs here."""
-        if method != s.RANDOM:
-            raise Exception("QCQPBatch.suggest is defined for the RANDOM method")
+    def suggest(self, method=s.RANDOM, num_samples=1, seed=0, first_index=0, seed_stride=1, max_sweeps=5000, tol=1e-11):
+        """RANDOM: R = num_samples random starts per problem: problem b draws the keyed normals (seed + b seed_stride, first_index + r).
+        The points are drawn inside the launch of improve(); nothing runs here.
+        SDR (constraints x_i^2 == d_i): one launch solves the relaxation of every problem (mixing method, max_sweeps / tol) and
+        draws R samples of N(mu_b, Sigma_b) from the keyed normals (seed + b seed_stride, first_index + r); every solve is certified
+        (sdr.certify_batch, which logs the warning for problems that are not certified).  Sets .sdr_bound (B,) -- the rigorous lower bound, NaN where the problem is not certified -- and
+        .sdr_info (primal, sweeps, lambda_min, converged); the samples are the starts of improve()."""
+        if method not in (s.RANDOM, s.SDR):
+            raise Exception("QCQPBatch.suggest is defined for the RANDOM and SDR methods")
         if int(num_samples) < 1:
             raise Exception("QCQPBatch.suggest: num_samples must be positive")
+        if method == s.SDR:
+            d = _sdr.unit_diagonal_family(self.form)
+            if d is None:
+                raise Exception("QCQPBatch.suggest(SDR) is defined for constraints x_i^2 == d_i (one per coordinate)")
+            out = self.engine.sdr_small_batch(self.P0s, self.q0s, self.r0s, int(num_samples), max_sweeps=max_sweeps, tol=tol, seed=seed,
+                                              seed_stride=seed_stride, first_index=first_index, want_V=False)
+            cert = _sdr.certify_batch(_sdr.lifted_cost_batch(self.P0s, self.q0s, self.r0s, d), out['y'], out['sweeps'], max_sweeps)
+            self.sdr_bound = np.where(cert['converged'], cert['bound'], np.nan)
+            self.sdr_info = dict(primal=out['primal'], sweeps=out['sweeps'], lambda_min=cert['lambda_min'], converged=cert['converged'])
+            self._starts = out['X']
+        else:
+            self._starts = None
         self._suggested = (int(num_samples), int(seed), int(first_index), int(seed_stride))
 
     def improve(self, method=s.COORD_DESCENT, num_iters=1000, viol_tol=1e-2, tol=1e-4, phase1=True, seed=None):
@@ -87,12 +112,12 @@ class QCQPBatch(object):
         if method != s.COORD_DESCENT:
             raise Exception("QCQPBatch.improve is defined for the COORD_DESCENT method")
         if self._suggested is None:
-            raise Exception("QCQPBatch.improve: call suggest(RANDOM, num_samples=R, seed=...) first")
+            raise Exception("QCQPBatch.improve: call suggest(RANDOM or SDR, num_samples=R, seed=...) first")
         R, sd, first_index, stride = self._suggested
         if seed is not None and int(seed) != sd:
             raise Exception("QCQPBatch.improve: seed %d differs from the seed of suggest (%d); the batch runs one keyed stream per problem"
                             % (int(seed), sd))
-        out = self.engine.cd_small_batch_run(self.P0s, self.q0s, self.r0s, R, phase1=phase1, num_iters=num_iters, viol_tol=viol_tol,
+        out = self.engine.cd_small_batch_run(self.P0s, self.q0s, self.r0s, R, X0=self._starts, phase1=phase1, num_iters=num_iters, viol_tol=viol_tol,
                                              tol=tol, seed=sd, seed_stride=stride, first_index=first_index, want_x=False)
         self.x = out['best_x']
         self.best_index = out['best_index']

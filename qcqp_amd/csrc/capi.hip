@@ -21,6 +21,7 @@
 #include "cd_queue.h"
 #include "cd_life.h"
 #include "cd_small.h"
+#include "sdr_small.h"
 #include "gemm_pk.h"
 #include "cd_general.h"
 #include "cd_dense.h"
@@ -218,6 +219,11 @@ struct qcqpmi_ctx {
     // (grown on demand; the resident population and its buffers are never used by that call)
     char *sb_work = nullptr;
     size_t sb_work_cap = 0;
+    // qcqpmi_sdr_small_batch: d (n) when every coordinate carries exactly one constraint p x_i^2 + r == 0 with d_i = -r / p > 0 (the
+    // unit-diagonal family of the relaxation), else empty; and the call's own device buffer, like sb_work
+    std::vector<double> unit_d;
+    char *ss_work = nullptr;
+    size_t ss_work_cap = 0;
 };
 
 namespace {
@@ -760,7 +766,7 @@ void qcqpmi_ctx_destroy(qcqpmi_ctx *c) {
     admm_free(c, false);
     for (void *p : c->prob_allocs) (void)hipFree(p);
     void *ptrs[] = {c->d_Fpack, c->d_Frow, c->d_mu, c->d_best_idx, c->d_best_key, c->d_comm, c->d_comm_big,   // d_gP is in prob_allocs
-                    c->dn_G, c->dn_Dg, c->dn_Ft, c->dn_prof, c->dn_state, c->d_planes, c->d_out, c->d_wS, c->d_wY, c->d_ww, c->d_wz, c->af_work, c->d_qnext, c->d_life, c->d_life_prof, c->d_bestK_idx, c->d_bestK_key, c->d_bestK_x, c->l2_scratch, c->l2_D, c->l2_S, c->l2_abort, c->l2_cuslot, c->l2_preslack, c->lr_L, c->lr_G, c->lr_U, c->sb_work};
+                    c->dn_G, c->dn_Dg, c->dn_Ft, c->dn_prof, c->dn_state, c->d_planes, c->d_out, c->d_wS, c->d_wY, c->d_ww, c->d_wz, c->af_work, c->d_qnext, c->d_life, c->d_life_prof, c->d_bestK_idx, c->d_bestK_key, c->d_bestK_x, c->l2_scratch, c->l2_D, c->l2_S, c->l2_abort, c->l2_cuslot, c->l2_preslack, c->lr_L, c->lr_G, c->lr_U, c->sb_work, c->ss_work};
     if (c->h_out) (void)hipHostFree(c->h_out);
     if (c->h_pin) (void)hipHostFree(c->h_pin);
     for (void *p : ptrs) if (p) (void)hipFree(p);
@@ -1012,6 +1018,17 @@ int qcqpmi_finalize(qcqpmi_ctx *c) {
             cp[e] = p; cq[e] = h.q[i]; cr[e] = h.r; crel[e] = h.relop; cidx[e] = (int)k + 1;
         }
         c->maxc = maxc; dp.maxc = maxc;
+        c->unit_d.clear();
+        if (m == n) {
+            std::vector<double> d((size_t)n, 0.0);
+            bool fam = true;
+            for (int64_t i = 0; i < n && fam; i++) {
+                const int e = cptr[i];
+                fam = cptr[i + 1] - e == 1 && cq[e] == 0.0 && crel[e] == RELOP_EQ && cp[e] != 0.0;
+                if (fam) { d[(size_t)i] = -cr[e] / cp[e]; fam = d[(size_t)i] > 0.0; }
+            }
+            if (fam) c->unit_d = d;
+        }
         // constraint classes: coordinates whose (p, q, r, relop) lists are bit-identical
         {
             std::vector<int> cls((size_t)n16, 0), krep;
@@ -1845,6 +1862,70 @@ int qcqpmi_cd_small_batch_run(qcqpmi_ctx *c, int64_t B, const double *P0s, const
         if (best_f0) best_f0[b] = bkey[(size_t)2 * b];
         if (best_maxviol) best_maxviol[b] = bkey[(size_t)2 * b + 1];
     }
+    return 0;
+}
+
+// ---- suggest(SDR) for B small problems (n <= 64) of the unit-diagonal family that share the context's constraints x_i^2 == d_i: the
+// relaxation (mixing method), its multipliers and S samples per problem in ONE launch of sdr_small_kernel (csrc/sdr_small.hip).  Works
+// in a buffer of its own: the resident population, its evaluation, its status codes and qcqpmi_last_cd_kernel are not touched, whether
+// the call succeeds or is refused.
+int qcqpmi_sdr_small_batch(qcqpmi_ctx *c, int64_t B, const double *P0s, const double *q0s, const double *r0s, int64_t S, int max_sweeps,
+                           double tol, uint64_t seed, uint64_t seed_stride, uint64_t first_index, const double *V0s, double *V,
+                           double *primal, double *y, int64_t *sweeps, double *X) {
+    int rc = check_ready(c, false);
+    if (rc) return rc;
+    if (c->n > SDR_SMALL_MAXN) return fail(c, QCQPMI_EUNSUPPORTED, "sdr_small_batch: n = %lld, the small-problem kernel takes n <= %d", (long long)c->n, SDR_SMALL_MAXN);
+    if (!c->sep || c->unit_d.empty()) return fail(c, QCQPMI_EUNSUPPORTED, "sdr_small_batch: the constraints are not of the unit-diagonal family (every coordinate exactly one constraint p x_i^2 + r == 0 with -r / p > 0)");
+    if (B < 1 || S < 0 || max_sweeps < 0 || !(tol >= 0.0) || !P0s || !q0s || !r0s)
+        return fail(c, QCQPMI_EINVAL, "sdr_small_batch: bad B / S / max_sweeps / tol, or a missing input array");
+    if (B >= (1LL << 30) || S >= (1LL << 30) || B * (S > 0 ? S : 1) >= (1LL << 30)) return fail(c, QCQPMI_EINVAL, "sdr_small_batch: B = %lld problems with S = %lld samples, at most 2^30 - 1 per call", (long long)B, (long long)S);
+    HIPCHK(c, hipSetDevice(c->device));
+    const int64_t n = c->n, N = n + 1;
+    // ---- carve the work buffer (every piece 256-byte aligned)
+    size_t off = 0;
+    auto take = [&off](size_t bytes) { const size_t o = off; off += (bytes + 255) / 256 * 256; return o; };
+    const size_t oP = take((size_t)B * n * n * 8), oq = take((size_t)B * n * 8), or0 = take((size_t)B * 8), os = take((size_t)n * 8);
+    const size_t oV0 = take(V0s ? (size_t)B * N * SDR_SMALL_K * 8 : 0), oV = take((size_t)B * N * SDR_SMALL_K * 8);
+    const size_t opr = take((size_t)B * 8), oy = take((size_t)B * N * 8), osw = take((size_t)B * 8), oX = take((size_t)B * S * n * 8);
+    const size_t oticket = take(2 * sizeof(int));
+    if (off > c->ss_work_cap) {
+        HIPCHK(c, spin_sync(c->stream));
+        if (c->ss_work) (void)hipFree(c->ss_work);
+        c->ss_work = nullptr; c->ss_work_cap = 0;
+        HIPCHK(c, hipMalloc((void **)&c->ss_work, off));
+        c->ss_work_cap = off;
+    }
+    char *w = c->ss_work;
+    std::vector<double> sv((size_t)n);
+    for (int64_t i = 0; i < n; i++) sv[(size_t)i] = sqrt(c->unit_d[(size_t)i]);
+    HIPCHK(c, hipMemcpyAsync(w + oP, P0s, (size_t)B * n * n * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(w + oq, q0s, (size_t)B * n * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(w + or0, r0s, (size_t)B * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(w + os, sv.data(), (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
+    if (V0s) HIPCHK(c, hipMemcpyAsync(w + oV0, V0s, (size_t)B * N * SDR_SMALL_K * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemsetAsync(w + oticket, 0, 2 * sizeof(int), c->stream));
+    HIPCHK(c, spin_sync(c->stream));      // sv goes out of scope; the pageable copies above have been staged
+    SdrSmallArgs a;
+    a.n = (int)n; a.B = B; a.S = S;
+    a.s = (const double *)(w + os); a.P0s = (const double *)(w + oP); a.q0s = (const double *)(w + oq); a.r0s = (const double *)(w + or0);
+    a.V0s = V0s ? (const double *)(w + oV0) : nullptr;
+    a.max_sweeps = max_sweeps; a.tol = tol; a.seed = seed; a.seed_stride = seed_stride; a.first_index = first_index;
+    a.ticket = (int *)(w + oticket);
+    a.V = (double *)(w + oV); a.primal = (double *)(w + opr); a.y = (double *)(w + oy); a.sweeps = (int64_t *)(w + osw); a.X = (double *)(w + oX);
+    const int wgs = sdr_small_workgroups((int)n, B, c->device);
+    if (wgs < 1) return fail(c, QCQPMI_EHIP, "sdr_small_batch: occupancy query failed: %s", hipGetErrorString((hipError_t)(-wgs)));
+    const hipError_t qe = (hipError_t)sdr_small_launch(a, wgs, c->stream);
+    if (qe != hipSuccess) return fail(c, QCQPMI_EHIP, "sdr_small_batch: %s", hipGetErrorString(qe));
+    int flags[2] = {0, 0};
+    HIPCHK(c, hipMemcpyAsync(flags, w + oticket, sizeof(flags), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, spin_sync(c->stream));
+    if (flags[1]) return fail(c, QCQPMI_EINVAL, "sdr_small_batch: an objective matrix P0_b is not symmetric (or holds a NaN)");
+    if (V) HIPCHK(c, hipMemcpyAsync(V, a.V, (size_t)B * N * SDR_SMALL_K * 8, hipMemcpyDeviceToHost, c->stream));
+    if (primal) HIPCHK(c, hipMemcpyAsync(primal, a.primal, (size_t)B * 8, hipMemcpyDeviceToHost, c->stream));
+    if (y) HIPCHK(c, hipMemcpyAsync(y, a.y, (size_t)B * N * 8, hipMemcpyDeviceToHost, c->stream));
+    if (sweeps) HIPCHK(c, hipMemcpyAsync(sweeps, a.sweeps, (size_t)B * 8, hipMemcpyDeviceToHost, c->stream));
+    if (X && S > 0) HIPCHK(c, hipMemcpyAsync(X, a.X, (size_t)B * S * n * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, spin_sync(c->stream));
     return 0;
 }
 

@@ -1,5 +1,5 @@
 // Small device helpers shared by the kernel files: pointers typed as global memory with their relaxed agent-scope
-// accesses, the order-preserving map between doubles and unsigned integers, the wave-wide maximum.
+// accesses, the order-preserving map between doubles and unsigned integers, the wave-wide maximum and sum.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -30,6 +30,27 @@ __device__ __attribute__((always_inline)) inline double ordered_unkey(unsigned l
 __device__ __attribute__((always_inline)) inline double wave_max(double v) {
 #pragma unroll
     for (int o = 32; o >= 1; o >>= 1) { const double w = __shfl_xor(v, o, 64); v = w > v ? w : v; }
+    return v;
+}
+
+// one value per lane from the lane a DPP control names (quad_perm / row_mirror / row_half_mirror: every lane has a partner)
+template <int CTRL>
+__device__ __attribute__((always_inline)) inline double dpp_partner(double v) {
+    const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), CTRL, 0xf, 0xf, false);
+    const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), CTRL, 0xf, 0xf, false);
+    return __hiloint2double(hi, lo);
+}
+
+// sum over the 64 lanes of a wave in ONE fixed order: the binary tree over adjacent lanes -- pairs, quads, eights (a lane and its
+// mirror image in the group of eight hold the two quads' sums), sixteens (mirror image in the row), then lane ^ 16 and lane ^ 32.
+// The two partners of a step add the same two numbers, so every lane ends with the same bits.
+__device__ __attribute__((always_inline)) inline double wave_sum_tree(double v) {
+    v += dpp_partner<0xB1>(v);       // quad_perm [1, 0, 3, 2]
+    v += dpp_partner<0x4E>(v);       // quad_perm [2, 3, 0, 1]
+    v += dpp_partner<0x141>(v);      // row_half_mirror
+    v += dpp_partner<0x140>(v);      // row_mirror
+    v += __shfl_xor(v, 16, 64);
+    v += __shfl_xor(v, 32, 64);
     return v;
 }
 

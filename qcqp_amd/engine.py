@@ -424,6 +424,31 @@ class Engine(object):
         self._chk(self.L.qcqpmi_sdr_solve_unitdiag(self.h, _dp(Cm), N, _dp(V), int(max_sweeps), float(tol), _dp(hist), C.byref(sw)))
         return V, hist[:sw.value + 2], sw.value
 
+    def sdr_small_batch(self, P0s, q0s, r0s, S, max_sweeps=5000, tol=1e-11, seed=0, seed_stride=1, first_index=0, V0s=None,
+                        want_V=True):
+        """suggest(SDR) for B small problems (n <= 64) that share this context's constraints x_i^2 == d_i and differ in their objective
+        -- P0s (B, n, n) symmetric, q0s (B, n), r0s (B,) -- in ONE launch (qcqpmi_sdr_small_batch): the relaxation of every problem by
+        the mixing method (start: keyed normal rows of seed + b seed_stride, or V0s (B, n + 1, 64)), its multipliers and S >= 0
+        samples x = s o (V_n u + V_n (xi - u (u . xi))), xi = the keyed normals (seed + b seed_stride, first_index + sample).
+        Returns a dictionary: V (B, n + 1, 64) if want_V, primal (B,), y (B, n + 1), sweeps (B,), X (B, S, n).  The resident
+        population is not touched."""
+        P0s = np.ascontiguousarray(P0s, dtype=np.float64)
+        q0s = np.ascontiguousarray(q0s, dtype=np.float64)
+        r0s = np.ascontiguousarray(r0s, dtype=np.float64).ravel()
+        B, S, n = int(P0s.shape[0]) if P0s.ndim == 3 else 0, int(S), self.n
+        if P0s.shape != (B, n, n) or q0s.shape != (B, n) or r0s.shape != (B,):
+            raise ValueError('sdr_small_batch: expected P0s (B, n, n), q0s (B, n), r0s (B,) with n = %d' % n)
+        if V0s is not None:
+            V0s = np.ascontiguousarray(V0s, dtype=np.float64)
+            if V0s.shape != (B, n + 1, 64):
+                raise ValueError('sdr_small_batch: expected V0s of shape (B, n + 1, 64)')
+        out = dict(V=np.empty((B, n + 1, 64)) if want_V else None, primal=np.empty(B), y=np.empty((B, n + 1)),
+                   sweeps=np.zeros(B, dtype=np.int64), X=np.empty((B, max(S, 0), n)))
+        self._chk(self.L.qcqpmi_sdr_small_batch(self.h, B, _dp(P0s), _dp(q0s), _dp(r0s), S, int(max_sweeps), float(tol), int(seed),
+                                                int(seed_stride), int(first_index), _dp(V0s), _dp(out['V']), _dp(out['primal']),
+                                                _dp(out['y']), _ip(out['sweeps']), _dp(out['X']) if S > 0 else None))
+        return out
+
     # ------------------------------------------------------------------ selection
     def select_best(self, tol=1e-4, want_x=True):
         idx = np.zeros(1, dtype=np.int64)

@@ -75,6 +75,50 @@ def dual_certificate(C, V):
     return y, lmin, float(-y.sum() + C.shape[0] * min(0.0, lmin))
 
 
+def lifted_cost_batch(P0s, q0s, r0s, d):
+    """C (B, N, N) of lifted_cost for B objectives over the same d: the same products, problem by problem."""
+    P0s = np.asarray(P0s, dtype=np.float64)
+    q0s = np.asarray(q0s, dtype=np.float64)
+    B, n = q0s.shape
+    s = np.sqrt(np.asarray(d, dtype=np.float64))
+    C = np.zeros((B, n + 1, n + 1))
+    C[:, :n, :n] = (0.5 * (P0s + P0s.transpose(0, 2, 1))) * np.outer(s, s)
+    C[:, :n, n] = C[:, n, :n] = 0.5 * q0s * s
+    C[:, n, n] = np.asarray(r0s, dtype=np.float64)
+    return C
+
+
+def certify_batch(C, y, sweeps, max_sweeps, what='sdr_small_batch (mixing method)'):
+    """certify for a batch of mixing-method solves: C (B, N, N), multipliers y (B, N), sweeps (B,).  S_b = C_b + diag(y_b),
+    lambda_min by ONE batched eigvalsh (BLAS pools capped, _threads.py), the rigorous bound -sum(y_b) + N min(0, lambda_min_b)
+    (valid for any y), converged_b by certify's thresholds: lambda_min_b >= -1e-6 (1 + max |C_b|) and the sweep limit not hit.
+    Raises where certify raises (lambda_min_b < -1e-2 (1 + max |C_b|)); problems that are merely not converged are logged.
+    Returns dict(lambda_min, bound, converged, scale), arrays of B."""
+    import logging
+    from . import _threads
+    C = np.asarray(C, dtype=np.float64)
+    y = np.asarray(y, dtype=np.float64)
+    B, N = y.shape
+    Sm = C.copy()
+    idx = np.arange(N)
+    Sm[:, idx, idx] += y
+    with _threads.blas_limit():
+        lmin = np.linalg.eigvalsh(0.5 * (Sm + Sm.transpose(0, 2, 1)))[:, 0]
+    scale = 1.0 + np.max(np.abs(C.reshape(B, -1)), axis=1)
+    bound = -y.sum(axis=1) + N * np.minimum(0.0, lmin)
+    limit = np.asarray(sweeps) >= int(max_sweeps)
+    converged = (lmin >= -1e-6 * scale) & ~limit
+    bad = np.nonzero(~converged)[0]
+    if bad.size:
+        w = int(bad[np.argmin(lmin[bad] / scale[bad])])
+        msg = ('%s: relaxation not solved to optimality for %d of %d problems (worst: problem %d, lambda_min of the dual slack '
+               '%.3e, iteration limit hit: %s)' % (what, bad.size, B, w, lmin[w], bool(limit[w])))
+        if np.any(lmin < -1e-2 * scale):
+            raise Exception("Relaxation problem status: " + msg)
+        logging.getLogger('qcqp_amd').warning(msg + '; the published bound is the rigorous / dual value where one exists')
+    return dict(lambda_min=lmin, bound=bound, converged=converged, scale=scale)
+
+
 def solve_sdr(engine, form, max_sweeps=5000, tol=1e-11, seed=0):
     """Returns (X, bound, info) like the reference's solve_sdr returns (X, bound): X is the lifted
     (n+1) x (n+1) solution in the ORIGINAL variables, bound = <M0, X> (minimise form)."""
