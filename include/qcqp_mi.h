@@ -369,6 +369,26 @@ int qcqpmi_cd_small_batch_run(qcqpmi_ctx *ctx, int64_t B, const double *P0s, con
                               int64_t *sweeps2, int64_t *visits2, int64_t *accepted2, uint8_t *ran_phase2, int *status1,
                               int *status2, double *f0, double *maxviol, double *X, int64_t *best_index, double *best_f0,
                               double *best_maxviol, double *best_x);
+/* THE SAME LAUNCH WITH PER-PROBLEM CONSTRAINT COEFFICIENTS (added within ABI 6: a new symbol, nothing else changes).  The context
+ * fixes the STRUCTURE of the constraints -- their number m, the coordinate constraint k touches and its relop -- and every problem
+ * brings its own coefficients: cons [B][m][3], (p, q, r) of constraint k of problem b at cons[(b m + k) 3 ..], k = 0..m-1 in the
+ * order of qcqpmi_set_quad (k + 1 there); p is the diagonal entry P_k[i,i] and q the linear entry q_k[i] on the coordinate i that
+ * constraint k touches in the context, r the constant: the values qcqpmi_finalize keeps per list entry.  Box-constrained QPs with
+ * bounds per instance ((x_i - lo)(x_i - hi) <= 0: p = 1, q = -(lo + hi), r = lo hi), annuli with per-instance radii, x_i^2 == d_{b,i}.
+ * PARITY.  Restart (b, r) is BIT FOR BIT restart r of qcqpmi_cd_small_batch_run called with B = 1 and seed + b seed_stride on a
+ * context created from problem b's own functions (same structure, b's coefficients); that restart is in turn the qcqpmi_pop_randn +
+ * qcqpmi_cd_run restart of that context, to the rounding stated above.  A result depends on (objective b, constraints b, seed of b,
+ * global index) alone.  A call whose cons repeats the context's coefficients for every problem equals the shared call bit for bit.
+ * The ticket's workgroup stages problem b's coefficients in LDS beside P0_b (cd_small_kernel<MAXC, pc>: 24 m bytes more, at most
+ * 6 KB); qcqpmi_last_cd_kernel: "cd_small_kernel<1,pc>" / "cd_small_kernel<4,pc>".  Refusals, the resident population left alone:
+ * those of qcqpmi_cd_small_batch_run, and QCQPMI_EINVAL for cons == NULL, a coefficient that is not finite, or a constraint of some
+ * problem with p == 0 and q == 0 (it touches no coordinate: no context could have been built from it). */
+int qcqpmi_cd_small_batch_run_pc(qcqpmi_ctx *ctx, int64_t B, const double *P0s, const double *q0s, const double *r0s,
+                                 const double *cons, int64_t R, int generate, const double *X0, int phase1, int64_t num_iters,
+                                 double viol_tol, double tol, uint64_t seed, uint64_t seed_stride, uint64_t first_index,
+                                 double select_tol, int64_t *sweeps1, int64_t *sweeps2, int64_t *visits2, int64_t *accepted2,
+                                 uint8_t *ran_phase2, int *status1, int *status2, double *f0, double *maxviol, double *X,
+                                 int64_t *best_index, double *best_f0, double *best_maxviol, double *best_x);
 /* SUGGEST(SDR) FOR MANY SMALL PROBLEMS IN ONE LAUNCH (added within ABI 6: a new symbol, nothing else changes).  The batch of
  * qcqpmi_cd_small_batch_run -- B objectives P0s [B][n][n] (each symmetric), q0s [B][n], r0s [B] over this context's constraints, n <= 64
  * -- for the UNIT-DIAGONAL family: every coordinate carries exactly one constraint p x_i^2 + r == 0 with d_i = -r / p > 0 and no linear
@@ -392,6 +412,15 @@ int qcqpmi_cd_small_batch_run(qcqpmi_ctx *ctx, int64_t B, const double *P0s, con
 int qcqpmi_sdr_small_batch(qcqpmi_ctx *ctx, int64_t B, const double *P0s, const double *q0s, const double *r0s, int64_t S,
                            int max_sweeps, double tol, uint64_t seed, uint64_t seed_stride, uint64_t first_index,
                            const double *V0s, double *V, double *primal, double *y, int64_t *sweeps, double *X);
+/* THE SAME LAUNCH WITH PER-PROBLEM d (added within ABI 6: a new symbol, nothing else changes): problem b has the constraints
+ * x_i^2 == ds[b n + i], ds [B][n], every entry > 0 and finite; the context must be of the unit-diagonal family as above and ds
+ * replaces its d problem by problem (s_b = sqrt(ds_b) scales C_b and the samples).  PARITY: problem b's V, y, primal, sweeps and X are
+ * BIT FOR BIT those of qcqpmi_sdr_small_batch called with B = 1 and seed + b seed_stride on a context created from problem b's own
+ * functions (d = ds_b); a result depends on (objective b, ds_b, seed of b, first_index) alone.  Refusals: those of
+ * qcqpmi_sdr_small_batch, and QCQPMI_EINVAL for ds == NULL or an entry that is not positive and finite. */
+int qcqpmi_sdr_small_batch_pc(qcqpmi_ctx *ctx, int64_t B, const double *P0s, const double *q0s, const double *r0s, const double *ds,
+                              int64_t S, int max_sweeps, double tol, uint64_t seed, uint64_t seed_stride, uint64_t first_index,
+                              const double *V0s, double *V, double *primal, double *y, int64_t *sweeps, double *X);
 /* Device and pinned-host buffers for a qcqpmi_cd_stream_run(K, R) to come (population, per-restart outputs, per-population
  * winners): allocation only, so that a timed or latency-sensitive run does not start with hipMalloc / hipHostMalloc.  A
  * resident population smaller than K R points is dropped (like any reallocation of the population). */

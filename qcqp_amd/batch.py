@@ -1,4 +1,4 @@
-"""QCQPBatch: many SMALL problems that share their constraints, solved in one launch.
+"""QCQPBatch: many SMALL problems that share their constraints -- or the structure of their constraints --, solved in one launch.
 
 A frame of MIMO detection problems is thousands of independent Boolean least squares instances of 8 .. 64 variables: every
 instance has its own objective and all of them the constraints x_i^2 == 1.  ``QCQP`` holds one problem per context; this class
@@ -7,7 +7,9 @@ kernel (``Engine.cd_small_batch_run``, qcqpmi_cd_small_batch_run).  suggest(SDR)
 semidefinite relaxation of all B problems and draws their samples in one launch as well (``Engine.sdr_small_batch``,
 qcqpmi_sdr_small_batch) and publishes the certified bounds in ``sdr_bound``; improve() then starts from the samples.  Problem b's results are those of
 ``QCQP(Problem(funcs_b))`` with suggest(RANDOM, num_samples=R, seed=seed + b seed_stride, first_index=...) followed by
-improve(COORD_DESCENT, ..., seed=seed + b seed_stride, first_index=...).
+improve(COORD_DESCENT, ..., seed=seed + b seed_stride, first_index=...).  Problems whose constraints differ in their COEFFICIENTS
+only (boxes with bounds per instance, x_i^2 == d_{b,i}: problems.per_problem_constraints_batch) run through the same launches with
+per-problem coefficients.
 
     from qcqp_amd.batch import QCQPBatch
     from qcqp_amd import problems, settings as s
@@ -44,9 +46,38 @@ def _same_constraints(fa, fb):
     return True
 
 
+def _entry(P, q, r, relop):
+    """(coordinate, relop, p, q, r) of a constraint that touches ONE coordinate -- p = P[i,i], q = q[i]: what qcqpmi_finalize keeps per
+    list entry -- or None for any other constraint (coupled, or constant).  The stored entries of a sparse P count as touched, zero or
+    not, as the context counts them."""
+    q = np.asarray(q, dtype=np.float64).ravel()
+    if sp.issparse(P):
+        Pc = P.tocoo()
+        rows, cols, vals = Pc.row, Pc.col, Pc.data
+    else:
+        Pd = np.asarray(P, dtype=np.float64)
+        rows, cols = np.nonzero(Pd)
+        vals = Pd[rows, cols]
+    touched = set(int(i) for i in rows) | set(int(j) for j in cols) | set(int(j) for j in np.nonzero(q)[0])
+    if len(touched) != 1:
+        return None
+    i = touched.pop()
+    return i, relop, float(np.sum(vals)), float(q[i]), float(r)
+
+
+def _structure(funcs):
+    """The entries of every constraint, or None if one of them is not separable."""
+    out = [_entry(*f) for f in funcs[1:]]
+    return None if any(e is None for e in out) else out
+
+
 class QCQPBatch(object):
     """``funcs_list`` = [funcs_0, ..., funcs_{B-1}], every funcs_b = [(P, q, r, relop), ...] in minimise form with the objective
-    first (what qcqp_amd.problems returns).  All problems must have the same n (<= 64) and the same constraints."""
+    first (what qcqp_amd.problems returns).  All problems must have the same n (<= 64) and constraints of the same STRUCTURE: the
+    same number of them, and constraint k with the same relop on the same coordinate in every problem.  Their coefficients may
+    differ from problem to problem (separable constraints only): ``cons`` (B, m, 3) then holds (p, q, r) of every constraint and the
+    launches are qcqpmi_cd_small_batch_run_pc / qcqpmi_sdr_small_batch_pc; with equal coefficients ``cons`` is None and the calls are
+    those for shared constraints."""
 
     def __init__(self, funcs_list, device=0):
         funcs_list = [list(f) for f in funcs_list]
@@ -57,8 +88,20 @@ class QCQPBatch(object):
             nb = int(np.asarray(funcs[0][1]).size)
             if nb != n:
                 raise Exception("QCQPBatch: problem %d has n = %d, problem 0 has n = %d" % (b, nb, n))
-            if b > 0 and not _same_constraints(funcs_list[0], funcs):
-                raise Exception("QCQPBatch: the constraints of problem %d differ from those of problem 0" % b)
+        differing = [b for b in range(1, len(funcs_list)) if not _same_constraints(funcs_list[0], funcs_list[b])]
+        self.cons = None
+        if differing:
+            st0 = _structure(funcs_list[0])
+            cons = np.empty((len(funcs_list), len(funcs_list[0]) - 1, 3))
+            for b, funcs in enumerate(funcs_list):
+                st = st0 if b == 0 else _structure(funcs)
+                if st0 is None or st is None or len(st) != len(st0) or any(e[:2] != e0[:2] for e, e0 in zip(st, st0)):
+                    raise Exception("QCQPBatch: the constraints of problem %d differ from those of problem 0 in their structure (number, "
+                                    "touched coordinate or relop; only the coefficients of separable constraints may differ)"
+                                    % (b if st0 is not None else differing[0]))
+                cons[b] = [e[2:] for e in st]
+            self.cons = cons
+            self._coords = np.array([e[0] for e in st0])
         self.B, self.n = len(funcs_list), n
         self.P0s = np.empty((self.B, n, n))
         self.q0s = np.empty((self.B, n))
@@ -95,8 +138,19 @@ class QCQPBatch(object):
             d = _sdr.unit_diagonal_family(self.form)
             if d is None:
                 raise Exception("QCQPBatch.suggest(SDR) is defined for constraints x_i^2 == d_i (one per coordinate)")
+            ds = None
+            if self.cons is not None:      # the family test problem by problem: p x_i^2 + r == 0 with d_b = -r / p > 0, no linear term
+                p, q, r = self.cons[:, :, 0], self.cons[:, :, 1], self.cons[:, :, 2]
+                ds = np.empty((self.B, self.n))
+                with np.errstate(divide='ignore', invalid='ignore'):
+                    ds[:, self._coords] = -r / p
+                bad = np.any(q != 0.0, axis=1) | ~np.all((ds > 0.0) & np.isfinite(ds), axis=1)
+                if bad.any():
+                    raise Exception("QCQPBatch.suggest(SDR) is defined for constraints x_i^2 == d_i (one per coordinate): problem %d is "
+                                    "not of the family" % int(np.nonzero(bad)[0][0]))
+                d = ds
             out = self.engine.sdr_small_batch(self.P0s, self.q0s, self.r0s, int(num_samples), max_sweeps=max_sweeps, tol=tol, seed=seed,
-                                              seed_stride=seed_stride, first_index=first_index, want_V=False)
+                                              seed_stride=seed_stride, first_index=first_index, want_V=False, ds=ds)
             cert = _sdr.certify_batch(_sdr.lifted_cost_batch(self.P0s, self.q0s, self.r0s, d), out['y'], out['sweeps'], max_sweeps)
             self.sdr_bound = np.where(cert['converged'], cert['bound'], np.nan)
             self.sdr_info = dict(primal=out['primal'], sweeps=out['sweeps'], lambda_min=cert['lambda_min'], converged=cert['converged'])
@@ -118,7 +172,7 @@ class QCQPBatch(object):
             raise Exception("QCQPBatch.improve: seed %d differs from the seed of suggest (%d); the batch runs one keyed stream per problem"
                             % (int(seed), sd))
         out = self.engine.cd_small_batch_run(self.P0s, self.q0s, self.r0s, R, X0=self._starts, phase1=phase1, num_iters=num_iters, viol_tol=viol_tol,
-                                             tol=tol, seed=sd, seed_stride=stride, first_index=first_index, want_x=False)
+                                             tol=tol, seed=sd, seed_stride=stride, first_index=first_index, want_x=False, cons=self.cons)
         self.x = out['best_x']
         self.best_index = out['best_index']
         self.population_f, self.population_v = out['f0'], out['maxviol']

@@ -1758,11 +1758,12 @@ int qcqpmi_cd_stream_run(qcqpmi_ctx *c, int64_t K, int64_t R, int generate, int 
 // ---- B small problems (n <= 64) that share the context's separable constraints, R restarts each, in ONE launch of cd_small_kernel
 // (csrc/cd_small.hip).  Works in a buffer of its own: the resident population, its evaluation and its status codes are not touched,
 // whether the call succeeds or is refused.
-int qcqpmi_cd_small_batch_run(qcqpmi_ctx *c, int64_t B, const double *P0s, const double *q0s, const double *r0s, int64_t R, int generate,
-                              const double *X0, int phase1, int64_t num_iters, double viol_tol, double tol, uint64_t seed,
-                              uint64_t seed_stride, uint64_t first_index, double select_tol, int64_t *sweeps1, int64_t *sweeps2,
-                              int64_t *visits2, int64_t *accepted2, uint8_t *ran_phase2, int *status1, int *status2, double *f0,
-                              double *maxviol, double *X, int64_t *best_index, double *best_f0, double *best_maxviol, double *best_x) {
+// cons == nullptr: the context's coefficients; else [B][m][3], per_problem set: qcqpmi_cd_small_batch_run_pc
+static int cd_small_batch(qcqpmi_ctx *c, bool per_problem, const double *cons, int64_t B, const double *P0s, const double *q0s, const double *r0s,
+                          int64_t R, int generate, const double *X0, int phase1, int64_t num_iters, double viol_tol, double tol, uint64_t seed,
+                          uint64_t seed_stride, uint64_t first_index, double select_tol, int64_t *sweeps1, int64_t *sweeps2,
+                          int64_t *visits2, int64_t *accepted2, uint8_t *ran_phase2, int *status1, int *status2, double *f0,
+                          double *maxviol, double *X, int64_t *best_index, double *best_f0, double *best_maxviol, double *best_x) {
     int rc = check_ready(c, false);
     if (rc) return rc;
     if (!c->sep) return fail(c, QCQPMI_EUNSUPPORTED, "cd_small_batch_run: the constraints are not separable (a constraint couples coordinates, or a coordinate carries more than 4)");
@@ -1770,6 +1771,18 @@ int qcqpmi_cd_small_batch_run(qcqpmi_ctx *c, int64_t B, const double *P0s, const
     if (B < 1 || R < 1 || num_iters < 0 || !(tol > 0.0) || !P0s || !q0s || !r0s || (!generate && !X0))
         return fail(c, QCQPMI_EINVAL, "cd_small_batch_run: bad B / R / num_iters / tol, or a missing input array");
     if (B >= (1LL << 30) || R >= (1LL << 30) || B * R >= (1LL << 30)) return fail(c, QCQPMI_EINVAL, "cd_small_batch_run: B R = %lld restarts, at most 2^30 - 1 per call", (long long)(B * R));
+    const int64_t m = c->m;
+    if (per_problem) {
+        if (!cons) return fail(c, QCQPMI_EINVAL, "cd_small_batch_run_pc: missing cons (B x m x 3 coefficients)");
+        for (int64_t k = 0; k < B * m; k++) {
+            const double p = cons[3 * k], q = cons[3 * k + 1], r = cons[3 * k + 2];
+            if (!std::isfinite(p) || !std::isfinite(q) || !std::isfinite(r))
+                return fail(c, QCQPMI_EINVAL, "cd_small_batch_run_pc: constraint %lld of problem %lld holds a coefficient that is not finite", (long long)(k % m + 1), (long long)(k / m));
+            if (p == 0.0 && q == 0.0)
+                return fail(c, QCQPMI_EINVAL, "cd_small_batch_run_pc: constraint %lld of problem %lld has p == 0 and q == 0: it touches no coordinate", (long long)(k % m + 1), (long long)(k / m));
+        }
+        if (m == 0) cons = nullptr;       // nothing to stage: the shared kernels
+    }
     HIPCHK(c, hipSetDevice(c->device));
     const int64_t n = c->n, T = B * R;
     // ---- carve the work buffer (every piece 256-byte aligned)
@@ -1780,6 +1793,7 @@ int qcqpmi_cd_small_batch_run(qcqpmi_ctx *c, int64_t B, const double *P0s, const
     const size_t oout = take((size_t)T * 57);      // 4 x int64, 2 x double, 2 x int, 1 x uint8 per restart, array after array
     const size_t oticket = take(2 * sizeof(int));
     const size_t obi = take((size_t)B * 2 * sizeof(int64_t)), obk = take((size_t)B * 2 * sizeof(double)), obx = take((size_t)B * n * 8);
+    const size_t ocons = take(cons ? (size_t)B * m * 24 : 0);
     if (off > c->sb_work_cap) {
         HIPCHK(c, spin_sync(c->stream));
         if (c->sb_work) (void)hipFree(c->sb_work);
@@ -1792,11 +1806,13 @@ int qcqpmi_cd_small_batch_run(qcqpmi_ctx *c, int64_t B, const double *P0s, const
     HIPCHK(c, hipMemcpyAsync(w + oq, q0s, (size_t)B * n * 8, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(w + or0, r0s, (size_t)B * 8, hipMemcpyHostToDevice, c->stream));
     if (!generate) HIPCHK(c, hipMemcpyAsync(w + oX0, X0, (size_t)T * n * 8, hipMemcpyHostToDevice, c->stream));
+    if (cons) HIPCHK(c, hipMemcpyAsync(w + ocons, cons, (size_t)B * m * 24, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemsetAsync(w + oticket, 0, 2 * sizeof(int), c->stream));
     CdSmallArgs a;
     a.P = c->dp; a.B = B; a.R = R;
     a.P0s = (const double *)(w + oP); a.q0s = (const double *)(w + oq); a.r0s = (const double *)(w + or0);
     a.X0 = generate ? nullptr : (const double *)(w + oX0);
+    a.cons = cons ? (const double *)(w + ocons) : nullptr;
     a.generate = generate ? 1 : 0; a.phase1 = phase1 ? 1 : 0; a.num_iters = num_iters; a.viol_tol = viol_tol; a.tol = tol;
     a.seed = seed; a.seed_stride = seed_stride; a.first_index = first_index;
     a.ticket = (int *)(w + oticket);
@@ -1807,7 +1823,7 @@ int qcqpmi_cd_small_batch_run(qcqpmi_ctx *c, int64_t B, const double *P0s, const
     a.X = (double *)(w + oX);
     // tickets: whole problems when there are enough of them to fill the device, else chunks of at least 4 restarts (one per wave)
     const int maxc = c->maxc <= 1 ? 1 : 4;
-    int wgs = cd_small_workgroups(n, maxc, B * R, c->device);
+    int wgs = cd_small_workgroups(n, maxc, cons ? m : 0, B * R, c->device);
     if (wgs < 1) return fail(c, QCQPMI_EHIP, "cd_small_batch_run: occupancy query failed: %s", hipGetErrorString((hipError_t)(-wgs)));
     int64_t chunks = B >= wgs ? 1 : (wgs + B - 1) / B;
     if (chunks > (R + 3) / 4) chunks = (R + 3) / 4;
@@ -1819,7 +1835,7 @@ int qcqpmi_cd_small_batch_run(qcqpmi_ctx *c, int64_t B, const double *P0s, const
     (void)hipEventRecord(c->timers[2].end, c->stream);
     c->timers[2].valid = true;
     if (qe != hipSuccess) return fail(c, QCQPMI_EHIP, "cd_small_batch_run: %s", hipGetErrorString(qe));
-    c->last_cd2_kernel = cd_small_name(maxc);
+    c->last_cd2_kernel = cd_small_name(maxc, cons != nullptr);
     const bool want_best = best_index || best_f0 || best_maxviol || best_x;
     if (want_best) {       // QCQPForm.better folded over every problem's restarts, ties -> lowest index: one workgroup per problem
         hipLaunchKernelGGL(select_best_kernel, dim3((unsigned)B), dim3(1024), 0, c->stream, (const double *)a.f0, (const double *)a.maxviol, R,
@@ -1865,13 +1881,37 @@ int qcqpmi_cd_small_batch_run(qcqpmi_ctx *c, int64_t B, const double *P0s, const
     return 0;
 }
 
+int qcqpmi_cd_small_batch_run(qcqpmi_ctx *c, int64_t B, const double *P0s, const double *q0s, const double *r0s, int64_t R, int generate,
+                              const double *X0, int phase1, int64_t num_iters, double viol_tol, double tol, uint64_t seed,
+                              uint64_t seed_stride, uint64_t first_index, double select_tol, int64_t *sweeps1, int64_t *sweeps2,
+                              int64_t *visits2, int64_t *accepted2, uint8_t *ran_phase2, int *status1, int *status2, double *f0,
+                              double *maxviol, double *X, int64_t *best_index, double *best_f0, double *best_maxviol, double *best_x) {
+    return cd_small_batch(c, false, nullptr, B, P0s, q0s, r0s, R, generate, X0, phase1, num_iters, viol_tol, tol, seed, seed_stride, first_index,
+                          select_tol, sweeps1, sweeps2, visits2, accepted2, ran_phase2, status1, status2, f0, maxviol, X, best_index, best_f0,
+                          best_maxviol, best_x);
+}
+
+// ---- the same launch with PER-PROBLEM constraint coefficients: the context fixes the structure (which coordinate constraint k touches,
+// its relop), cons [B][m][3] holds (p, q, r) of constraint k of problem b (cd_small_kernel<MAXC, pc> stages them in LDS with P0_b).
+int qcqpmi_cd_small_batch_run_pc(qcqpmi_ctx *c, int64_t B, const double *P0s, const double *q0s, const double *r0s, const double *cons,
+                                 int64_t R, int generate, const double *X0, int phase1, int64_t num_iters, double viol_tol, double tol,
+                                 uint64_t seed, uint64_t seed_stride, uint64_t first_index, double select_tol, int64_t *sweeps1,
+                                 int64_t *sweeps2, int64_t *visits2, int64_t *accepted2, uint8_t *ran_phase2, int *status1, int *status2,
+                                 double *f0, double *maxviol, double *X, int64_t *best_index, double *best_f0, double *best_maxviol,
+                                 double *best_x) {
+    return cd_small_batch(c, true, cons, B, P0s, q0s, r0s, R, generate, X0, phase1, num_iters, viol_tol, tol, seed, seed_stride, first_index,
+                          select_tol, sweeps1, sweeps2, visits2, accepted2, ran_phase2, status1, status2, f0, maxviol, X, best_index, best_f0,
+                          best_maxviol, best_x);
+}
+
 // ---- suggest(SDR) for B small problems (n <= 64) of the unit-diagonal family that share the context's constraints x_i^2 == d_i: the
 // relaxation (mixing method), its multipliers and S samples per problem in ONE launch of sdr_small_kernel (csrc/sdr_small.hip).  Works
 // in a buffer of its own: the resident population, its evaluation, its status codes and qcqpmi_last_cd_kernel are not touched, whether
 // the call succeeds or is refused.
-int qcqpmi_sdr_small_batch(qcqpmi_ctx *c, int64_t B, const double *P0s, const double *q0s, const double *r0s, int64_t S, int max_sweeps,
-                           double tol, uint64_t seed, uint64_t seed_stride, uint64_t first_index, const double *V0s, double *V,
-                           double *primal, double *y, int64_t *sweeps, double *X) {
+// ds == nullptr: the context's d for every problem; else [B][n], per_problem set: qcqpmi_sdr_small_batch_pc
+static int sdr_small_batch(qcqpmi_ctx *c, bool per_problem, const double *ds, int64_t B, const double *P0s, const double *q0s, const double *r0s,
+                           int64_t S, int max_sweeps, double tol, uint64_t seed, uint64_t seed_stride, uint64_t first_index, const double *V0s,
+                           double *V, double *primal, double *y, int64_t *sweeps, double *X) {
     int rc = check_ready(c, false);
     if (rc) return rc;
     if (c->n > SDR_SMALL_MAXN) return fail(c, QCQPMI_EUNSUPPORTED, "sdr_small_batch: n = %lld, the small-problem kernel takes n <= %d", (long long)c->n, SDR_SMALL_MAXN);
@@ -1879,12 +1919,19 @@ int qcqpmi_sdr_small_batch(qcqpmi_ctx *c, int64_t B, const double *P0s, const do
     if (B < 1 || S < 0 || max_sweeps < 0 || !(tol >= 0.0) || !P0s || !q0s || !r0s)
         return fail(c, QCQPMI_EINVAL, "sdr_small_batch: bad B / S / max_sweeps / tol, or a missing input array");
     if (B >= (1LL << 30) || S >= (1LL << 30) || B * (S > 0 ? S : 1) >= (1LL << 30)) return fail(c, QCQPMI_EINVAL, "sdr_small_batch: B = %lld problems with S = %lld samples, at most 2^30 - 1 per call", (long long)B, (long long)S);
-    HIPCHK(c, hipSetDevice(c->device));
     const int64_t n = c->n, N = n + 1;
+    if (per_problem) {
+        if (!ds) return fail(c, QCQPMI_EINVAL, "sdr_small_batch_pc: missing ds (B x n)");
+        for (int64_t k = 0; k < B * n; k++)
+            if (!(ds[k] > 0.0) || !std::isfinite(ds[k]))
+                return fail(c, QCQPMI_EINVAL, "sdr_small_batch_pc: d of coordinate %lld of problem %lld is not a positive finite number", (long long)(k % n), (long long)(k / n));
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    const int64_t ns = ds ? B * n : n;      // entries of s
     // ---- carve the work buffer (every piece 256-byte aligned)
     size_t off = 0;
     auto take = [&off](size_t bytes) { const size_t o = off; off += (bytes + 255) / 256 * 256; return o; };
-    const size_t oP = take((size_t)B * n * n * 8), oq = take((size_t)B * n * 8), or0 = take((size_t)B * 8), os = take((size_t)n * 8);
+    const size_t oP = take((size_t)B * n * n * 8), oq = take((size_t)B * n * 8), or0 = take((size_t)B * 8), os = take((size_t)ns * 8);
     const size_t oV0 = take(V0s ? (size_t)B * N * SDR_SMALL_K * 8 : 0), oV = take((size_t)B * N * SDR_SMALL_K * 8);
     const size_t opr = take((size_t)B * 8), oy = take((size_t)B * N * 8), osw = take((size_t)B * 8), oX = take((size_t)B * S * n * 8);
     const size_t oticket = take(2 * sizeof(int));
@@ -1896,18 +1943,18 @@ int qcqpmi_sdr_small_batch(qcqpmi_ctx *c, int64_t B, const double *P0s, const do
         c->ss_work_cap = off;
     }
     char *w = c->ss_work;
-    std::vector<double> sv((size_t)n);
-    for (int64_t i = 0; i < n; i++) sv[(size_t)i] = sqrt(c->unit_d[(size_t)i]);
+    std::vector<double> sv((size_t)ns);
+    for (int64_t i = 0; i < ns; i++) sv[(size_t)i] = sqrt(ds ? ds[i] : c->unit_d[(size_t)i]);
     HIPCHK(c, hipMemcpyAsync(w + oP, P0s, (size_t)B * n * n * 8, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(w + oq, q0s, (size_t)B * n * 8, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(w + or0, r0s, (size_t)B * 8, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(w + os, sv.data(), (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(w + os, sv.data(), (size_t)ns * 8, hipMemcpyHostToDevice, c->stream));
     if (V0s) HIPCHK(c, hipMemcpyAsync(w + oV0, V0s, (size_t)B * N * SDR_SMALL_K * 8, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemsetAsync(w + oticket, 0, 2 * sizeof(int), c->stream));
     HIPCHK(c, spin_sync(c->stream));      // sv goes out of scope; the pageable copies above have been staged
     SdrSmallArgs a;
     a.n = (int)n; a.B = B; a.S = S;
-    a.s = (const double *)(w + os); a.P0s = (const double *)(w + oP); a.q0s = (const double *)(w + oq); a.r0s = (const double *)(w + or0);
+    a.s = (const double *)(w + os); a.s_stride = ds ? n : 0; a.P0s = (const double *)(w + oP); a.q0s = (const double *)(w + oq); a.r0s = (const double *)(w + or0);
     a.V0s = V0s ? (const double *)(w + oV0) : nullptr;
     a.max_sweeps = max_sweeps; a.tol = tol; a.seed = seed; a.seed_stride = seed_stride; a.first_index = first_index;
     a.ticket = (int *)(w + oticket);
@@ -1927,6 +1974,19 @@ int qcqpmi_sdr_small_batch(qcqpmi_ctx *c, int64_t B, const double *P0s, const do
     if (X && S > 0) HIPCHK(c, hipMemcpyAsync(X, a.X, (size_t)B * S * n * 8, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, spin_sync(c->stream));
     return 0;
+}
+
+int qcqpmi_sdr_small_batch(qcqpmi_ctx *c, int64_t B, const double *P0s, const double *q0s, const double *r0s, int64_t S, int max_sweeps,
+                           double tol, uint64_t seed, uint64_t seed_stride, uint64_t first_index, const double *V0s, double *V,
+                           double *primal, double *y, int64_t *sweeps, double *X) {
+    return sdr_small_batch(c, false, nullptr, B, P0s, q0s, r0s, S, max_sweeps, tol, seed, seed_stride, first_index, V0s, V, primal, y, sweeps, X);
+}
+
+// ---- the same launch with PER-PROBLEM d: ds [B][n] replaces the context's d problem by problem (the context must still be of the family)
+int qcqpmi_sdr_small_batch_pc(qcqpmi_ctx *c, int64_t B, const double *P0s, const double *q0s, const double *r0s, const double *ds, int64_t S,
+                              int max_sweeps, double tol, uint64_t seed, uint64_t seed_stride, uint64_t first_index, const double *V0s,
+                              double *V, double *primal, double *y, int64_t *sweeps, double *X) {
+    return sdr_small_batch(c, true, ds, B, P0s, q0s, r0s, S, max_sweeps, tol, seed, seed_stride, first_index, V0s, V, primal, y, sweeps, X);
 }
 
 int qcqpmi_cd_stream_reserve(qcqpmi_ctx *c, int64_t K, int64_t R) {

@@ -7,6 +7,11 @@
 // a context that holds the constraints and objective b: the keyed draws go by the GLOBAL restart index first_index + r, so a
 // result depends on nothing but (objective b, seed of b, global index) -- not on B, the neighbours, the workgroups or the order
 // in which the work is dealt out.
+//
+// Per-problem constraint coefficients (qcqpmi_cd_small_batch_run_pc): the context fixes the STRUCTURE of the lists
+// (cptr, crel, maxc -- which coordinate a constraint touches, its relop) and problem b brings (p, q, r) of every constraint in
+// cons [B][m][3]; the ticket's workgroup stages them in LDS beside P0_b.  Restart (b, r) is then bit for bit the restart of the shared
+// call with B = 1 on a context created from problem b's own functions.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -35,13 +40,15 @@ struct CdSmallArgs {
     int *status1, *status2;
     double *f0, *maxviol;
     double *X;                   // [B][R][n] final points
+    const double *cons;          // per-problem constraint coefficients [B][m][3] = (p, q, r) in CONSTRAINT order, or nullptr: P's
 };
 
-size_t cd_small_lds_bytes(int64_t n);
+// pc_entries: 0, or the m list entries whose (p, q, r) the per-problem-constraint kernels stage beside P0_b and q0_b
+size_t cd_small_lds_bytes(int64_t n, int64_t pc_entries);
 // workgroups of the launch (persistent: at most what the device holds at once), or < 0: -hipError_t
-int cd_small_workgroups(int64_t n, int maxc, int64_t tickets, int device);
-int cd_small_launch(const CdSmallArgs &a, int maxc, int wgs, hipStream_t st);
-const char *cd_small_name(int maxc);
+int cd_small_workgroups(int64_t n, int maxc, int64_t pc_entries, int64_t tickets, int device);
+int cd_small_launch(const CdSmallArgs &a, int maxc, int wgs, hipStream_t st);      // a.cons != nullptr: the <MAXC, pc> kernels
+const char *cd_small_name(int maxc, bool pc);
 // the winners' points: out[b][0..n) = X[b][idx[2 b]][0..n)  (idx as select_best_kernel leaves it; < 0: row left as it is)
 int cd_small_gather_launch(const double *X, int64_t n, int64_t R, int64_t B, const int64_t *idx, double *out, hipStream_t st);
 

@@ -1,5 +1,6 @@
 // cd_small_kernel -- improve_coord_descent (qcqp.py:181-192) for a batch of SMALL problems (n <= 64) that share their separable
-// constraints and differ in their objective, R restarts each, inside one persistent launch (cd_small.h).
+// constraints and differ in their objective, R restarts each, inside one persistent launch (cd_small.h); in the per-problem-constraint
+// mode (cd_small_kernel<MAXC, true>) they share the STRUCTURE of the lists and problem b's coefficients are staged with its objective.
 //
 // Layout.  ONE WAVEFRONT PER (problem, restart), LANE = COORDINATE.  A workgroup of four waves draws a ticket -- a problem and a
 // chunk of its restarts -- from a global counter (an ordinary atomic add), stages P0_b (n x n doubles, at most 32 KB) and q0_b in
@@ -59,7 +60,9 @@ __device__ inline double sm_refresh(const double *Ps, const double *qs, double r
     return acc + r0;
 }
 
-template <int MAXC>
+// a.P: the constraint lists the restart reads -- the context's, or the view of problem b's staged coefficients (cd_small_kernel).
+// PC only names the caller: every kernel keeps an instance of its own, inlined as the single-caller function it was.
+template <int MAXC, bool PC>
 __device__ inline void sm_restart(const CdSmallArgs &a, const double *Ps, const double *qs, int64_t b, int64_t r, int lane) {
     const DevProblem &P = a.P;
     const int n = (int)P.n;
@@ -157,12 +160,19 @@ __device__ inline void sm_restart(const CdSmallArgs &a, const double *Ps, const 
     if (on) a.X[o * n + lane] = x;
 }
 
-template <int MAXC>
+// PC: per-problem constraint coefficients (cd_small.h).  The ticket's workgroup stages problem b's (p, q, r) of every list entry in
+// LDS beside P0_b and q0_b -- entry e of the context's lists (cptr order) is constraint cidx[e] of a.cons [B][m][3] -- and its waves
+// read their lists through the kernel's copy of the context's DevProblem, whose cp / cq / cr point at that image: cptr and crel stay
+// the context's, and the visit arithmetic is the one copy above.
+template <int MAXC, bool PC = false>
 __global__ __launch_bounds__(256) void cd_small_kernel(CdSmallArgs a) {
     extern __shared__ double sm_lds[];
-    const int n = (int)a.P.n;
+    const int n = (int)a.P.n, m = PC ? (int)a.P.m : 0;
     double *Ps = sm_lds, *qs = sm_lds + n * n;
-    int *ctl = (int *)(qs + n);      // [0] the workgroup's ticket, [1] next restart of its chunk
+    double *cs = qs + n;             // PC: [3][m] the staged coefficients, p then q then r
+    int *ctl = (int *)(cs + 3 * m);  // [0] the workgroup's ticket, [1] next restart of its chunk
+    const int *cidx = a.P.cidx;
+    if constexpr (PC) { a.P.cp = cs; a.P.cq = cs + m; a.P.cr = cs + 2 * m; }      // the view: cptr and crel stay the context's
     const int tid = threadIdx.x, lane = tid & 63;
     const int64_t tickets = a.B * a.chunks;
     for (;;) {
@@ -179,6 +189,13 @@ __global__ __launch_bounds__(256) void cd_small_kernel(CdSmallArgs a) {
         const double *Pg = a.P0s + b * n * n;
         for (int e = tid; e < n * n; e += 256) Ps[e] = Pg[e];
         if (tid < n) qs[tid] = a.q0s[b * n + tid];
+        if constexpr (PC) {
+            const double *cg = a.cons + b * m * 3;
+            for (int e = tid; e < m; e += 256) {
+                const double *ck = cg + (cidx[e] - 1) * 3;
+                cs[e] = ck[0]; cs[m + e] = ck[1]; cs[2 * m + e] = ck[2];
+            }
+        }
         __syncthreads();
         // the visits read column i as row i: a matrix that is not symmetric (or holds a NaN) makes the call fail
         bool asym = false;
@@ -192,7 +209,7 @@ __global__ __launch_bounds__(256) void cd_small_kernel(CdSmallArgs a) {
             if (lane == 0) k = atomicAdd(&ctl[1], 1);
             k = __builtin_amdgcn_readfirstlane(k);
             if (r_lo + k >= r_hi) break;
-            sm_restart<MAXC>(a, Ps, qs, b, r_lo + k, lane);
+            sm_restart<MAXC, PC>(a, Ps, qs, b, r_lo + k, lane);
         }
     }
 }
@@ -206,15 +223,19 @@ __global__ void cd_small_gather_kernel(const double *__restrict__ X, int64_t n, 
 
 }  // namespace
 
-size_t cd_small_lds_bytes(int64_t n) { return (size_t)(n * n + n) * sizeof(double) + 2 * sizeof(int); }
+size_t cd_small_lds_bytes(int64_t n, int64_t pc_entries) { return (size_t)(n * n + n + 3 * pc_entries) * sizeof(double) + 2 * sizeof(int); }
 
-int cd_small_workgroups(int64_t n, int maxc, int64_t tickets, int device) {
+int cd_small_workgroups(int64_t n, int maxc, int64_t pc_entries, int64_t tickets, int device) {
     int cus = 0, per = 0;
     hipError_t e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device);
     if (e != hipSuccess) return -(int)e;
-    const size_t lds = cd_small_lds_bytes(n);
-    e = (maxc <= 1) ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, cd_small_kernel<1>, 256, lds)
-                    : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, cd_small_kernel<4>, 256, lds);
+    const size_t lds = cd_small_lds_bytes(n, pc_entries);
+    if (pc_entries > 0)
+        e = (maxc <= 1) ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, cd_small_kernel<1, true>, 256, lds)
+                        : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, cd_small_kernel<4, true>, 256, lds);
+    else
+        e = (maxc <= 1) ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, cd_small_kernel<1>, 256, lds)
+                        : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, cd_small_kernel<4>, 256, lds);
     if (e != hipSuccess) return -(int)e;
     if (per < 1) per = 1;
     const int64_t cap = (int64_t)cus * per;
@@ -222,13 +243,19 @@ int cd_small_workgroups(int64_t n, int maxc, int64_t tickets, int device) {
 }
 
 int cd_small_launch(const CdSmallArgs &a, int maxc, int wgs, hipStream_t st) {
-    const size_t lds = cd_small_lds_bytes(a.P.n);
-    if (maxc <= 1) hipLaunchKernelGGL(cd_small_kernel<1>, dim3((unsigned)wgs), dim3(256), lds, st, a);
+    const bool pc = a.cons != nullptr;
+    const size_t lds = cd_small_lds_bytes(a.P.n, pc ? a.P.m : 0);
+    if (pc && maxc <= 1) hipLaunchKernelGGL((cd_small_kernel<1, true>), dim3((unsigned)wgs), dim3(256), lds, st, a);
+    else if (pc) hipLaunchKernelGGL((cd_small_kernel<4, true>), dim3((unsigned)wgs), dim3(256), lds, st, a);
+    else if (maxc <= 1) hipLaunchKernelGGL(cd_small_kernel<1>, dim3((unsigned)wgs), dim3(256), lds, st, a);
     else hipLaunchKernelGGL(cd_small_kernel<4>, dim3((unsigned)wgs), dim3(256), lds, st, a);
     return (int)hipGetLastError();
 }
 
-const char *cd_small_name(int maxc) { return maxc <= 1 ? "cd_small_kernel<1>" : "cd_small_kernel<4>"; }
+const char *cd_small_name(int maxc, bool pc) {
+    if (pc) return maxc <= 1 ? "cd_small_kernel<1,pc>" : "cd_small_kernel<4,pc>";
+    return maxc <= 1 ? "cd_small_kernel<1>" : "cd_small_kernel<4>";
+}
 
 int cd_small_gather_launch(const double *X, int64_t n, int64_t R, int64_t B, const int64_t *idx, double *out, hipStream_t st) {
     hipLaunchKernelGGL(cd_small_gather_kernel, dim3((unsigned)B), dim3(64), 0, st, X, n, R, idx, out);

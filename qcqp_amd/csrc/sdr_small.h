@@ -34,7 +34,8 @@ constexpr int SDR_SMALL_VSTR = 65;       // row stride of V in LDS (doubles): V[
 struct SdrSmallArgs {
     int n;                       // variables; N = n + 1
     int64_t B, S;
-    const double *s;             // [n] sqrt(d)
+    const double *s;             // sqrt(d): [n] shared by the problems (s_stride = 0), or [B][n] (s_stride = n): problem b reads s + b s_stride
+    int64_t s_stride;
     const double *P0s;           // [B][n][n] symmetric
     const double *q0s;           // [B][n]
     const double *r0s;           // [B]

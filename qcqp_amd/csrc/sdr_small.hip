@@ -2,7 +2,7 @@
 // objective: relaxation by the mixing method, multipliers and samples of every problem inside one persistent launch (sdr_small.h).
 //
 // Layout.  ONE WAVEFRONT PER PROBLEM, one wavefront per workgroup: a wave draws a problem from a global counter (an ordinary atomic
-// add), builds C_b (N x N doubles) in its LDS from P0_b, q0_b, r0_b and s = sqrt(d), keeps V_b (N rows of 64, row stride 65
+// add), builds C_b (N x N doubles) in its LDS from P0_b, q0_b, r0_b and s = sqrt(d) (the shared one, or problem b's row of a [B][n] array), keeps V_b (N rows of 64, row stride 65
 // doubles) beside it and never waits for another wave: no flags, no spinning; the barriers below are those of a one-wave workgroup
 // and order the wave's own LDS traffic where lanes read what other lanes wrote.
 //   sweeps      LANE = COMPONENT k of V.  g_i[k] = sum_{j != i} C_ij V[j][k]: C_ij is one address for the whole wave (a broadcast
@@ -47,7 +47,7 @@ __device__ inline void ss_problem(const SdrSmallArgs &a, double *Vs, double *Cs,
     __syncthreads();             // the wave is done with the LDS image of its previous problem
 
     // ---- C_b (sdr.lifted_cost, the same products); a matrix that is not symmetric (or holds a NaN) makes the call fail
-    const double *Pg = a.P0s + b * n * n, *qg = a.q0s + b * n;
+    const double *Pg = a.P0s + b * n * n, *qg = a.q0s + b * n, *sv = a.s + b * a.s_stride;
     bool asym = false;
     for (int e = lane; e < N * N; e += 64) {
         const int i = e / N, j = e - i * N;
@@ -55,11 +55,11 @@ __device__ inline void ss_problem(const SdrSmallArgs &a, double *Vs, double *Cs,
         if (i < n && j < n) {
             const double p = Pg[i * n + j];
             asym = asym || (j > i && !(p == Pg[j * n + i]));
-            c = p * (a.s[i] * a.s[j]);
+            c = p * (sv[i] * sv[j]);
         } else if (i < n) {
-            c = 0.5 * qg[i] * a.s[i];
+            c = 0.5 * qg[i] * sv[i];
         } else if (j < n) {
-            c = 0.5 * qg[j] * a.s[j];
+            c = 0.5 * qg[j] * sv[j];
         } else {
             c = a.r0s[b];
         }
@@ -121,7 +121,7 @@ __device__ inline void ss_problem(const SdrSmallArgs &a, double *Vs, double *Cs,
     if (a.S > 0) {
         const int il = lane < n ? lane : 0;
         const double *Vi = Vs + il * SDR_SMALL_VSTR, *U = Vs + n * SDR_SMALL_VSTR;
-        const double u = U[lane], si = a.s[il];
+        const double u = U[lane], si = sv[il];
         double mu = 0.0;
         for (int k = 0; k < SDR_SMALL_K; k++) mu = __builtin_fma(Vi[k], U[k], mu);
         for (int64_t sg = 0; sg < a.S; sg++) {

@@ -213,13 +213,16 @@ class Engine(object):
         return out
 
     def cd_small_batch_run(self, P0s, q0s, r0s, R, X0=None, phase1=True, num_iters=1000, viol_tol=1e-2, tol=1e-4, seed=0,
-                           seed_stride=1, first_index=0, select_tol=1e-4, want_x=True):
+                           seed_stride=1, first_index=0, select_tol=1e-4, want_x=True, cons=None):
         """B small problems (n <= 64) that share this context's separable constraints and differ in their objective -- P0s (B, n, n)
         symmetric, q0s (B, n), r0s (B,) -- with R restarts each in ONE launch (qcqpmi_cd_small_batch_run).  Restart (b, r) is restart r
         of randn(R, seed + b seed_stride, first_index) + cd_run(seed + b seed_stride, first_index) on a context that holds objective b.
         X0 (B, R, n): start points instead of the keyed normals.  Returns the dictionary of cd_run with arrays of shape (B, R), X
         (B, R, n) if want_x, and per problem best_index / best_f0 / best_maxviol (B,) and best_x (B, n).  The resident population is
-        not touched."""
+        not touched.
+        cons (B, m, 3): PER-PROBLEM constraint coefficients (qcqpmi_cd_small_batch_run_pc) -- (p, q, r) of constraint k of problem b
+        on the coordinate and with the relop constraint k has in this context; restart (b, r) is then bit for bit the restart of a
+        batch of one on a context built from problem b's own functions.  None: the context's constraints for every problem."""
         P0s = np.ascontiguousarray(P0s, dtype=np.float64)
         q0s = np.ascontiguousarray(q0s, dtype=np.float64)
         r0s = np.ascontiguousarray(r0s, dtype=np.float64).ravel()
@@ -230,19 +233,25 @@ class Engine(object):
             X0 = np.ascontiguousarray(X0, dtype=np.float64)
             if X0.shape != (B, R, n):
                 raise ValueError('cd_small_batch_run: expected X0 of shape (B, R, n)')
+        if cons is not None:
+            cons = np.ascontiguousarray(cons, dtype=np.float64)
+            if cons.shape != (B, self.m, 3):
+                raise ValueError('cd_small_batch_run: expected cons of shape (B, m, 3) with m = %d' % self.m)
         T = B * R
         out = dict(sweeps1=np.zeros(T, dtype=np.int64), sweeps2=np.zeros(T, dtype=np.int64), visits2=np.zeros(T, dtype=np.int64),
                    accepted2=np.zeros(T, dtype=np.int64), ran_phase2=np.zeros(T, dtype=np.uint8), status1=np.zeros(T, dtype=np.int32),
                    status2=np.zeros(T, dtype=np.int32), f0=np.empty(T), maxviol=np.empty(T), X=np.empty((B, R, n)) if want_x else None,
                    best_index=np.zeros(B, dtype=np.int64), best_f0=np.empty(B), best_maxviol=np.empty(B), best_x=np.zeros((B, n)))
         c_intp = C.POINTER(C.c_int)
-        self._chk(self.L.qcqpmi_cd_small_batch_run(self.h, B, _dp(P0s), _dp(q0s), _dp(r0s), R, 0 if X0 is not None else 1, _dp(X0),
-                                                   int(bool(phase1)), int(num_iters), float(viol_tol), float(tol), int(seed), int(seed_stride),
-                                                   int(first_index), float(select_tol), _ip(out['sweeps1']), _ip(out['sweeps2']),
-                                                   _ip(out['visits2']), _ip(out['accepted2']), _bp(out['ran_phase2']),
-                                                   out['status1'].ctypes.data_as(c_intp), out['status2'].ctypes.data_as(c_intp),
-                                                   _dp(out['f0']), _dp(out['maxviol']), _dp(out['X']), _ip(out['best_index']),
-                                                   _dp(out['best_f0']), _dp(out['best_maxviol']), _dp(out['best_x'])))
+        tail = (R, 0 if X0 is not None else 1, _dp(X0), int(bool(phase1)), int(num_iters), float(viol_tol), float(tol), int(seed),
+                int(seed_stride), int(first_index), float(select_tol), _ip(out['sweeps1']), _ip(out['sweeps2']), _ip(out['visits2']),
+                _ip(out['accepted2']), _bp(out['ran_phase2']), out['status1'].ctypes.data_as(c_intp), out['status2'].ctypes.data_as(c_intp),
+                _dp(out['f0']), _dp(out['maxviol']), _dp(out['X']), _ip(out['best_index']), _dp(out['best_f0']), _dp(out['best_maxviol']),
+                _dp(out['best_x']))
+        if cons is None:
+            self._chk(self.L.qcqpmi_cd_small_batch_run(self.h, B, _dp(P0s), _dp(q0s), _dp(r0s), *tail))
+        else:
+            self._chk(self.L.qcqpmi_cd_small_batch_run_pc(self.h, B, _dp(P0s), _dp(q0s), _dp(r0s), _dp(cons), *tail))
         for k in ('sweeps1', 'sweeps2', 'visits2', 'accepted2', 'ran_phase2', 'status1', 'status2', 'f0', 'maxviol'):
             out[k] = out[k].reshape(B, R)
         return out
@@ -425,13 +434,15 @@ class Engine(object):
         return V, hist[:sw.value + 2], sw.value
 
     def sdr_small_batch(self, P0s, q0s, r0s, S, max_sweeps=5000, tol=1e-11, seed=0, seed_stride=1, first_index=0, V0s=None,
-                        want_V=True):
+                        want_V=True, ds=None):
         """suggest(SDR) for B small problems (n <= 64) that share this context's constraints x_i^2 == d_i and differ in their objective
         -- P0s (B, n, n) symmetric, q0s (B, n), r0s (B,) -- in ONE launch (qcqpmi_sdr_small_batch): the relaxation of every problem by
         the mixing method (start: keyed normal rows of seed + b seed_stride, or V0s (B, n + 1, 64)), its multipliers and S >= 0
         samples x = s o (V_n u + V_n (xi - u (u . xi))), xi = the keyed normals (seed + b seed_stride, first_index + sample).
         Returns a dictionary: V (B, n + 1, 64) if want_V, primal (B,), y (B, n + 1), sweeps (B,), X (B, S, n).  The resident
-        population is not touched."""
+        population is not touched.
+        ds (B, n), every entry > 0: PER-PROBLEM d (qcqpmi_sdr_small_batch_pc) -- problem b has the constraints x_i^2 == ds[b, i]
+        instead of the context's; None: the context's d for every problem."""
         P0s = np.ascontiguousarray(P0s, dtype=np.float64)
         q0s = np.ascontiguousarray(q0s, dtype=np.float64)
         r0s = np.ascontiguousarray(r0s, dtype=np.float64).ravel()
@@ -444,9 +455,15 @@ class Engine(object):
                 raise ValueError('sdr_small_batch: expected V0s of shape (B, n + 1, 64)')
         out = dict(V=np.empty((B, n + 1, 64)) if want_V else None, primal=np.empty(B), y=np.empty((B, n + 1)),
                    sweeps=np.zeros(B, dtype=np.int64), X=np.empty((B, max(S, 0), n)))
-        self._chk(self.L.qcqpmi_sdr_small_batch(self.h, B, _dp(P0s), _dp(q0s), _dp(r0s), S, int(max_sweeps), float(tol), int(seed),
-                                                int(seed_stride), int(first_index), _dp(V0s), _dp(out['V']), _dp(out['primal']),
-                                                _dp(out['y']), _ip(out['sweeps']), _dp(out['X']) if S > 0 else None))
+        tail = (S, int(max_sweeps), float(tol), int(seed), int(seed_stride), int(first_index), _dp(V0s), _dp(out['V']), _dp(out['primal']),
+                _dp(out['y']), _ip(out['sweeps']), _dp(out['X']) if S > 0 else None)
+        if ds is None:
+            self._chk(self.L.qcqpmi_sdr_small_batch(self.h, B, _dp(P0s), _dp(q0s), _dp(r0s), *tail))
+        else:
+            ds = np.ascontiguousarray(ds, dtype=np.float64)
+            if ds.shape != (B, n):
+                raise ValueError('sdr_small_batch: expected ds of shape (B, n)')
+            self._chk(self.L.qcqpmi_sdr_small_batch_pc(self.h, B, _dp(P0s), _dp(q0s), _dp(r0s), _dp(ds), *tail))
         return out
 
     # ------------------------------------------------------------------ selection

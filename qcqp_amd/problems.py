@@ -10,6 +10,7 @@ with the objective first (relop ``None``) -- the raw-array form accepted by
 * ``box_least_squares``      -- the box-constrained sibling of the Boolean family (one interval per coordinate)
 * ``box_qp``                 -- the box-constrained QP with an INDEFINITE objective (a diagonal of mixed sign)
 * ``boolean_least_squares_batch`` / ``box_qp_batch`` -- B small problems with shared constraints (qcqp_amd.batch.QCQPBatch)
+* ``per_problem_constraints_batch`` -- B small problems with the same constraint STRUCTURE and their own coefficients
 * ``beamforming``            -- examples/secondary_user_beamforming.py:18-41
 * ``dense_indefinite``       -- SURVEY.md section 8(d) cfg5 generator
 * ``circle_packing``         -- examples/circle_packing.py:6-17 (two variables: centres 2 x N and the radius)
@@ -126,6 +127,69 @@ def box_qp_batch(n, seeds, **kwargs):
     seeds = [int(sd) for sd in np.atleast_1d(seeds)]
     cons = box_qp(n, seed=seeds[0], **kwargs)[0][1:]
     return [[box_qp(n, seed=sd, **kwargs)[0][0]] + cons for sd in seeds]
+
+
+PER_PROBLEM_FAMILIES = ('boxpp', 'boxppneg', 'eq2pp', 'eqpp', 'annpp', 'linpp')
+
+
+def per_problem_constraints_batch(name, n, seeds):
+    """B = len(seeds) small problems whose constraints have the same STRUCTURE (number, touched coordinate, relop) and their own
+    COEFFICIENTS -- what qcqp_amd.batch.QCQPBatch solves through qcqpmi_cd_small_batch_run_pc.  Problem b takes its objective from the
+    shared-constraint generator at seed seeds[b] and draws its constraint coefficients from a RandomState keyed by (name, n,
+    seeds[b]): it depends on seeds[b] alone, not on B or on its place in the list.
+      boxpp     box_qp objective (indefinite diagonal); (x_i - lo)(x_i - hi) <= 0, lo ~ U(-2, 1), hi = lo + U(0.05, 2) per coordinate
+      boxppneg  box_qp(diagonal='negative') objective; the same constraints
+      eq2pp     box_qp objective; (x_i - lo)(x_i - hi) == 0, the same draws
+      eqpp      Boolean least squares objective (n + n // 2 + 1 rows); x_i^2 == d, d ~ U(0.25, 4) (the unit-diagonal family of SDR)
+      annpp     multi_class('ann2') objective; even i: x^2 <= ro^2 and -x^2 <= -ri^2, ro ~ U(0.8, 2), ri = ro U(0.2, 0.8);
+                odd i: x^2 == U(0.25, 4)  (two constraints on a coordinate)
+      linpp     box_qp objective; two LINEAR constraints per coordinate, x <= hi and -x <= -lo (p = 0), lo / hi as in boxpp
+    Returns a list of funcs lists (objective first)."""
+    import zlib
+    if name not in PER_PROBLEM_FAMILIES:
+        raise KeyError(name)
+    key = zlib.crc32(name.encode())
+    out = []
+    for sd in [int(sd) for sd in np.atleast_1d(seeds)]:
+        rs = np.random.RandomState([key, int(n), sd & 0xffffffff, (sd >> 32) & 0xffffffff])
+        if name == 'boxppneg':
+            funcs = [box_qp(n, seed=sd, diagonal='negative')[0][0]]
+        elif name == 'eqpp':
+            funcs = [boolean_least_squares(n, n + n // 2 + 1, seed=sd)[0][0]]
+        elif name == 'annpp':
+            funcs = [multi_class('ann2', n, seed=sd)[0]]
+        else:
+            funcs = [box_qp(n, seed=sd)[0][0]]
+
+        def quad(i, p, q, r, relop):
+            qv = np.zeros(n)
+            qv[i] = float(q)
+            funcs.append((sp.csr_matrix(([float(p)], ([i], [i])), shape=(n, n)), qv, float(r), relop))
+        if name in ('boxpp', 'boxppneg', 'eq2pp', 'linpp'):
+            lo = rs.uniform(-2.0, 1.0, size=n)
+            hi = lo + rs.uniform(0.05, 2.0, size=n)
+            for i in range(n):
+                if name == 'linpp':
+                    quad(i, 0.0, 1.0, -hi[i], '<=')
+                    quad(i, 0.0, -1.0, lo[i], '<=')
+                else:
+                    quad(i, 1.0, -(lo[i] + hi[i]), lo[i] * hi[i], '==' if name == 'eq2pp' else '<=')
+        elif name == 'eqpp':
+            d = rs.uniform(0.25, 4.0, size=n)
+            for i in range(n):
+                quad(i, 1.0, 0.0, -d[i], '==')
+        else:
+            ro = rs.uniform(0.8, 2.0, size=n)
+            ri = ro * rs.uniform(0.2, 0.8, size=n)
+            d = rs.uniform(0.25, 4.0, size=n)
+            for i in range(n):
+                if i % 2 == 0:
+                    quad(i, 1.0, 0.0, -ro[i] ** 2, '<=')
+                    quad(i, -1.0, 0.0, ri[i] ** 2, '<=')
+                else:
+                    quad(i, 1.0, 0.0, -d[i], '==')
+        out.append(funcs)
+    return out
 
 
 def multi_class(name, n, seed=1):

@@ -76,13 +76,14 @@ def dual_certificate(C, V):
 
 
 def lifted_cost_batch(P0s, q0s, r0s, d):
-    """C (B, N, N) of lifted_cost for B objectives over the same d: the same products, problem by problem."""
+    """C (B, N, N) of lifted_cost for B objectives: the same products, problem by problem.  d (n,): one d for all of them; d (B, n):
+    problem b's own."""
     P0s = np.asarray(P0s, dtype=np.float64)
     q0s = np.asarray(q0s, dtype=np.float64)
     B, n = q0s.shape
     s = np.sqrt(np.asarray(d, dtype=np.float64))
     C = np.zeros((B, n + 1, n + 1))
-    C[:, :n, :n] = (0.5 * (P0s + P0s.transpose(0, 2, 1))) * np.outer(s, s)
+    C[:, :n, :n] = (0.5 * (P0s + P0s.transpose(0, 2, 1))) * (s[..., :, None] * s[..., None, :])
     C[:, :n, n] = C[:, n, :n] = 0.5 * q0s * s
     C[:, n, n] = np.asarray(r0s, dtype=np.float64)
     return C

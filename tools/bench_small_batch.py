@@ -8,6 +8,11 @@ Workload: problems.boolean_least_squares_batch(B, n, m), R restarts per problem,
              Timed on the first --loop-problems problems and SCALED LINEARLY to B (every problem costs the same launches).
 Prints one JSON line (with how many winners of the timed subset the two paths agree on).  --profile-run: only the batched call, once
 after a warm-up (for rocprofv3 --kernel-trace --stats).
+
+--per-problem-constraints: the workload is problems.per_problem_constraints_batch('boxpp', n, seeds) -- box-constrained indefinite QPs
+with bounds per instance -- and the batched call is qcqpmi_cd_small_batch_run_pc (Engine.cd_small_batch_run(cons=...)).  The loop is the
+best the library offered for such a batch before: per problem a fresh context from the problem's own functions and ONE call of
+qcqpmi_cd_small_batch_run with B = 1 (bit for bit the same restarts), timed on --loop-problems problems and scaled linearly to B.
 """
 import argparse
 import json
@@ -29,6 +34,7 @@ def main():
     ap.add_argument('--loop-problems', type=int, default=256)
     ap.add_argument('--seed', type=int, default=1)
     ap.add_argument('--profile-run', action='store_true')
+    ap.add_argument('--per-problem-constraints', action='store_true')
     args = ap.parse_args()
 
     from qcqp_amd import problems
@@ -38,13 +44,18 @@ def main():
     if device_count() < 1:
         raise SystemExit('bench_small_batch: no HIP device visible (there is no CPU path)')
 
-    fl = problems.boolean_least_squares_batch(args.B, args.n, args.m, seed=args.seed)
+    pc = args.per_problem_constraints
+    if pc:
+        fl = problems.per_problem_constraints_batch('boxpp', args.n, [args.seed + b for b in range(args.B)])
+    else:
+        fl = problems.boolean_least_squares_batch(args.B, args.n, args.m, seed=args.seed)
     qb = QCQPBatch(fl)
     e = qb.engine
+    kw = dict(cons=qb.cons) if pc else {}
 
     def batched():
         t0 = time.perf_counter()
-        o = e.cd_small_batch_run(qb.P0s, qb.q0s, qb.r0s, args.R, num_iters=args.num_iters, seed=args.seed, seed_stride=1, want_x=False)
+        o = e.cd_small_batch_run(qb.P0s, qb.q0s, qb.r0s, args.R, num_iters=args.num_iters, seed=args.seed, seed_stride=1, want_x=False, **kw)
         return time.perf_counter() - t0, o
 
     batched()                                       # warm-up: code object, buffers
@@ -66,9 +77,14 @@ def main():
         t0 = time.perf_counter()
         for b in range(nl):
             eb = Engine(QCQPForm.from_arrays(fl[b]))
-            eb.randn(args.R, seed=args.seed + b)
-            eb.cd_run(num_iters=args.num_iters, seed=args.seed + b)
-            best.append(eb.select_best())
+            if pc:
+                ob = eb.cd_small_batch_run(qb.P0s[b:b + 1], qb.q0s[b:b + 1], qb.r0s[b:b + 1], args.R, num_iters=args.num_iters,
+                                           seed=args.seed + b, want_x=False)
+                best.append((int(ob['best_index'][0]), float(ob['best_f0'][0])))
+            else:
+                eb.randn(args.R, seed=args.seed + b)
+                eb.cd_run(num_iters=args.num_iters, seed=args.seed + b)
+                best.append(eb.select_best())
             eb.close()
         return time.perf_counter() - t0, best
 
@@ -77,7 +93,7 @@ def main():
     t_loop, best = lt[1]
     agree = sum(1 for b in range(nl) if int(o['best_index'][b]) == best[b][0] and abs(o['best_f0'][b] - best[b][1]) <= 1e-9 * (1 + abs(best[b][1])))
     print(json.dumps(dict(
-        workload=dict(B=args.B, n=args.n, m=args.m, R=args.R, num_iters=args.num_iters), kernel=e.last_cd_kernel(),
+        workload=dict(family='boxpp' if pc else 'bls', B=args.B, n=args.n, m=args.m, R=args.R, num_iters=args.num_iters), kernel=e.last_cd_kernel(),
         batched_s=t_batched, batched_all_s=times, batched_kernel_ms=kernel_ms, restart_sweeps=sweeps,
         restart_sweeps_per_s=sweeps / t_batched, loop_problems=nl, loop_s_measured=t_loop,
         loop_s_scaled_to_B=t_loop * args.B / nl, speedup=(t_loop * args.B / nl) / t_batched, winners_agree='%d/%d' % (agree, nl))))
