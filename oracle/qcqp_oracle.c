@@ -523,15 +523,15 @@ static int64_t gather_onevars(const orc_prob *p, const double *x, int64_t i,
 
 /* test hook: the value of x[i] after every coordinate visit of the coordinate-descent runs that follow (phase 1 and
  * phase 2 append to the same buffer; the state after any visit is x0 with the recorded values applied in order) */
-static double *g_trace = NULL;
-static int64_t g_trace_cap = 0, g_trace_len = 0;
+static _Thread_local double *g_trace = NULL;       /* per thread: traced runs of independent restarts may run side by side */
+static _Thread_local int64_t g_trace_cap = 0, g_trace_len = 0;
 void orc_cd_trace(double *buf, int64_t cap) { g_trace = buf; g_trace_cap = buf ? cap : 0; g_trace_len = 0; }
 int64_t orc_cd_trace_len(void) { return g_trace_len; }
 #define ORC_TRACE(v) do { if (g_trace && g_trace_len < g_trace_cap) g_trace[g_trace_len] = (v); if (g_trace) g_trace_len++; } while (0)
 /* test instrumentation like the trace: stop orc_cd_phase1 / orc_cd_phase2 after this many coordinate visits (< 0: off) -- a
  * visit of a problem with 257 dense 1024 x 1024 functions costs 0.13 s (get_onevar_func forms P_k z for every function,
  * utilities.py:99-105), a sweep two minutes: the teacher-forced parity test at that size follows the first visits only */
-static int64_t g_visit_limit = -1;
+static _Thread_local int64_t g_visit_limit = -1;
 void orc_cd_visit_limit(int64_t visits) { g_visit_limit = visits; }
 
 int orc_cd_phase1(const orc_prob *p, double *x, int64_t num_iters, double viol_tol,

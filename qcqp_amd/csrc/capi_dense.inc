@@ -251,6 +251,8 @@ int dense_phase(qcqpmi_ctx *c, int64_t num_iters, double viol_tol, double tol, u
     while (wpb > 1 && per * wpb > 160 * 1024) wpb--;
     const size_t lds = mw ? dense_chain_mw_lds_bytes(D.m1p) : per * wpb;
     if (lds > 160 * 1024) return fail(c, QCQPMI_EUNSUPPORTED, "coupled constraints: m = %d too large for the per-restart LDS tables", D.m1 - 1);
+    // the one-wave kernel keeps one flag per function slot of a lane (DnSlotBits); the LDS tables end far below that today
+    if (!mw && D.m1p > 64 * DN_SLOTS) return fail(c, QCQPMI_EUNSUPPORTED, "coupled constraints: m = %d beyond the %d function slots per lane of dense_chain_kernel", D.m1 - 1, DN_SLOTS);
     ca.prof = c->profile ? c->dn_prof : nullptr;
     ca.slack = c->d_mv; ca.S = S; ca.tol = tol; ca.viol_tol = viol_tol; ca.seed = seed; ca.first_index = first_index;
     void (*kc)(DenseChainArgs);

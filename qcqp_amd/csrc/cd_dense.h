@@ -51,6 +51,8 @@ constexpr int DN_LDS_WAVE = 2 * DN_GC + 2 * DN_SC + 32 + 8;
 constexpr int DN_FARR = 6;
 constexpr int DN_FARR_MIN = 4;
 constexpr int DN_PF = 8;     // function slots per lane whose per-coordinate operands are requested in one batch
+constexpr int DN_SLOTS = 128;   // function slots per lane the one-wave chain kernel keeps flags for (m1p <= 64 DN_SLOTS = 8192;
+                                // the LDS tables admit m1p <= 5056, 79 slots)
 
 typedef double dn_v4d __attribute__((ext_vector_type(4)));
 
@@ -606,6 +608,15 @@ struct DnProf {
     }
 };
 
+// one flag per function slot j of a lane (function lane + 64 j), j < DN_SLOTS: two words, never a shift by more than 63
+struct DnSlotBits {
+    unsigned long long lo = 0ull, hi = 0ull;
+    __device__ inline void set(int j) { if (j < 64) lo |= 1ull << j; else hi |= 1ull << (j - 64); }
+    __device__ inline bool get(int j) const { return (((j < 64) ? (lo >> j) : (hi >> (j - 64))) & 1ull) != 0ull; }
+    __device__ inline bool any() const { return (lo | hi) != 0ull; }
+};
+static_assert(DN_SLOTS == 128, "DnSlotBits holds two 64-bit words");
+
 struct DnWave {            // the wave's LDS region
     double *t2, *t1, *t0, *F;    // [m1p]
     double *fga, *fgb;           // [m1p] the gap of a function that allows two intervals (pass 1 -> pass 2)
@@ -656,21 +667,21 @@ __device__ inline int dn_sweep_segments(double *ga, double *gb, int ng, double *
 // Returns the number of segments (wave-uniform); the list is in W.seglo / W.seghi.
 template <bool SG>      // SG: the gaps found in pass 1 are kept in W.fga / W.fgb; else pass 2 recomputes them
 __device__ inline int dn_feasible_set(const DnWave &W, const DenseProblem &D, int lane, double s, int *overflow, DnProf &pf,
-                                      unsigned long long relbits) {
+                                      const DnSlotBits &eqbits) {
     // pass 1: bounds of this lane's constraints
     double L = -QM_INF, H = QM_INF;
     int mH = 0;
     bool empty = false;
-    unsigned n2 = 0;   // bit j: function lane + 64 j allows two intervals
+    DnSlotBits n2;     // slot j: function lane + 64 j allows two intervals
     int j = 0;
     for (int k = lane; k < D.m1; k += 64, j++) {
         if (k == 0) continue;
         const double t2 = W.t2[k], t1 = W.t1[k];
         if (t2 == 0.0 && t1 == 0.0) continue;   // qcqp.py:116,166
-        const Seg2 iv = feasible_intervals(t2, t1, W.t0[k], (int)((relbits >> (2 * j)) & 3ull), s);
+        const Seg2 iv = feasible_intervals(t2, t1, W.t0[k], eqbits.get(j) ? RELOP_EQ : RELOP_LE, s);
         if (iv.n == 0) { empty = true; continue; }
         const double lo = iv.lo0, hi = (iv.n == 2) ? iv.hi1 : iv.hi0;
-        if (iv.n == 2) { n2 |= 1u << j; if (SG) { W.fga[k] = iv.hi0; W.fgb[k] = iv.lo1; } }   // same lane reads them back in pass 2
+        if (iv.n == 2) { n2.set(j); if (SG) { W.fga[k] = iv.hi0; W.fgb[k] = iv.lo1; } }   // same lane reads them back in pass 2
         L = lo > L ? lo : L;
         if (hi < H) { H = hi; mH = 1; } else if (hi == H) mH++;
     }
@@ -691,15 +702,15 @@ __device__ inline int dn_feasible_set(const DnWave &W, const DenseProblem &D, in
     int ng = 0;
     const int kpt = (D.m1 + 63) >> 6;
     const unsigned long long lt = (1ull << lane) - 1ull;
-    if (__builtin_amdgcn_ballot_w64(n2 != 0u) != 0ull) {
+    if (__builtin_amdgcn_ballot_w64(n2.any()) != 0ull) {
         for (int jj = 0; jj < kpt; jj++) {
             const int k = lane + 64 * jj;
             bool has = false;
             double ga = 0.0, gb = 0.0;
-            if ((n2 >> jj) & 1u) {
+            if (n2.get(jj)) {
                 if (SG) { ga = W.fga[k]; gb = W.fgb[k]; }
                 else {
-                    const Seg2 iv = feasible_intervals(W.t2[k], W.t1[k], W.t0[k], (int)((relbits >> (2 * jj)) & 3ull), s);
+                    const Seg2 iv = feasible_intervals(W.t2[k], W.t1[k], W.t0[k], eqbits.get(jj) ? RELOP_EQ : RELOP_LE, s);
                     ga = iv.hi0; gb = iv.lo1;
                 }
                 has = gb > Lg && ga <= Hg;
@@ -763,11 +774,12 @@ __global__ __launch_bounds__(64 * DN_WPB) void dense_chain_kernel(DenseChainArgs
     double *Xt = a.X + tile * D.n16 * 16;
     double *Ftr = a.Ft + gr * m1p;
     for (int k = lane; k < m1; k += 64) W.F[k] = Ftr[k];
-    // relop of the lane's functions, 2 bits per slot (m1p <= 2048)
-    unsigned long long relbits = 0ull;
+    // which of the lane's functions are '==' constraints (the interval rules know '==' and the rest, onevar.h): one flag
+    // per slot, for every slot count the dispatch admits (dense_phase refuses m1p > 64 DN_SLOTS)
+    DnSlotBits eqbits;
     {
         int j = 0;
-        for (int k = lane; k < m1; k += 64, j++) relbits |= (unsigned long long)(D.relop[k] & 3) << (2 * j);
+        for (int k = lane; k < m1; k += 64, j++) if (D.relop[k] == RELOP_EQ) eqbits.set(j);
     }
     if (GLDS) {
         const double *Gr = a.G + (tile * 256 + r) * m1p;   // row c of this restart: + c * 16 * m1p
@@ -844,7 +856,7 @@ __global__ __launch_bounds__(64 * DN_WPB) void dense_chain_kernel(DenseChainArgs
                 W.t2[k] = t2; W.t1[k] = t1; W.t0[k] = t0;
                 if (PHASE == 1 && k > 0 && !(t2 == 0.0 && t1 == 0.0)) {
                     const double f = xi * (t2 * xi + t1) + t0;
-                    const double v = ((int)((relbits >> (2 * j)) & 3ull) == RELOP_EQ) ? fabs(f) : (f > 0.0 ? f : 0.0);
+                    const double v = eqbits.get(j) ? fabs(f) : (f > 0.0 ? f : 0.0);
                     vloc = v > vloc ? v : vloc;
                     inv = true;
                 }
@@ -856,7 +868,7 @@ __global__ __launch_bounds__(64 * DN_WPB) void dense_chain_kernel(DenseChainArgs
         pf.tick(1);
         if (PHASE == 2) {
             // ---- B. feasible set at the fixed slack, minimiser of the scalar objective
-            const int ns = dn_feasible_set<GLDS>(W, D, lane, slack, &overflow, pf, relbits);
+            const int ns = dn_feasible_set<GLDS>(W, D, lane, slack, &overflow, pf, eqbits);
             int got = 0;
             if (lane == 0) {
                 SegList C = SL;
@@ -888,7 +900,7 @@ __global__ __launch_bounds__(64 * DN_WPB) void dense_chain_kernel(DenseChainArgs
                 bool pending = false;
                 while (es - ss > a.tol) {
                     const double sm = (ss + es) / 2.0;
-                    const int ns = dn_feasible_set<GLDS>(W, D, lane, sm, &overflow, pf, relbits);
+                    const int ns = dn_feasible_set<GLDS>(W, D, lane, sm, &overflow, pf, eqbits);
                     const uint32_t itc = it++;
                     if (ns == 0) { ss = sm; continue; }
                     bool unb = false;
