@@ -149,10 +149,13 @@ __global__ __launch_bounds__(256) void admm_secular_kernel(AdmmArgs a) {
     }
     // element slots e whose eigenvalues are zero in every lane (low-rank constraints: all but the ends of the
     // spectrum): there 2 (1 + nu lam) == 2 exactly and the division in phi is a multiplication by 0.5
-    unsigned nzmask = 0;
+    // (one bit per slot: a 32-bit mask shifted by e >= 32 is undefined, and the compiler dropped the secular function from both
+    // EPL = 64 instantiations -- profiles/r14_admm_domain.md)
+    static_assert(EPL <= 64, "nzmask holds one bit per element slot");
+    unsigned long long nzmask = 0ull;
 #pragma unroll
     for (int e = 0; e < EPL; e++)
-        if (__builtin_amdgcn_ballot_w64(L[e] != 0.0) != 0ull) nzmask |= 1u << e;
+        if (__builtin_amdgcn_ballot_w64(L[e] != 0.0) != 0ull) nzmask |= 1ull << e;
     // violation of z itself (QuadraticFunction.violation, utilities.py:56-62) in eigen form
     double sa_, sb_;
     pair_sum(fz_a, fz_b, &sa_, &sb_);
@@ -175,7 +178,7 @@ __global__ __launch_bounds__(256) void admm_secular_kernel(AdmmArgs a) {
 #pragma unroll
             for (int e = 0; e < EPL; e++) {
                 const double num = -(nu * Qh[e] - 2.0 * V[e]);
-                const double xh = ((nzmask >> e) & 1u) ? admm_div(num, 2.0 * (1.0 + nu * L[e])) : num * 0.5;   // wave-uniform
+                const double xh = ((nzmask >> e) & 1ull) ? admm_div(num, 2.0 * (1.0 + nu * L[e])) : num * 0.5;   // wave-uniform
                 X[e] = xh;
                 pa += L[e] * (xh * xh);
                 pb += Qh[e] * xh;
@@ -566,7 +569,9 @@ struct AdmmBook {
     int phase;                 // 1 or 2
     double tol, viol_lim;
     int have_last;             // phase 2: a previous z exists
-    const double *Z;
+    int first;                 // phase 1: this is iteration 0 (a restart that stops here never left its start)
+    const double *X0;          // phase 1: the points the phase started from
+    double *Z;
     double *Zlast, *BEST;
     const double *dist2, *f0z;
     unsigned long long *mvbits;
@@ -578,17 +583,17 @@ struct AdmmBook {
 
 // per-restart control flow of admm_phase1 (qcqp.py:202-204) / admm_phase2 (qcqp.py:240-249); one workgroup per tile
 __global__ __launch_bounds__(ADMM_TPB) void admm_book_kernel(AdmmBook b) {
-    __shared__ int take[16], live[16];
+    __shared__ int take[16], live[16], back[16];
     const int64_t tile = blockIdx.x;
     const int rr = threadIdx.x & 15, jl = threadIdx.x >> 4;
     if (threadIdx.x < 16) {
         const int64_t r = tile * 16 + threadIdx.x;
-        int tk = 0, lv = 0;
+        int tk = 0, lv = 0, bc = 0;
         if (r < b.R && b.act[r]) {
             const double mv = __longlong_as_double((long long)b.mvbits[r]);
             bool stop = false;
             if (b.phase == 1) {
-                if (mv < b.tol) stop = true;                       // qcqp.py:203
+                if (mv < b.tol) { stop = true; bc = b.first; }     // qcqp.py:203
             } else {
                 if (b.have_last && sqrt(b.dist2[r]) < b.tol) stop = true;       // qcqp.py:241-242 (before bestx)
                 else if (mv > b.viol_lim) stop = true;                          // qcqp.py:248
@@ -604,9 +609,16 @@ __global__ __launch_bounds__(ADMM_TPB) void admm_book_kernel(AdmmBook b) {
             lv = 1;
         }
         if (r < b.R) b.mvbits[r] = 0ull;      // read: the next iteration's projections start from zero (no fill launch per iteration)
-        take[threadIdx.x] = tk; live[threadIdx.x] = lv;
+        take[threadIdx.x] = tk; live[threadIdx.x] = lv; back[threadIdx.x] = bc;
     }
     __syncthreads();
+    // feasible at the start: the reference tests x0 before its first z-update (qcqp.py:202-205) and returns x0 itself; the z-update
+    // in front of this iteration left fl(fl(m x0) / m), up to an ulp away
+    if (b.phase == 1 && back[rr])
+        for (int64_t j = jl; j < b.n; j += ADMM_TPB / 16) {
+            const int64_t idx = (tile * b.n16 + j) * 16 + rr;
+            b.Z[idx] = b.X0[idx];
+        }
     if (b.phase == 2 && live[rr]) {
         const bool tk = take[rr] != 0;
         for (int64_t j = jl; j < b.n; j += ADMM_TPB / 16) {

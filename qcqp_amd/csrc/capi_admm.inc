@@ -1051,7 +1051,7 @@ int qcqpmi_admm_run(qcqpmi_ctx *c, int phase1, int64_t num_iters, double tol, do
     AdmmBook bk;
     bk.n = n; bk.n16 = n16; bk.R = R; bk.tol = tol; bk.viol_lim = viol_lim; bk.Z = Z.p; bk.Zlast = Zlast.p; bk.BEST = BEST.p;
     bk.dist2 = dist2.p; bk.f0z = f0z.p; bk.mvbits = mvb.p; bk.best_f0 = bf0.p; bk.best_mv = bmv.p; bk.act = act.p;
-    bk.nactive = nact.p;
+    bk.nactive = nact.p; bk.first = 0; bk.X0 = X0.p;
     // first z-update of a phase: xs = x0, us = 0  =>  S = m x0.  In a reduced basis S is assembled as m z + W D: the
     // planes hold zero then.
     auto seed_S = [&](const double *x) -> int {
@@ -1085,6 +1085,7 @@ int qcqpmi_admm_run(qcqpmi_ctx *c, int phase1, int64_t num_iters, double tol, do
             }
             if ((t & 7) == 0) HIPCHK(c, hipMemsetAsync(nact.p, 0, 8 * sizeof(int), st));
             bk.nactive = nact.p + (t & 7);
+            bk.first = t == 0 ? 1 : 0;
             hipLaunchKernelGGL(admm_book_kernel, dim3((unsigned)ntiles), dim3(ADMM_TPB), 0, st, bk);
             HIPCHK(c, hipGetLastError());
             if ((t & 7) == 7 || t + 1 == num_iters) {
@@ -1093,6 +1094,7 @@ int qcqpmi_admm_run(qcqpmi_ctx *c, int phase1, int64_t num_iters, double tol, do
                 if (na == 0) break;
             }
         }
+        bk.first = 0;
         // x1 = better(x0, z1) (qcqp.py:281)
         if ((rc = evaluate(Z.p, fa.p, f_a, v_a))) return rc;
         for (int64_t r = 0; r < R; r++) {
