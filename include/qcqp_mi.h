@@ -389,6 +389,29 @@ int qcqpmi_cd_small_batch_run_pc(qcqpmi_ctx *ctx, int64_t B, const double *P0s, 
                                  double select_tol, int64_t *sweeps1, int64_t *sweeps2, int64_t *visits2, int64_t *accepted2,
                                  uint8_t *ran_phase2, int *status1, int *status2, double *f0, double *maxviol, double *X,
                                  int64_t *best_index, double *best_f0, double *best_maxviol, double *best_x);
+/* THE BATCH FOR PROBLEMS OF UP TO 128 VARIABLES (added within ABI 6: a new symbol, nothing else changes).  The arguments of
+ * qcqpmi_cd_small_batch_run_pc; cons may be NULL: shared constraints, the context's.  1 <= n <= 128.
+ * n <= 64: exactly the launch of qcqpmi_cd_small_batch_run (cons == NULL) or qcqpmi_cd_small_batch_run_pc -- the same kernel, the same
+ * bits, the same name in qcqpmi_last_cd_kernel.
+ * 65 <= n <= 128: the WIDE kernels cd_small_kernel<MAXC, pc, 2> -- one wavefront per (problem, restart) as before, lane l holds the
+ * coordinates l and l + 64 (the second one where l + 64 < n); a visit of coordinate i reads slot i >> 6 at lane i & 63 and its rank-one
+ * update covers both slots.  The LDS image is the same -- P0_b row-major n x n, q0_b, the [3][m] coefficients with cons, two control
+ * words: (n^2 + n + 3 m) 8 + 8 bytes, at most 144 392 of the 160 KB of a CU; from n = 101 one workgroup (512 threads, eight waves)
+ * owns a CU.  A 64 x 64 QPSK MIMO frame (128 real variables) is the example.
+ * PARITY: that of the two symbols above, unchanged.  Every sum is formed in the same order (row sums over k ascending, the objective
+ * over j ascending across both slots), the keyed draws go by the coordinate index, status1 is that of the highest coordinate with a
+ * nonzero code.  A result depends on (objective b, constraints b, seed of b, global index) alone -- not on B, the neighbours, the order
+ * of the problems, the workgroups or a split of the restarts over calls: bit for bit.  With cons, restart (b, r) is bit for bit the
+ * restart of the call with B = 1, cons == NULL on a context created from problem b's own functions.
+ * qcqpmi_last_cd_kernel for n > 64: "cd_small_kernel<1,w2>" / "<4,w2>" / "<1,pc,w2>" / "<4,pc,w2>".
+ * Refusals, the resident population left alone.  QCQPMI_EUNSUPPORTED: n > 128, constraints that are not separable.  QCQPMI_EINVAL:
+ * B < 1, R < 1, B R >= 2^30, a missing array, a cons entry that is not finite or has p == q == 0, a P0_b that is not symmetric. */
+int qcqpmi_cd_batch_run(qcqpmi_ctx *ctx, int64_t B, const double *P0s, const double *q0s, const double *r0s, const double *cons,
+                        int64_t R, int generate, const double *X0, int phase1, int64_t num_iters, double viol_tol, double tol,
+                        uint64_t seed, uint64_t seed_stride, uint64_t first_index, double select_tol, int64_t *sweeps1,
+                        int64_t *sweeps2, int64_t *visits2, int64_t *accepted2, uint8_t *ran_phase2, int *status1, int *status2,
+                        double *f0, double *maxviol, double *X, int64_t *best_index, double *best_f0, double *best_maxviol,
+                        double *best_x);
 /* SUGGEST(SDR) FOR MANY SMALL PROBLEMS IN ONE LAUNCH (added within ABI 6: a new symbol, nothing else changes).  The batch of
  * qcqpmi_cd_small_batch_run -- B objectives P0s [B][n][n] (each symmetric), q0s [B][n], r0s [B] over this context's constraints, n <= 64
  * -- for the UNIT-DIAGONAL family: every coordinate carries exactly one constraint p x_i^2 + r == 0 with d_i = -r / p > 0 and no linear

@@ -1,15 +1,16 @@
 """QCQPBatch: many SMALL problems that share their constraints -- or the structure of their constraints --, solved in one launch.
 
-A frame of MIMO detection problems is thousands of independent Boolean least squares instances of 8 .. 64 variables: every
+A frame of MIMO detection problems is thousands of independent Boolean least squares instances of 8 .. 128 variables: every
 instance has its own objective and all of them the constraints x_i^2 == 1.  ``QCQP`` holds one problem per context; this class
 holds B of them on ONE context and runs suggest(RANDOM) + improve(COORD_DESCENT) for all B x R restarts through one persistent
-kernel (``Engine.cd_small_batch_run``, qcqpmi_cd_small_batch_run).  suggest(SDR) -- for constraints x_i^2 == d_i -- solves the
+kernel (``Engine.cd_small_batch_run``, qcqpmi_cd_small_batch_run; for 64 < n <= 128 ``Engine.cd_batch_run``, qcqpmi_cd_batch_run: the
+wide kernels, two coordinates per lane).  suggest(SDR) -- for constraints x_i^2 == d_i -- solves the
 semidefinite relaxation of all B problems and draws their samples in one launch as well (``Engine.sdr_small_batch``,
 qcqpmi_sdr_small_batch) and publishes the certified bounds in ``sdr_bound``; improve() then starts from the samples.  Problem b's results are those of
 ``QCQP(Problem(funcs_b))`` with suggest(RANDOM, num_samples=R, seed=seed + b seed_stride, first_index=...) followed by
 improve(COORD_DESCENT, ..., seed=seed + b seed_stride, first_index=...).  Problems whose constraints differ in their COEFFICIENTS
 only (boxes with bounds per instance, x_i^2 == d_{b,i}: problems.per_problem_constraints_batch) run through the same launches with
-per-problem coefficients.
+per-problem coefficients.  suggest(SDR) is defined for n <= 64 (the relaxation's LDS image does not fit beyond).
 
     from qcqp_amd.batch import QCQPBatch
     from qcqp_amd import problems, settings as s
@@ -71,9 +72,13 @@ def _structure(funcs):
     return None if any(e is None for e in out) else out
 
 
+MAX_N = 128          # qcqpmi_cd_batch_run: two coordinates per lane
+MAX_N_SMALL = 64     # qcqpmi_cd_small_batch_run, qcqpmi_sdr_small_batch: one coordinate per lane
+
+
 class QCQPBatch(object):
     """``funcs_list`` = [funcs_0, ..., funcs_{B-1}], every funcs_b = [(P, q, r, relop), ...] in minimise form with the objective
-    first (what qcqp_amd.problems returns).  All problems must have the same n (<= 64) and constraints of the same STRUCTURE: the
+    first (what qcqp_amd.problems returns).  All problems must have the same n (<= 128; suggest(SDR): <= 64) and constraints of the same STRUCTURE: the
     same number of them, and constraint k with the same relop on the same coordinate in every problem.  Their coefficients may
     differ from problem to problem (separable constraints only): ``cons`` (B, m, 3) then holds (p, q, r) of every constraint and the
     launches are qcqpmi_cd_small_batch_run_pc / qcqpmi_sdr_small_batch_pc; with equal coefficients ``cons`` is None and the calls are
@@ -88,6 +93,8 @@ class QCQPBatch(object):
             nb = int(np.asarray(funcs[0][1]).size)
             if nb != n:
                 raise Exception("QCQPBatch: problem %d has n = %d, problem 0 has n = %d" % (b, nb, n))
+        if n > MAX_N:
+            raise Exception("QCQPBatch: n = %d, the batch kernels take n <= %d (use QCQP, one context per problem)" % (n, MAX_N))
         differing = [b for b in range(1, len(funcs_list)) if not _same_constraints(funcs_list[0], funcs_list[b])]
         self.cons = None
         if differing:
@@ -135,6 +142,9 @@ class QCQPBatch(object):
         if int(num_samples) < 1:
             raise Exception("QCQPBatch.suggest: num_samples must be positive")
         if method == s.SDR:
+            if self.n > MAX_N_SMALL:      # before any launch: (65 N + N^2 + 64) doubles of LDS, N = n + 1, do not fit a CU past N = 114
+                raise Exception("QCQPBatch.suggest(SDR) is defined for n <= %d (n = %d): the batched relaxation keeps V_b and C_b in "
+                                "LDS; use suggest(RANDOM), or QCQP per problem" % (MAX_N_SMALL, self.n))
             d = _sdr.unit_diagonal_family(self.form)
             if d is None:
                 raise Exception("QCQPBatch.suggest(SDR) is defined for constraints x_i^2 == d_i (one per coordinate)")
@@ -171,8 +181,9 @@ class QCQPBatch(object):
         if seed is not None and int(seed) != sd:
             raise Exception("QCQPBatch.improve: seed %d differs from the seed of suggest (%d); the batch runs one keyed stream per problem"
                             % (int(seed), sd))
-        out = self.engine.cd_small_batch_run(self.P0s, self.q0s, self.r0s, R, X0=self._starts, phase1=phase1, num_iters=num_iters, viol_tol=viol_tol,
-                                             tol=tol, seed=sd, seed_stride=stride, first_index=first_index, want_x=False, cons=self.cons)
+        run = self.engine.cd_small_batch_run if self.n <= MAX_N_SMALL else self.engine.cd_batch_run
+        out = run(self.P0s, self.q0s, self.r0s, R, X0=self._starts, phase1=phase1, num_iters=num_iters, viol_tol=viol_tol,
+                  tol=tol, seed=sd, seed_stride=stride, first_index=first_index, want_x=False, cons=self.cons)
         self.x = out['best_x']
         self.best_index = out['best_index']
         self.population_f, self.population_v = out['f0'], out['maxviol']

@@ -1759,7 +1759,9 @@ int qcqpmi_cd_stream_run(qcqpmi_ctx *c, int64_t K, int64_t R, int generate, int 
 // (csrc/cd_small.hip).  Works in a buffer of its own: the resident population, its evaluation and its status codes are not touched,
 // whether the call succeeds or is refused.
 // cons == nullptr: the context's coefficients; else [B][m][3], per_problem set: qcqpmi_cd_small_batch_run_pc
-static int cd_small_batch(qcqpmi_ctx *c, bool per_problem, const double *cons, int64_t B, const double *P0s, const double *q0s, const double *r0s,
+// maxn: CD_SMALL_MAXN for the two small-batch symbols; CD_WIDE_MAXN for qcqpmi_cd_batch_run, whose problems of more than CD_SMALL_MAXN
+// variables run the wide kernels (two coordinates per lane) -- everything else is the same call
+static int cd_small_batch(qcqpmi_ctx *c, int64_t maxn, bool per_problem, const double *cons, int64_t B, const double *P0s, const double *q0s, const double *r0s,
                           int64_t R, int generate, const double *X0, int phase1, int64_t num_iters, double viol_tol, double tol, uint64_t seed,
                           uint64_t seed_stride, uint64_t first_index, double select_tol, int64_t *sweeps1, int64_t *sweeps2,
                           int64_t *visits2, int64_t *accepted2, uint8_t *ran_phase2, int *status1, int *status2, double *f0,
@@ -1767,7 +1769,8 @@ static int cd_small_batch(qcqpmi_ctx *c, bool per_problem, const double *cons, i
     int rc = check_ready(c, false);
     if (rc) return rc;
     if (!c->sep) return fail(c, QCQPMI_EUNSUPPORTED, "cd_small_batch_run: the constraints are not separable (a constraint couples coordinates, or a coordinate carries more than 4)");
-    if (c->n > CD_SMALL_MAXN) return fail(c, QCQPMI_EUNSUPPORTED, "cd_small_batch_run: n = %lld, the small-problem kernel takes n <= %d (one lane per coordinate)", (long long)c->n, CD_SMALL_MAXN);
+    if (c->n > maxn) return fail(c, QCQPMI_EUNSUPPORTED, "cd_small_batch_run: n = %lld, the small-problem kernel takes n <= %lld (%s)", (long long)c->n, (long long)maxn,
+                                 maxn > CD_SMALL_MAXN ? "two coordinates per lane" : "one lane per coordinate");
     if (B < 1 || R < 1 || num_iters < 0 || !(tol > 0.0) || !P0s || !q0s || !r0s || (!generate && !X0))
         return fail(c, QCQPMI_EINVAL, "cd_small_batch_run: bad B / R / num_iters / tol, or a missing input array");
     if (B >= (1LL << 30) || R >= (1LL << 30) || B * R >= (1LL << 30)) return fail(c, QCQPMI_EINVAL, "cd_small_batch_run: B R = %lld restarts, at most 2^30 - 1 per call", (long long)(B * R));
@@ -1821,21 +1824,23 @@ static int cd_small_batch(qcqpmi_ctx *c, bool per_problem, const double *cons, i
     a.f0 = (double *)(o + 32 * T); a.maxviol = (double *)(o + 40 * T);
     a.status1 = (int *)(o + 48 * T); a.status2 = (int *)(o + 52 * T); a.ran2 = (uint8_t *)(o + 56 * T);
     a.X = (double *)(w + oX);
-    // tickets: whole problems when there are enough of them to fill the device, else chunks of at least 4 restarts (one per wave)
+    // tickets: whole problems when there are enough of them to fill the device, else chunks of at least one restart per wave of a workgroup
     const int maxc = c->maxc <= 1 ? 1 : 4;
-    int wgs = cd_small_workgroups(n, maxc, cons ? m : 0, B * R, c->device);
+    int threads = 0;
+    int wgs = cd_small_workgroups(n, maxc, cons ? m : 0, B * R, c->device, &threads);
     if (wgs < 1) return fail(c, QCQPMI_EHIP, "cd_small_batch_run: occupancy query failed: %s", hipGetErrorString((hipError_t)(-wgs)));
     int64_t chunks = B >= wgs ? 1 : (wgs + B - 1) / B;
-    if (chunks > (R + 3) / 4) chunks = (R + 3) / 4;
+    const int64_t waves = threads / 64;
+    if (chunks > (R + waves - 1) / waves) chunks = (R + waves - 1) / waves;
     a.RC = (R + chunks - 1) / chunks;
     a.chunks = (R + a.RC - 1) / a.RC;
     if (wgs > B * a.chunks) wgs = (int)(B * a.chunks);
     (void)hipEventRecord(c->timers[2].beg, c->stream);
-    hipError_t qe = (hipError_t)cd_small_launch(a, maxc, wgs, c->stream);
+    hipError_t qe = (hipError_t)cd_small_launch(a, maxc, wgs, threads, c->stream);
     (void)hipEventRecord(c->timers[2].end, c->stream);
     c->timers[2].valid = true;
     if (qe != hipSuccess) return fail(c, QCQPMI_EHIP, "cd_small_batch_run: %s", hipGetErrorString(qe));
-    c->last_cd2_kernel = cd_small_name(maxc, cons != nullptr);
+    c->last_cd2_kernel = cd_small_name(maxc, cons != nullptr, n > CD_SMALL_MAXN);
     const bool want_best = best_index || best_f0 || best_maxviol || best_x;
     if (want_best) {       // QCQPForm.better folded over every problem's restarts, ties -> lowest index: one workgroup per problem
         hipLaunchKernelGGL(select_best_kernel, dim3((unsigned)B), dim3(1024), 0, c->stream, (const double *)a.f0, (const double *)a.maxviol, R,
@@ -1886,7 +1891,7 @@ int qcqpmi_cd_small_batch_run(qcqpmi_ctx *c, int64_t B, const double *P0s, const
                               uint64_t seed_stride, uint64_t first_index, double select_tol, int64_t *sweeps1, int64_t *sweeps2,
                               int64_t *visits2, int64_t *accepted2, uint8_t *ran_phase2, int *status1, int *status2, double *f0,
                               double *maxviol, double *X, int64_t *best_index, double *best_f0, double *best_maxviol, double *best_x) {
-    return cd_small_batch(c, false, nullptr, B, P0s, q0s, r0s, R, generate, X0, phase1, num_iters, viol_tol, tol, seed, seed_stride, first_index,
+    return cd_small_batch(c, CD_SMALL_MAXN, false, nullptr, B, P0s, q0s, r0s, R, generate, X0, phase1, num_iters, viol_tol, tol, seed, seed_stride, first_index,
                           select_tol, sweeps1, sweeps2, visits2, accepted2, ran_phase2, status1, status2, f0, maxviol, X, best_index, best_f0,
                           best_maxviol, best_x);
 }
@@ -1899,9 +1904,21 @@ int qcqpmi_cd_small_batch_run_pc(qcqpmi_ctx *c, int64_t B, const double *P0s, co
                                  int64_t *sweeps2, int64_t *visits2, int64_t *accepted2, uint8_t *ran_phase2, int *status1, int *status2,
                                  double *f0, double *maxviol, double *X, int64_t *best_index, double *best_f0, double *best_maxviol,
                                  double *best_x) {
-    return cd_small_batch(c, true, cons, B, P0s, q0s, r0s, R, generate, X0, phase1, num_iters, viol_tol, tol, seed, seed_stride, first_index,
+    return cd_small_batch(c, CD_SMALL_MAXN, true, cons, B, P0s, q0s, r0s, R, generate, X0, phase1, num_iters, viol_tol, tol, seed, seed_stride, first_index,
                           select_tol, sweeps1, sweeps2, visits2, accepted2, ran_phase2, status1, status2, f0, maxviol, X, best_index, best_f0,
                           best_maxviol, best_x);
+}
+
+// ---- the batch for 1 <= n <= 128: what the two symbols above run for n <= 64 (cons == NULL: shared constraints), the wide kernels
+// cd_small_kernel<MAXC, pc, 2> (one wavefront per restart, two coordinates per lane) for 65 <= n <= 128
+int qcqpmi_cd_batch_run(qcqpmi_ctx *c, int64_t B, const double *P0s, const double *q0s, const double *r0s, const double *cons, int64_t R,
+                        int generate, const double *X0, int phase1, int64_t num_iters, double viol_tol, double tol, uint64_t seed,
+                        uint64_t seed_stride, uint64_t first_index, double select_tol, int64_t *sweeps1, int64_t *sweeps2, int64_t *visits2,
+                        int64_t *accepted2, uint8_t *ran_phase2, int *status1, int *status2, double *f0, double *maxviol, double *X,
+                        int64_t *best_index, double *best_f0, double *best_maxviol, double *best_x) {
+    return cd_small_batch(c, CD_WIDE_MAXN, cons != nullptr, cons, B, P0s, q0s, r0s, R, generate, X0, phase1, num_iters, viol_tol, tol, seed, seed_stride,
+                          first_index, select_tol, sweeps1, sweeps2, visits2, accepted2, ran_phase2, status1, status2, f0, maxviol, X, best_index,
+                          best_f0, best_maxviol, best_x);
 }
 
 // ---- suggest(SDR) for B small problems (n <= 64) of the unit-diagonal family that share the context's constraints x_i^2 == d_i: the

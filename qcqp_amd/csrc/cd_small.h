@@ -12,6 +12,9 @@
 // (cptr, crel, maxc -- which coordinate a constraint touches, its relop) and problem b brings (p, q, r) of every constraint in
 // cons [B][m][3]; the ticket's workgroup stages them in LDS beside P0_b.  Restart (b, r) is then bit for bit the restart of the shared
 // call with B = 1 on a context created from problem b's own functions.
+//
+// 64 < n <= 128 (qcqpmi_cd_batch_run): the wide kernels cd_small_kernel<MAXC, pc, 2> -- one wavefront per (problem,
+// restart) as before, two coordinates per lane, the same LDS image (up to 144 392 bytes), the same parity statement.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -20,6 +23,11 @@
 namespace qcqpmi {
 
 constexpr int CD_SMALL_MAXN = 64;        // lane = coordinate: one wavefront holds a point
+constexpr int CD_WIDE_MAXN = 128;        // the wide kernels (cd_small_kernel<MAXC, pc, 2>): lane l holds coordinates l and l + 64
+// their largest workgroup: from n = 101 the LDS image lets ONE workgroup on a CU, so its size decides how many waves the CU holds (eight;
+// with __launch_bounds__(768) the kernels for one constraint per coordinate, at 168 VGPRs, spill 8 bytes per lane: DESIGN.md 4.12).
+// The launch takes 256 or 512 threads, whichever puts more waves on a CU (cd_small_workgroups).
+constexpr int CD_WIDE_THREADS = 512;
 
 struct CdSmallArgs {
     DevProblem P;                // n and the shared per-coordinate constraint lists (cptr / cp / cq / cr / crel); its objective is not read
@@ -45,10 +53,12 @@ struct CdSmallArgs {
 
 // pc_entries: 0, or the m list entries whose (p, q, r) the per-problem-constraint kernels stage beside P0_b and q0_b
 size_t cd_small_lds_bytes(int64_t n, int64_t pc_entries);
-// workgroups of the launch (persistent: at most what the device holds at once), or < 0: -hipError_t
-int cd_small_workgroups(int64_t n, int maxc, int64_t pc_entries, int64_t tickets, int device);
-int cd_small_launch(const CdSmallArgs &a, int maxc, int wgs, hipStream_t st);      // a.cons != nullptr: the <MAXC, pc> kernels
-const char *cd_small_name(int maxc, bool pc);
+// workgroups of the launch (persistent: at most what the device holds at once), or < 0: -hipError_t; *threads: the size of a workgroup
+// -- 256 for n <= CD_SMALL_MAXN; for the wide kernels 256 or CD_WIDE_THREADS, whichever the occupancy query gives more resident waves
+// (a tie goes to the larger one)
+int cd_small_workgroups(int64_t n, int maxc, int64_t pc_entries, int64_t tickets, int device, int *threads);
+int cd_small_launch(const CdSmallArgs &a, int maxc, int wgs, int threads, hipStream_t st);      // a.cons != nullptr: the <MAXC, pc> kernels
+const char *cd_small_name(int maxc, bool pc, bool wide);
 // the winners' points: out[b][0..n) = X[b][idx[2 b]][0..n)  (idx as select_best_kernel leaves it; < 0: row left as it is)
 int cd_small_gather_launch(const double *X, int64_t n, int64_t R, int64_t B, const int64_t *idx, double *out, hipStream_t st);
 

@@ -1,4 +1,4 @@
-// cd_small_kernel -- improve_coord_descent (qcqp.py:181-192) for a batch of SMALL problems (n <= 64) that share their separable
+// cd_small_kernel -- improve_coord_descent (qcqp.py:181-192) for a batch of SMALL problems (n <= 64; n <= 128 in the wide kernels below) that share their separable
 // constraints and differ in their objective, R restarts each, inside one persistent launch (cd_small.h); in the per-problem-constraint
 // mode (cd_small_kernel<MAXC, true>) they share the STRUCTURE of the lists and problem b's coefficients are staged with its objective.
 //
@@ -23,7 +23,20 @@
 //   results           objective (the same sum) and max violation of the final point, the counters of qcqpmi_cd_run, the point.
 // The scalar decision of a visit is computed by all 64 lanes on the same values: the layout spends lanes to keep the restart's
 // state in registers and its matrix in LDS; what runs in parallel are the waves (up to 16 per CU) and phase 1.
+//
+// WIDE KERNELS (cd_small_kernel<MAXC, pc, 2>, 64 < n <= 128, qcqpmi_cd_batch_run).  The same layout with TWO
+// coordinates per lane: lane l holds coordinate l in slot 0 and coordinate l + 64 in slot 1 (live where l + 64 < n); x, h, the diagonal,
+// q and the feasible set exist once per slot.  A visit of coordinate i reads slot i >> 6 (wave-uniform) at lane i & 63, its rank-one
+// update covers both slots (lane l reads words i n + l and i n + l + 64 of the image); the keyed draws go by the coordinate index; the
+// sums of the refresh run over k = 0..n-1 and j = 0..n-1 in ascending order across both slots -- the terms of improve_cd_sep, as before.
+// Phase 1 visits both coordinates of a lane, its reductions run over both slots, and status1 is that of the highest coordinate with a
+// code.  The image is the same (P0_b n x n, q0_b, [3][m] coefficients, two control words: at most 144 392 bytes, one workgroup per CU from
+// n = 101) and the workgroup has up to 512 threads.  With up to four constraints per coordinate the two FeasSet<4> of a lane do not fit
+// beside the visit: those kernels recompute coordinate i's set at its visit (same inputs, same code, same bits).  The slots are written
+// out (slot 0, then slot 1 under if constexpr) instead of looped over: with loops the W = 1 kernels came out as other code.
 #include "cd_small.h"
+
+#include <stdlib.h>
 
 #include "onevar.h"
 #include "cd_phase1_sep.h"
@@ -43,56 +56,106 @@ __device__ inline double sm_coord_viol(const DevProblem &P, int i, double xi) {
     return v;
 }
 
-// h (lane j) = sum_{k != j} P0[k][j] x_k in ascending k; returns f0(x) = sum_j (row_j + q_j) x_j + r0 in ascending j, row_j the
-// same sum with the diagonal term.  x is zero in the lanes >= n.
-__device__ inline double sm_refresh(const double *Ps, const double *qs, double r0, int n, int lane, double x, double &h) {
+// W = coordinates per lane (cd_small.h): lane l holds coordinate l in slot 0 and, in the wide kernels (W = 2), coordinate l + 64 in
+// slot 1.  The value of coordinate i, broadcast: slot i >> 6 (wave-uniform) at lane i & 63.
+template <int W>
+__device__ inline double sm_bcast(const double (&v)[W], int i) {
+    if constexpr (W == 1) return readlane_d(v[0], i);
+    else return readlane_d((i >> 6) ? v[1] : v[0], i & 63);
+}
+
+// h (coordinate j) = sum_{k != j} P0[k][j] x_k in ascending k; returns f0(x) = sum_j (row_j + q_j) x_j + r0 in ascending j, row_j the
+// same sum with the diagonal term.  x is zero in the slots whose coordinate is >= n.
+template <int W>
+__device__ inline double sm_refresh(const double *Ps, const double *qs, double r0, int n, int lane, const double (&x)[W], double (&h)[W]) {
+    // slot 0 is written out and slot 1 added under if constexpr (no loop over the slots): the W = 1 kernels stay the code they were
     const int lc = lane < n ? lane : 0;
-    double row = 0.0;
-    h = 0.0;
+    const int lc1 = lane + 64 < n ? lane + 64 : 0;
+    double row = 0.0, row1 = 0.0;
+    h[0] = 0.0;
+    if constexpr (W == 2) h[W - 1] = 0.0;
     for (int k = 0; k < n; k++) {
-        const double prod = Ps[k * n + lc] * readlane_d(x, k);
+        const double xk = sm_bcast<W>(x, k);
+        const double prod = Ps[k * n + lc] * xk;
         row += prod;
-        h = (k == lane) ? h : h + prod;
+        h[0] = (k == lane) ? h[0] : h[0] + prod;
+        if constexpr (W == 2) {
+            const double prod1 = Ps[k * n + lc1] * xk;
+            row1 += prod1;
+            h[W - 1] = (k == lane + 64) ? h[W - 1] : h[W - 1] + prod1;
+        }
     }
-    const double term = (row + qs[lc]) * x;
+    double term[W];
+    term[0] = (row + qs[lc]) * x[0];
+    if constexpr (W == 2) term[W - 1] = (row1 + qs[lc1]) * x[W - 1];
     double acc = 0.0;
-    for (int k = 0; k < n; k++) acc += readlane_d(term, k);
+    for (int k = 0; k < n; k++) acc += sm_bcast<W>(term, k);
     return acc + r0;
+}
+
+// max violation of the point: a wave maximum of the own constraints of every coordinate the lanes hold
+template <int W>
+__device__ inline double sm_point_viol(const DevProblem &P, int n, int lane, const double (&x)[W]) {
+    double v = -QM_INF;
+#pragma unroll
+    for (int s = 0; s < W; s++) {
+        const int j = lane + 64 * s;
+        if (j < n) {
+            const double w = sm_coord_viol(P, j, x[s]);
+            v = (s == 0 || w > v) ? w : v;
+        }
+    }
+    return wave_max(v);
 }
 
 // a.P: the constraint lists the restart reads -- the context's, or the view of problem b's staged coefficients (cd_small_kernel).
 // PC only names the caller: every kernel keeps an instance of its own, inlined as the single-caller function it was.
-template <int MAXC, bool PC>
+template <int MAXC, bool PC, int W>
 __device__ inline void sm_restart(const CdSmallArgs &a, const double *Ps, const double *qs, int64_t b, int64_t r, int lane) {
     const DevProblem &P = a.P;
     const int n = (int)P.n;
-    const bool on = lane < n;
-    const int lc = on ? lane : 0;
     const uint64_t seed = a.seed + (uint64_t)b * a.seed_stride;
     const uint64_t gr = a.first_index + (uint64_t)r;
     const int64_t o = b * a.R + r;
     const double r0 = a.r0s[b];
-    double x = 0.0;
-    if (on) x = a.generate ? keyed_normal(seed, gr, (uint64_t)lane) : a.X0[o * n + lane];
+    bool on[W];
+    int jc[W];
+    double x[W];
+    on[0] = lane < n;
+    jc[0] = on[0] ? lane : 0;
+    x[0] = 0.0;
+    if (on[0]) x[0] = a.generate ? keyed_normal(seed, gr, (uint64_t)lane) : a.X0[o * n + lane];
+    if constexpr (W == 2) {      // the keyed draws go by the coordinate, not the lane
+        on[W - 1] = lane + 64 < n;
+        jc[W - 1] = on[W - 1] ? lane + 64 : 0;
+        x[W - 1] = 0.0;
+        if (on[W - 1]) x[W - 1] = a.generate ? keyed_normal(seed, gr, (uint64_t)(lane + 64)) : a.X0[o * n + lane + 64];
+    }
 
-    // ---- phase 1 (qcqp.py:101-149): the loop of cd_phase1_sep_kernel for one restart, a coordinate per lane
+    // ---- phase 1 (qcqp.py:101-149): the loop of cd_phase1_sep_kernel for one restart; a lane visits the coordinates it holds
     int64_t sweeps1 = 0;
     int st1 = 0;
     if (a.phase1) {
-        int my_status = 0;
+        int my_status[W];
+#pragma unroll
+        for (int s = 0; s < W; s++) my_status[s] = 0;
         bool fin = false;
         for (int64_t t = 0; t < a.num_iters && !fin; t++) {
             sweeps1++;
             double vmax = -QM_INF;
             bool upd = false;
-            if (on) {
-                double xi = x;
-                P1Visit V;
-                p1_sep_visit<MAXC>(P, lane, xi, a.tol, a.viol_tol, seed, gr, t, V);
-                if (V.status) my_status = V.status;
-                if (V.visited) {
-                    if (V.moved) { x = xi; upd = true; }
-                    vmax = V.vafter;
+#pragma nounroll
+            for (int s = 0; s < W; s++) {      // one copy of the visit's code: the slot is picked with selects
+                const bool live = (W == 1 || s == 0) ? on[0] : on[W - 1];
+                if (live) {
+                    double xi = (W == 1 || s == 0) ? x[0] : x[W - 1];
+                    P1Visit V;
+                    p1_sep_visit<MAXC>(P, lane + 64 * s, xi, a.tol, a.viol_tol, seed, gr, t, V);
+                    if (V.status) { if (W == 1 || s == 0) my_status[0] = V.status; else my_status[W - 1] = V.status; }
+                    if (V.visited) {
+                        if (V.moved) { if (W == 1 || s == 0) x[0] = xi; else x[W - 1] = xi; upd = true; }
+                        vmax = (s == 0 || !(V.vafter <= vmax)) ? V.vafter : vmax;
+                    }
                 }
             }
             const double v = wave_max(vmax);
@@ -100,36 +163,68 @@ __device__ inline void sm_restart(const CdSmallArgs &a, const double *Ps, const 
             // done when feasible enough (qcqp.py:111); a sweep without an update is a fixed point
             fin = v < a.viol_tol || !u;
         }
-        const unsigned long long bad = __builtin_amdgcn_ballot_w64(my_status != 0);
-        if (bad) st1 = __builtin_amdgcn_readlane(my_status, 63 - __builtin_clzll(bad));      // the highest coordinate's, like the serial kernel
+        // the highest coordinate's, like the serial kernel: a coordinate of slot 1 lies above every coordinate of slot 0
+#pragma unroll
+        for (int s = W - 1; s >= 0; s--) {
+            const unsigned long long bad = __builtin_amdgcn_ballot_w64(my_status[s] != 0);
+            if (bad && st1 == 0) st1 = __builtin_amdgcn_readlane(my_status[s], 63 - __builtin_clzll(bad));
+        }
     }
 
     // ---- gate (qcqp.py:189); the max violation is also the slack phase 2 fixes (qcqp.py:157)
-    const double slack = wave_max(on ? sm_coord_viol(P, lane, x) : -QM_INF);
+    const double slack = sm_point_viol<W>(P, n, lane, x);
     const bool ran2 = st1 == 0 && slack < a.viol_tol;
 
     // ---- phase 2 (qcqp.py:152-178)
     ChainState S;
     S.fcur = 0.0; S.upd_counter = 0; S.visits = 0; S.accepted = 0; S.sweeps = 0; S.conv = !ran2; S.status = 0;
     if (ran2) {
-        FeasSet<MAXC> Cm;
-        Cm.n = 0;
+        // the feasible sets at the fixed slack: in registers, one per slot -- except in the wide kernels with up to four constraints
+        // per coordinate, where two FeasSet<4> do not fit beside the visit: those recompute coordinate i's set at its visit (the same
+        // inputs through the same code: the same bits)
+        constexpr bool KEEP = W == 1 || MAXC <= 1;
+        FeasSet<MAXC> Cm[KEEP ? W : 1];
+        double dg[W], ql[W];
+        if constexpr (KEEP) {
+            Cm[0].n = 0;
 #pragma unroll
-        for (int j = 0; j <= MAXC; j++) { Cm.lo[j] = 0.0; Cm.hi[j] = 0.0; }
-        if (on) compute_set<MAXC>(P, lane, slack, Cm);
-        const double dg = Ps[lc * n + lc], ql = qs[lc];
+            for (int j = 0; j <= MAXC; j++) { Cm[0].lo[j] = 0.0; Cm[0].hi[j] = 0.0; }
+            if (on[0]) compute_set<MAXC>(P, lane, slack, Cm[0]);
+        }
+        dg[0] = Ps[jc[0] * n + jc[0]]; ql[0] = qs[jc[0]];
+        if constexpr (W == 2) {
+            if constexpr (KEEP) {
+                Cm[W - 1].n = 0;
+#pragma unroll
+                for (int j = 0; j <= MAXC; j++) { Cm[W - 1].lo[j] = 0.0; Cm[W - 1].hi[j] = 0.0; }
+                if (on[W - 1]) compute_set<MAXC>(P, lane + 64, slack, Cm[W - 1]);
+            }
+            dg[W - 1] = Ps[jc[W - 1] * n + jc[W - 1]]; ql[W - 1] = qs[jc[W - 1]];
+        }
         for (int64_t t = 0; t < a.num_iters && !S.conv; t++) {
             S.sweeps++;
-            double h;
-            S.fcur = sm_refresh(Ps, qs, r0, n, lane, x, h);
+            double h[W];
+            S.fcur = sm_refresh<W>(Ps, qs, r0, n, lane, x, h);
             for (int i = 0; i < n; i++) {
-                const double xi = readlane_d(x, i), t2 = readlane_d(dg, i);
-                const double t1 = 2.0 * readlane_d(h, i) + readlane_d(ql, i);
+                const double xi = sm_bcast<W>(x, i), t2 = sm_bcast<W>(dg, i);
+                const double t1 = 2.0 * sm_bcast<W>(h, i) + sm_bcast<W>(ql, i);
                 const double t0 = S.fcur - xi * (t2 * xi + t1);
                 FeasSet<MAXC> C;
-                C.n = __builtin_amdgcn_readlane(Cm.n, i);
+                if constexpr (!KEEP) {
+                    compute_set<MAXC>(P, i, slack, C);
+                } else if constexpr (W == 1) {
+                    C.n = __builtin_amdgcn_readlane(Cm[0].n, i);
 #pragma unroll
-                for (int j = 0; j <= MAXC; j++) { C.lo[j] = readlane_d(Cm.lo[j], i); C.hi[j] = readlane_d(Cm.hi[j], i); }
+                    for (int j = 0; j <= MAXC; j++) { C.lo[j] = readlane_d(Cm[0].lo[j], i); C.hi[j] = readlane_d(Cm[0].hi[j], i); }
+                } else {
+                    const bool hi = (i >> 6) != 0;
+                    C.n = __builtin_amdgcn_readlane(hi ? Cm[W - 1].n : Cm[0].n, i & 63);
+#pragma unroll
+                    for (int j = 0; j <= MAXC; j++) {
+                        C.lo[j] = readlane_d(hi ? Cm[W - 1].lo[j] : Cm[0].lo[j], i & 63);
+                        C.hi[j] = readlane_d(hi ? Cm[W - 1].hi[j] : Cm[0].hi[j], i & 63);
+                    }
+                }
                 DrawKey dk{seed, gr, (uint32_t)i, (uint32_t)t | 0x80000000u, 0u};
                 double xn = xi;
                 const int got = onevar_minimise<MAXC>(t2, t1, t0, C, dk, &xn);
@@ -137,9 +232,12 @@ __device__ inline void sm_restart(const CdSmallArgs &a, const double *Ps, const 
                 double delta;
                 chain_commit<MAXC>(S, got, xn, xi, t2, t1, t0, a.tol, n, moved, delta);
                 if (moved) {      // rank-one update along column i (= row i of the symmetric image)
-                    const double pij = Ps[i * n + lc];
-                    h = (lane == i) ? h : h + pij * delta;
-                    x = (lane == i) ? xn : x;
+#pragma unroll
+                    for (int s = 0; s < W; s++) {
+                        const double pij = Ps[i * n + jc[s]];
+                        h[s] = (lane + 64 * s == i) ? h[s] : h[s] + pij * delta;
+                        x[s] = (lane + 64 * s == i) ? xn : x[s];
+                    }
                 }
                 if (S.conv) break;
             }
@@ -147,9 +245,9 @@ __device__ inline void sm_restart(const CdSmallArgs &a, const double *Ps, const 
     }
 
     // ---- results: objective and max violation of the final point; a restart on which the reference raises never wins
-    double hh;
-    double f = sm_refresh(Ps, qs, r0, n, lane, x, hh);
-    double mv = wave_max(on ? sm_coord_viol(P, lane, x) : -QM_INF);
+    double hh[W];
+    double f = sm_refresh<W>(Ps, qs, r0, n, lane, x, hh);
+    double mv = sm_point_viol<W>(P, n, lane, x);
     if (st1 != 0 || S.status != 0) { f = QM_INF; mv = QM_INF; }
     if (lane == 0) {
         a.sweeps1[o] = sweeps1; a.sweeps2[o] = S.sweeps; a.visits2[o] = S.visits; a.accepted2[o] = S.accepted;
@@ -157,17 +255,22 @@ __device__ inline void sm_restart(const CdSmallArgs &a, const double *Ps, const 
         a.status1[o] = st1; a.status2[o] = S.status;
         a.f0[o] = f; a.maxviol[o] = mv;
     }
-    if (on) a.X[o * n + lane] = x;
+    if (on[0]) a.X[o * n + lane] = x[0];
+    if constexpr (W == 2) {
+        if (on[W - 1]) a.X[o * n + lane + 64] = x[W - 1];
+    }
 }
 
 // PC: per-problem constraint coefficients (cd_small.h).  The ticket's workgroup stages problem b's (p, q, r) of every list entry in
 // LDS beside P0_b and q0_b -- entry e of the context's lists (cptr order) is constraint cidx[e] of a.cons [B][m][3] -- and its waves
 // read their lists through the kernel's copy of the context's DevProblem, whose cp / cq / cr point at that image: cptr and crel stay
 // the context's, and the visit arithmetic is the one copy above.
-template <int MAXC, bool PC = false>
-__global__ __launch_bounds__(256) void cd_small_kernel(CdSmallArgs a) {
+// W = 2: the wide kernels (64 < n <= 128).  Their workgroup is CD_WIDE_THREADS threads or fewer (the launch decides; blockDim.x).
+template <int MAXC, bool PC = false, int W = 1>
+__global__ __launch_bounds__(W == 1 ? 256 : CD_WIDE_THREADS) void cd_small_kernel(CdSmallArgs a) {
     extern __shared__ double sm_lds[];
     const int n = (int)a.P.n, m = PC ? (int)a.P.m : 0;
+    const int nt = W == 1 ? 256 : (int)blockDim.x;
     double *Ps = sm_lds, *qs = sm_lds + n * n;
     double *cs = qs + n;             // PC: [3][m] the staged coefficients, p then q then r
     int *ctl = (int *)(cs + 3 * m);  // [0] the workgroup's ticket, [1] next restart of its chunk
@@ -187,11 +290,11 @@ __global__ __launch_bounds__(256) void cd_small_kernel(CdSmallArgs a) {
         const int64_t b = tk / a.chunks, r_lo = (tk % a.chunks) * a.RC;
         const int64_t r_hi = r_lo + a.RC < a.R ? r_lo + a.RC : a.R;
         const double *Pg = a.P0s + b * n * n;
-        for (int e = tid; e < n * n; e += 256) Ps[e] = Pg[e];
+        for (int e = tid; e < n * n; e += nt) Ps[e] = Pg[e];
         if (tid < n) qs[tid] = a.q0s[b * n + tid];
         if constexpr (PC) {
             const double *cg = a.cons + b * m * 3;
-            for (int e = tid; e < m; e += 256) {
+            for (int e = tid; e < m; e += nt) {
                 const double *ck = cg + (cidx[e] - 1) * 3;
                 cs[e] = ck[0]; cs[m + e] = ck[1]; cs[2 * m + e] = ck[2];
             }
@@ -199,7 +302,7 @@ __global__ __launch_bounds__(256) void cd_small_kernel(CdSmallArgs a) {
         __syncthreads();
         // the visits read column i as row i: a matrix that is not symmetric (or holds a NaN) makes the call fail
         bool asym = false;
-        for (int e = tid; e < n * n; e += 256) {
+        for (int e = tid; e < n * n; e += nt) {
             const int i = e / n, j = e - i * n;
             asym = asym || (j > i && !(Ps[e] == Ps[j * n + i]));
         }
@@ -209,7 +312,7 @@ __global__ __launch_bounds__(256) void cd_small_kernel(CdSmallArgs a) {
             if (lane == 0) k = atomicAdd(&ctl[1], 1);
             k = __builtin_amdgcn_readfirstlane(k);
             if (r_lo + k >= r_hi) break;
-            sm_restart<MAXC, PC>(a, Ps, qs, b, r_lo + k, lane);
+            sm_restart<MAXC, PC, W>(a, Ps, qs, b, r_lo + k, lane);
         }
     }
 }
@@ -225,34 +328,81 @@ __global__ void cd_small_gather_kernel(const double *__restrict__ X, int64_t n, 
 
 size_t cd_small_lds_bytes(int64_t n, int64_t pc_entries) { return (size_t)(n * n + n + 3 * pc_entries) * sizeof(double) + 2 * sizeof(int); }
 
-int cd_small_workgroups(int64_t n, int maxc, int64_t pc_entries, int64_t tickets, int device) {
+namespace {
+
+typedef void (*CdSmallKernel)(CdSmallArgs);
+
+CdSmallKernel cd_small_pick(int64_t n, int maxc, bool pc) {
+    if (n > CD_SMALL_MAXN) {
+        if (pc) return maxc <= 1 ? cd_small_kernel<1, true, 2> : cd_small_kernel<4, true, 2>;
+        return maxc <= 1 ? cd_small_kernel<1, false, 2> : cd_small_kernel<4, false, 2>;
+    }
+    if (pc) return maxc <= 1 ? cd_small_kernel<1, true> : cd_small_kernel<4, true>;
+    return maxc <= 1 ? cd_small_kernel<1> : cd_small_kernel<4>;
+}
+
+}  // namespace
+
+// QCQPMI_CD_WIDE_THREADS = 64 .. 512 (a multiple of 64): that workgroup size for the wide kernels instead of the rule below -- for
+// measuring the rule (tools/bench_small_batch.py --wide-threads); results do not depend on it
+static int cd_wide_threads_asked() {
+    static const int asked = [] {
+        const char *v = getenv("QCQPMI_CD_WIDE_THREADS");
+        const int t = v ? atoi(v) : 0;
+        return (t >= 64 && t <= CD_WIDE_THREADS && t % 64 == 0) ? t : 0;
+    }();
+    return asked;
+}
+
+int cd_small_workgroups(int64_t n, int maxc, int64_t pc_entries, int64_t tickets, int device, int *threads) {
     int cus = 0, per = 0;
     hipError_t e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device);
     if (e != hipSuccess) return -(int)e;
     const size_t lds = cd_small_lds_bytes(n, pc_entries);
-    if (pc_entries > 0)
-        e = (maxc <= 1) ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, cd_small_kernel<1, true>, 256, lds)
-                        : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, cd_small_kernel<4, true>, 256, lds);
-    else
-        e = (maxc <= 1) ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, cd_small_kernel<1>, 256, lds)
-                        : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, cd_small_kernel<4>, 256, lds);
-    if (e != hipSuccess) return -(int)e;
+    const CdSmallKernel k = cd_small_pick(n, maxc, pc_entries > 0);
+    *threads = 256;
+    if (n > CD_SMALL_MAXN) {      // the image passes 64 KB from n = 91
+        e = hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return -(int)e;
+        // the workgroup that puts more waves on a CU: while three images fit a CU (n = 72: 41 KB each) four waves of each beat the eight
+        // of one workgroup; from n = 101 there is one image and eight waves beat four (measured: profiles/r12_wide_batch.md)
+        const int asked = cd_wide_threads_asked();
+        int per_small = 0, per_large = 0;
+        e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_small, k, asked ? asked : 256, lds);
+        if (e != hipSuccess) return -(int)e;
+        per = per_small;
+        *threads = asked ? asked : 256;
+        if (!asked) {
+            e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_large, k, CD_WIDE_THREADS, lds);
+            if (e != hipSuccess) return -(int)e;
+            if (per_large * CD_WIDE_THREADS >= per_small * 256) { per = per_large; *threads = CD_WIDE_THREADS; }
+        }
+    } else {
+        e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, k, 256, lds);
+        if (e != hipSuccess) return -(int)e;
+    }
     if (per < 1) per = 1;
     const int64_t cap = (int64_t)cus * per;
     return (int)(tickets < cap ? tickets : cap);
 }
 
-int cd_small_launch(const CdSmallArgs &a, int maxc, int wgs, hipStream_t st) {
+int cd_small_launch(const CdSmallArgs &a, int maxc, int wgs, int threads, hipStream_t st) {
     const bool pc = a.cons != nullptr;
     const size_t lds = cd_small_lds_bytes(a.P.n, pc ? a.P.m : 0);
-    if (pc && maxc <= 1) hipLaunchKernelGGL((cd_small_kernel<1, true>), dim3((unsigned)wgs), dim3(256), lds, st, a);
-    else if (pc) hipLaunchKernelGGL((cd_small_kernel<4, true>), dim3((unsigned)wgs), dim3(256), lds, st, a);
-    else if (maxc <= 1) hipLaunchKernelGGL(cd_small_kernel<1>, dim3((unsigned)wgs), dim3(256), lds, st, a);
-    else hipLaunchKernelGGL(cd_small_kernel<4>, dim3((unsigned)wgs), dim3(256), lds, st, a);
+    const CdSmallKernel k = cd_small_pick(a.P.n, maxc, pc);
+    if (a.P.n > CD_SMALL_MAXN) {
+        const hipError_t e = hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return (int)e;
+    }
+    hipLaunchKernelGGL(k, dim3((unsigned)wgs), dim3((unsigned)threads), lds, st, a);
     return (int)hipGetLastError();
 }
 
-const char *cd_small_name(int maxc, bool pc) {
+const char *cd_small_name(int maxc, bool pc, bool wide) {
+    if (wide) {
+        if (pc) return maxc <= 1 ? "cd_small_kernel<1,pc,w2>" : "cd_small_kernel<4,pc,w2>";
+        return maxc <= 1 ? "cd_small_kernel<1,w2>" : "cd_small_kernel<4,w2>";
+    }
     if (pc) return maxc <= 1 ? "cd_small_kernel<1,pc>" : "cd_small_kernel<4,pc>";
     return maxc <= 1 ? "cd_small_kernel<1>" : "cd_small_kernel<4>";
 }

@@ -223,20 +223,35 @@ class Engine(object):
         cons (B, m, 3): PER-PROBLEM constraint coefficients (qcqpmi_cd_small_batch_run_pc) -- (p, q, r) of constraint k of problem b
         on the coordinate and with the relop constraint k has in this context; restart (b, r) is then bit for bit the restart of a
         batch of one on a context built from problem b's own functions.  None: the context's constraints for every problem."""
+        return self._cd_batch('cd_small_batch_run', P0s, q0s, r0s, R, X0, phase1, num_iters, viol_tol, tol, seed, seed_stride, first_index,
+                              select_tol, want_x, cons)
+
+    def cd_batch_run(self, P0s, q0s, r0s, R, X0=None, phase1=True, num_iters=1000, viol_tol=1e-2, tol=1e-4, seed=0, seed_stride=1,
+                     first_index=0, select_tol=1e-4, want_x=True, cons=None):
+        """cd_small_batch_run for problems of up to 128 variables (qcqpmi_cd_batch_run): the same arguments, the same dictionary.
+        n <= 64 runs exactly the launch of cd_small_batch_run (same kernel, same bits); 65 <= n <= 128 runs the wide kernels
+        cd_small_kernel<MAXC[,pc],w2> -- one wavefront per (problem, restart), two coordinates per lane -- with the same parity
+        statement: restart (b, r) is restart r of randn + cd_run on a context that holds problem b, and depends on (objective b,
+        constraints b, seed of b, global index) alone."""
+        return self._cd_batch('cd_batch_run', P0s, q0s, r0s, R, X0, phase1, num_iters, viol_tol, tol, seed, seed_stride, first_index,
+                              select_tol, want_x, cons)
+
+    def _cd_batch(self, name, P0s, q0s, r0s, R, X0, phase1, num_iters, viol_tol, tol, seed, seed_stride, first_index, select_tol, want_x,
+                  cons):
         P0s = np.ascontiguousarray(P0s, dtype=np.float64)
         q0s = np.ascontiguousarray(q0s, dtype=np.float64)
         r0s = np.ascontiguousarray(r0s, dtype=np.float64).ravel()
         B, R, n = int(P0s.shape[0]) if P0s.ndim == 3 else 0, int(R), self.n
         if P0s.shape != (B, n, n) or q0s.shape != (B, n) or r0s.shape != (B,):
-            raise ValueError('cd_small_batch_run: expected P0s (B, n, n), q0s (B, n), r0s (B,) with n = %d' % n)
+            raise ValueError('%s: expected P0s (B, n, n), q0s (B, n), r0s (B,) with n = %d' % (name, n))
         if X0 is not None:
             X0 = np.ascontiguousarray(X0, dtype=np.float64)
             if X0.shape != (B, R, n):
-                raise ValueError('cd_small_batch_run: expected X0 of shape (B, R, n)')
+                raise ValueError('%s: expected X0 of shape (B, R, n)' % name)
         if cons is not None:
             cons = np.ascontiguousarray(cons, dtype=np.float64)
             if cons.shape != (B, self.m, 3):
-                raise ValueError('cd_small_batch_run: expected cons of shape (B, m, 3) with m = %d' % self.m)
+                raise ValueError('%s: expected cons of shape (B, m, 3) with m = %d' % (name, self.m))
         T = B * R
         out = dict(sweeps1=np.zeros(T, dtype=np.int64), sweeps2=np.zeros(T, dtype=np.int64), visits2=np.zeros(T, dtype=np.int64),
                    accepted2=np.zeros(T, dtype=np.int64), ran_phase2=np.zeros(T, dtype=np.uint8), status1=np.zeros(T, dtype=np.int32),
@@ -248,7 +263,9 @@ class Engine(object):
                 _ip(out['accepted2']), _bp(out['ran_phase2']), out['status1'].ctypes.data_as(c_intp), out['status2'].ctypes.data_as(c_intp),
                 _dp(out['f0']), _dp(out['maxviol']), _dp(out['X']), _ip(out['best_index']), _dp(out['best_f0']), _dp(out['best_maxviol']),
                 _dp(out['best_x']))
-        if cons is None:
+        if name == 'cd_batch_run':
+            self._chk(self.L.qcqpmi_cd_batch_run(self.h, B, _dp(P0s), _dp(q0s), _dp(r0s), _dp(cons), *tail))
+        elif cons is None:
             self._chk(self.L.qcqpmi_cd_small_batch_run(self.h, B, _dp(P0s), _dp(q0s), _dp(r0s), *tail))
         else:
             self._chk(self.L.qcqpmi_cd_small_batch_run_pc(self.h, B, _dp(P0s), _dp(q0s), _dp(r0s), _dp(cons), *tail))

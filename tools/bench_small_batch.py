@@ -13,6 +13,10 @@ after a warm-up (for rocprofv3 --kernel-trace --stats).
 with bounds per instance -- and the batched call is qcqpmi_cd_small_batch_run_pc (Engine.cd_small_batch_run(cons=...)).  The loop is the
 best the library offered for such a batch before: per problem a fresh context from the problem's own functions and ONE call of
 qcqpmi_cd_small_batch_run with B = 1 (bit for bit the same restarts), timed on --loop-problems problems and scaled linearly to B.
+
+--n above 64 (up to 128): the batched call is qcqpmi_cd_batch_run (Engine.cd_batch_run, the wide kernels: two coordinates per lane), e.g.
+--n 128 --m 192 --B 1024 --loop-problems 64 for a frame of 64 x 64 QPSK MIMO detection problems; the loop is the same as for n <= 64.
+--wide-threads T: the wide kernels' workgroup size for this run (QCQPMI_CD_WIDE_THREADS; the library's choice is 512).
 """
 import argparse
 import json
@@ -35,7 +39,10 @@ def main():
     ap.add_argument('--seed', type=int, default=1)
     ap.add_argument('--profile-run', action='store_true')
     ap.add_argument('--per-problem-constraints', action='store_true')
+    ap.add_argument('--wide-threads', type=int, default=0)
     args = ap.parse_args()
+    if args.wide_threads:
+        os.environ['QCQPMI_CD_WIDE_THREADS'] = str(args.wide_threads)      # read once, by the first wide launch
 
     from qcqp_amd import problems
     from qcqp_amd.batch import QCQPBatch
@@ -53,9 +60,11 @@ def main():
     e = qb.engine
     kw = dict(cons=qb.cons) if pc else {}
 
+    run = e.cd_small_batch_run if args.n <= 64 else e.cd_batch_run
+
     def batched():
         t0 = time.perf_counter()
-        o = e.cd_small_batch_run(qb.P0s, qb.q0s, qb.r0s, args.R, num_iters=args.num_iters, seed=args.seed, seed_stride=1, want_x=False, **kw)
+        o = run(qb.P0s, qb.q0s, qb.r0s, args.R, num_iters=args.num_iters, seed=args.seed, seed_stride=1, want_x=False, **kw)
         return time.perf_counter() - t0, o
 
     batched()                                       # warm-up: code object, buffers
@@ -78,8 +87,8 @@ def main():
         for b in range(nl):
             eb = Engine(QCQPForm.from_arrays(fl[b]))
             if pc:
-                ob = eb.cd_small_batch_run(qb.P0s[b:b + 1], qb.q0s[b:b + 1], qb.r0s[b:b + 1], args.R, num_iters=args.num_iters,
-                                           seed=args.seed + b, want_x=False)
+                ob = (eb.cd_small_batch_run if args.n <= 64 else eb.cd_batch_run)(qb.P0s[b:b + 1], qb.q0s[b:b + 1], qb.r0s[b:b + 1], args.R,
+                                                                                  num_iters=args.num_iters, seed=args.seed + b, want_x=False)
                 best.append((int(ob['best_index'][0]), float(ob['best_f0'][0])))
             else:
                 eb.randn(args.R, seed=args.seed + b)
@@ -94,6 +103,7 @@ def main():
     agree = sum(1 for b in range(nl) if int(o['best_index'][b]) == best[b][0] and abs(o['best_f0'][b] - best[b][1]) <= 1e-9 * (1 + abs(best[b][1])))
     print(json.dumps(dict(
         workload=dict(family='boxpp' if pc else 'bls', B=args.B, n=args.n, m=args.m, R=args.R, num_iters=args.num_iters), kernel=e.last_cd_kernel(),
+        wide_threads=args.wide_threads or None,
         batched_s=t_batched, batched_all_s=times, batched_kernel_ms=kernel_ms, restart_sweeps=sweeps,
         restart_sweeps_per_s=sweeps / t_batched, loop_problems=nl, loop_s_measured=t_loop,
         loop_s_scaled_to_B=t_loop * args.B / nl, speedup=(t_loop * args.B / nl) / t_batched, winners_agree='%d/%d' % (agree, nl))))
