@@ -444,6 +444,40 @@ int qcqpmi_sdr_small_batch(qcqpmi_ctx *ctx, int64_t B, const double *P0s, const 
 int qcqpmi_sdr_small_batch_pc(qcqpmi_ctx *ctx, int64_t B, const double *P0s, const double *q0s, const double *r0s, const double *ds,
                               int64_t S, int max_sweeps, double tol, uint64_t seed, uint64_t seed_stride, uint64_t first_index,
                               const double *V0s, double *V, double *primal, double *y, int64_t *sweeps, double *X);
+/* IMPROVE(ADMM) FOR MANY SMALL PROBLEMS IN ONE LAUNCH (added within ABI 6: a new symbol, nothing else changes).  The batch of
+ * qcqpmi_cd_small_batch_run -- B objectives P0s [B][n][n] (each symmetric), q0s [B][n], r0s [B] over this context's separable
+ * constraint lists (up to four per coordinate, m >= 1 in all), 1 <= n <= 64 -- through improve_admm (qcqp.py:254-285): phase 1, x1 =
+ * better(x0, z1), phase 2 with its bestx bookkeeping, better(x1, bestx); R restarts per problem, no host in the loop.  cons == NULL:
+ * the context's coefficients for every problem; else [B][m][3] as qcqpmi_cd_small_batch_run_pc takes them.  rhos [B]: problem b's
+ * penalty (the caller applies the rule of qcqp.py:261-278); Minvs [B][n][n]: (2 (P0_b + rho_b m I))^-1, symmetric.
+ * Restart (b, r) starts from the keyed normals (seed + b seed_stride, first_index + r) of qcqpmi_pop_randn, or from X0 [B][R][n]
+ * (generate = 0).  The loop, its exits and its iteration counts are those of the reference: phase 1 ends when the max violation of z
+ * is < tol (iters1 = z-updates made; 0 for a start that is feasible enough, which is returned as it is), phase 2 ends after the
+ * iteration in which |last_z - z| < tol or max violation > viol_lim (iters2 = iterations made, that one included), both at num_iters.
+ * Separable constraints move one coordinate each: a lane holds z_i, one dual per constraint on its coordinate and the sum of their
+ * operands (the state of the unit-bases path of qcqpmi_admm_run, same expressions); every projection is the reference's bracket and
+ * bisection to 1e-6 on one row, bracket from p as qcqpmi_admm_set_basis derives it.  z = Minv_b (2 rho_b (S + m z) - q0_b) is summed
+ * in ascending index order; f0 of a phase-2 iterate comes from the solve's right-hand side, the objective of the start, of the
+ * phase-1 result and of the reported point from P0_b itself.
+ * PARITY.  The iteration is the reference's up to the rounding of its sums; on constraints x_i^2 == d a last-bit difference doubles
+ * with every iteration, so agreement with the reference is to 1e-9 for a few iterations per phase and a median
+ * statement beyond.  A result depends on (problem b, rho_b, Minv_b, seed of b, global index) alone -- not on B, the neighbours, the
+ * order of the problems, the workgroups or a split of the restarts over calls: bit for bit.  With cons, restart (b, r) is bit for bit
+ * the restart of the call with B = 1, cons == NULL on a context created from problem b's own functions.
+ * One persistent launch of admm_small_kernel (csrc/admm_small.hip): one wavefront per (problem, restart), lane = coordinate, Minv_b
+ * (and b's coefficients) staged in LDS once per workgroup.  Outputs, any may be NULL: per restart [B R] (problem-major) iters1,
+ * iters2, f0, maxviol and the points X [B][R][n]; per problem [B] the best restart as qcqpmi_cd_small_batch_run reports it.
+ * qcqpmi_last_admm_kernel: "admm_small_kernel<1>" / "<4>" / "<1,pc>" / "<4,pc>" (workgroups per tile: 0).
+ * Refusals, before any launch where the host can see them; the resident population, its evaluation, an installed ADMM basis and
+ * qcqpmi_last_cd_kernel stay as they were, whether the call succeeds or is refused.  QCQPMI_EUNSUPPORTED: n > 64, constraints that are
+ * not separable.  QCQPMI_EINVAL: B < 1, R < 1, B R >= 2^30, num_iters < 0, no constraint, a missing array, a rhos entry that is not
+ * positive and finite, a cons entry that is not finite or has p == q == 0, a P0_b or Minv_b that is not symmetric (found while staging:
+ * the call fails after its launch and returns no results). */
+int qcqpmi_admm_small_batch_run(qcqpmi_ctx *ctx, int64_t B, const double *P0s, const double *q0s, const double *r0s, const double *cons,
+                                const double *rhos, const double *Minvs, int64_t R, int generate, const double *X0, int phase1,
+                                int64_t num_iters, double tol, double viol_lim, uint64_t seed, uint64_t seed_stride,
+                                uint64_t first_index, double select_tol, int64_t *iters1, int64_t *iters2, double *f0, double *maxviol,
+                                double *X, int64_t *best_index, double *best_f0, double *best_maxviol, double *best_x);
 /* Device and pinned-host buffers for a qcqpmi_cd_stream_run(K, R) to come (population, per-restart outputs, per-population
  * winners): allocation only, so that a timed or latency-sensitive run does not start with hipMalloc / hipHostMalloc.  A
  * resident population smaller than K R points is dropped (like any reallocation of the population). */

@@ -4,7 +4,9 @@ A frame of MIMO detection problems is thousands of independent Boolean least squ
 instance has its own objective and all of them the constraints x_i^2 == 1.  ``QCQP`` holds one problem per context; this class
 holds B of them on ONE context and runs suggest(RANDOM) + improve(COORD_DESCENT) for all B x R restarts through one persistent
 kernel (``Engine.cd_small_batch_run``, qcqpmi_cd_small_batch_run; for 64 < n <= 128 ``Engine.cd_batch_run``, qcqpmi_cd_batch_run: the
-wide kernels, two coordinates per lane).  suggest(SDR) -- for constraints x_i^2 == d_i -- solves the
+wide kernels, two coordinates per lane).  improve(ADMM) -- n <= 64 -- runs the reference's consensus ADMM for all B x R restarts in
+one launch too (``Engine.admm_small_batch_run``, qcqpmi_admm_small_batch_run), with rho per problem by the reference's rule and
+(2 (P0_b + rho_b m I))^-1 from one batched host inverse.  suggest(SDR) -- for constraints x_i^2 == d_i -- solves the
 semidefinite relaxation of all B problems and draws their samples in one launch as well (``Engine.sdr_small_batch``,
 qcqpmi_sdr_small_batch) and publishes the certified bounds in ``sdr_bound``; improve() then starts from the samples.  Problem b's results are those of
 ``QCQP(Problem(funcs_b))`` with suggest(RANDOM, num_samples=R, seed=seed + b seed_stride, first_index=...) followed by
@@ -20,6 +22,8 @@ per-problem coefficients.  suggest(SDR) is defined for n <= 64 (the relaxation's
     batch.x                                        # (B, n)
     batch.suggest(s.SDR, num_samples=64, seed=7)   # the SDR detector: batch.sdr_bound (B,), samples of N(mu_b, Sigma_b)
     f, v = batch.improve(s.COORD_DESCENT)
+    batch.suggest(s.RANDOM, num_samples=64, seed=7)
+    f, v = batch.improve(s.ADMM, num_iters=100)    # batch.last_stats['rho'] (B,), ['iters1'], ['iters2'] (B, R)
 """
 import numpy as np
 import scipy.sparse as sp
@@ -73,7 +77,31 @@ def _structure(funcs):
 
 
 MAX_N = 128          # qcqpmi_cd_batch_run: two coordinates per lane
-MAX_N_SMALL = 64     # qcqpmi_cd_small_batch_run, qcqpmi_sdr_small_batch: one coordinate per lane
+MAX_N_SMALL = 64     # qcqpmi_cd_small_batch_run, qcqpmi_sdr_small_batch, qcqpmi_admm_small_batch_run: one coordinate per lane
+
+
+def admm_rhos(P0s, m, rho=None):
+    """The rho rule of improve_admm (qcqp.py:261-278) for every problem, from ONE batched eigvalsh of P0s (B, n, n): rho == None gives
+    50 * 2 (1 - lambda_min) / m where lambda_min < 0 and 50 / m elsewhere; a given rho is checked against lambda_min + m rho >= 0 and
+    the reference's exception names the first problem that fails.  Returns rhos (B,)."""
+    P0s = np.asarray(P0s, dtype=np.float64)
+    lmin = np.linalg.eigvalsh(P0s)[:, 0]
+    if rho is not None:
+        rho = float(rho)
+        bad = np.nonzero(lmin + m * rho < 0)[0]
+        if bad.size:
+            raise Exception("rho parameter is too small, need at least %.3f. (problem %d: minimum possible value %.3f)"
+                            % (rho, int(bad[0]), -lmin[bad[0]] / m))
+        return np.full(P0s.shape[0], rho)
+    return 50. * np.where(lmin < 0, 2. * (1. - lmin) / m, 1. / m)
+
+
+def admm_minvs(P0s, rhos, m):
+    """(2 (P0_b + rho_b m I))^-1 for every problem: one batched inverse, symmetrised (the kernel reads columns as rows)."""
+    P0s = np.asarray(P0s, dtype=np.float64)
+    n = P0s.shape[1]
+    Mi = np.linalg.inv(2. * (P0s + (np.asarray(rhos) * m)[:, None, None] * np.eye(n)))
+    return (Mi + Mi.transpose(0, 2, 1)) / 2.
 
 
 class QCQPBatch(object):
@@ -169,18 +197,28 @@ class QCQPBatch(object):
             self._starts = None
         self._suggested = (int(num_samples), int(seed), int(first_index), int(seed_stride))
 
-    def improve(self, method=s.COORD_DESCENT, num_iters=1000, viol_tol=1e-2, tol=1e-4, phase1=True, seed=None):
-        """improve(COORD_DESCENT) of every suggested start of every problem; returns (f (B,), v (B,)) of the best restart per
-        problem (QCQPForm.better, ties -> lowest index) and sets .x (B, n), .population_f / .population_v (B, R), .best_index,
-        .last_stats.  seed: the seed of suggest() (a problem's normals and its draws come from ONE keyed stream)."""
-        if method != s.COORD_DESCENT:
-            raise Exception("QCQPBatch.improve is defined for the COORD_DESCENT method")
+    def improve(self, method=s.COORD_DESCENT, num_iters=1000, viol_tol=1e-2, tol=None, phase1=True, seed=None, viol_lim=1e4, rho=None):
+        """improve(COORD_DESCENT) or improve(ADMM) of every suggested start of every problem; returns (f (B,), v (B,)) of the best
+        restart per problem (QCQPForm.better, ties -> lowest index) and sets .x (B, n), .population_f / .population_v (B, R),
+        .best_index, .last_stats.  seed: the seed of suggest() (a problem's normals and its draws come from ONE keyed stream).
+        COORD_DESCENT: num_iters, viol_tol, tol (1e-4), phase1.
+        ADMM (n <= 64): num_iters, tol (1e-2), viol_lim, rho, phase1 -- the arguments of the reference's improve_admm.  rho == None:
+        the reference's rule (qcqp.py:270-277) problem by problem; a given rho that is too small for some problem raises the
+        reference's message.  .last_stats holds rho (B,), iters1, iters2 (B, R) and the kernel's name."""
+        if method not in (s.COORD_DESCENT, s.ADMM):
+            raise Exception("QCQPBatch.improve is defined for the COORD_DESCENT and ADMM methods")
+        if method == s.ADMM and self.n > MAX_N_SMALL:      # before any launch
+            raise Exception("QCQPBatch.improve(ADMM) is defined for n <= %d (n = %d): the batched kernel holds a point in one wavefront; "
+                            "use improve(COORD_DESCENT), or QCQP per problem" % (MAX_N_SMALL, self.n))
         if self._suggested is None:
             raise Exception("QCQPBatch.improve: call suggest(RANDOM or SDR, num_samples=R, seed=...) first")
         R, sd, first_index, stride = self._suggested
         if seed is not None and int(seed) != sd:
             raise Exception("QCQPBatch.improve: seed %d differs from the seed of suggest (%d); the batch runs one keyed stream per problem"
                             % (int(seed), sd))
+        if method == s.ADMM:
+            return self._improve_admm(R, sd, first_index, stride, num_iters, 1e-2 if tol is None else tol, viol_lim, rho, phase1)
+        tol = 1e-4 if tol is None else tol
         run = self.engine.cd_small_batch_run if self.n <= MAX_N_SMALL else self.engine.cd_batch_run
         out = run(self.P0s, self.q0s, self.r0s, R, X0=self._starts, phase1=phase1, num_iters=num_iters, viol_tol=viol_tol,
                   tol=tol, seed=sd, seed_stride=stride, first_index=first_index, want_x=False, cons=self.cons)
@@ -190,6 +228,19 @@ class QCQPBatch(object):
         failed = int(np.count_nonzero((out['status1'] != 0) | (out['status2'] != 0)))
         self.last_stats = dict(out, method=method, num_problems=self.B, num_restarts=R, failed_restarts=failed,
                                kernel=self.engine.last_cd_kernel())
+        return out['best_f0'], out['best_maxviol']
+
+    def _improve_admm(self, R, sd, first_index, stride, num_iters, tol, viol_lim, rho, phase1):
+        m = self.form.m
+        rhos = admm_rhos(self.P0s, m, rho)
+        out = self.engine.admm_small_batch_run(self.P0s, self.q0s, self.r0s, R, rhos, admm_minvs(self.P0s, rhos, m), X0=self._starts,
+                                               phase1=phase1, num_iters=num_iters, tol=tol, viol_lim=viol_lim, seed=sd,
+                                               seed_stride=stride, first_index=first_index, want_x=False, cons=self.cons)
+        self.x = out['best_x']
+        self.best_index = out['best_index']
+        self.population_f, self.population_v = out['f0'], out['maxviol']
+        self.last_stats = dict(out, method=s.ADMM, num_problems=self.B, num_restarts=R, rho=rhos,
+                               kernel=self.engine.last_admm_kernel()[0])
         return out['best_f0'], out['best_maxviol']
 
     def close(self):

@@ -1,0 +1,49 @@
+// Small-problem ADMM batch kernel: interface between capi.hip and admm_small.hip (own translation unit).
+//
+// improve_admm (qcqp.py:254-285: phase 1, `better`, phase 2 with its bestx bookkeeping, `better`) for B problems of n <= 64 variables
+// with separable constraints (up to four per coordinate: the lists of qcqpmi_cd_small_batch_run) that differ in their objective
+// (P0_b, q0_b, r0_b) -- and, with cons, in the coefficients of their constraints --, R restarts each, inside ONE persistent launch
+// (qcqpmi_admm_small_batch_run).  The loop, its exits and its iteration counts are those of orc_admm_phase1 /
+// orc_admm_phase2 (oracle/qcqp_oracle.c); the projection is admm_small_solve<1> (admm.h), the operand and dual expressions are those of
+// admm_unit_step_kernel.  Restart (b, r) starts from the keyed normals (seed + b seed_stride, first_index + r) or from X0 and depends
+// on nothing but (problem b, rho_b, Minv_b, its start): not on B, the neighbours, the workgroups or the order in which the work is
+// dealt out.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include "kernels.h"
+
+namespace qcqpmi {
+
+constexpr int ADMM_SMALL_MAXN = 64;      // lane = coordinate: one wavefront holds a point
+
+struct AdmmSmallArgs {
+    DevProblem P;                // n, m and the per-coordinate constraint lists (cptr / cp / cq / cr / crel / cidx); its objective is not read
+    int64_t B, R;
+    int64_t RC, chunks;          // a ticket = (problem, RC consecutive restarts); chunks = tickets per problem
+    const double *P0s;           // [B][n][n] symmetric (read from global memory: the objective of the two or three points that no solve produced)
+    const double *q0s;           // [B][n]
+    const double *r0s;           // [B]
+    const double *rhos;          // [B]
+    const double *Minvs;         // [B][n][n] (2 (P0_b + rho_b m I))^-1, symmetric (staged in LDS)
+    const double *X0;            // [B][R][n] start points (generate == 0), else unused
+    const double *cons;          // per-problem constraint coefficients [B][m][3] = (p, q, r) in CONSTRAINT order, or nullptr: P's
+    int generate, phase1;
+    int64_t num_iters;
+    double tol, viol_lim;
+    uint64_t seed, seed_stride, first_index;
+    int *ticket;                 // [0] zeroed before the launch: next ticket; [1] set when some P0_b or Minv_b is not symmetric
+    // per restart [B R]
+    int64_t *iters1, *iters2;
+    double *f0, *maxviol;
+    double *X;                   // [B][R][n] final points
+};
+
+// pc_entries: 0, or the m list entries whose (p, q, r) the per-problem-constraint kernels stage beside Minv_b and q0_b
+size_t admm_small_lds_bytes(int64_t n, int64_t pc_entries);
+// workgroups of the launch (persistent: at most what the device holds at once), or < 0: -hipError_t
+int admm_small_workgroups(int64_t n, int maxc, int64_t pc_entries, int64_t tickets, int device);
+int admm_small_launch(const AdmmSmallArgs &a, int maxc, int wgs, hipStream_t st);      // a.cons != nullptr: the <MAXC, pc> kernels
+const char *admm_small_name(int maxc, bool pc);
+
+}  // namespace qcqpmi

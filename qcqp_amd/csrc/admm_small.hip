@@ -1,0 +1,298 @@
+// admm_small_kernel -- improve_admm (qcqp.py:254-285) for a batch of SMALL problems (n <= 64) with separable constraints, R restarts
+// each, inside one persistent launch (admm_small.h).
+//
+// Layout: that of cd_small_kernel.  ONE WAVEFRONT PER (problem, restart), LANE = COORDINATE.  A workgroup of four waves draws a ticket
+// -- a problem and a chunk of its restarts -- from a global counter (an ordinary atomic add), stages Minv_b = (2 (P0_b + rho_b m I))^-1
+// (n x n doubles, at most 32 KB), q0_b and -- with per-problem coefficients -- the [3][m] image of problem b's (p, q, r) in LDS once, and
+// its waves take the chunk's restarts one by one from a counter in LDS.  After the barrier that follows the staging a wave never
+// waits for another one: no flags, no spinning.
+//   consensus state   separable constraints move one coordinate each, so the copies x_k and duals u_k of the reference collapse to what
+//                     admm_unit_step_kernel keeps: per lane z_i, one dual per constraint on the coordinate (registers) and the sum
+//                     S_i of the operands 2 xhat - vhat - z of its constraints; the consensus sum is m z + S;
+//   projection        a lane walks the constraints on its coordinate in ascending entry order through admm_small_solve<1> (admm_solve.h: the
+//                     one copy of the reference's bracket doubling and bisection, with the one-row shortcut); the bracket of an entry
+//                     is what qcqpmi_admm_set_basis derives for one row: slo = -1 / p for p > 0, ehi = -1 / p for p < 0;
+//   phase 1           orc_admm_phase1: max violation of z (a wave maximum) < tol ends it, else z = (S + m z) / m and the projections;
+//   phase 2           orc_admm_phase2: rhs = 2 rho (S + m z) - q0, z_j = sum_k Minv[k][j] rhs_k in ascending k (rhs_k broadcast by
+//                     v_readlane; Minv is symmetric, so column j is read as word k n + j of the image: consecutive doubles), the
+//                     projections, |last_z - z| through wave_sum_tree, the exits `< tol` and `maxviol > viol_lim`, and bestx =
+//                     better(z, bestx) with f0(z) = z . (rhs / 2 - rho m z + q0) + r0 from the solve itself (admm_take_z_kernel);
+//   P0_b              is read from GLOBAL memory, for the objective of the points no solve produced (the start, the phase-1 result)
+//                     and of the best point, which is reported through P0 itself like qcqpmi_admm_run does: two or three products per
+//                     restart against up to 2 num_iters solves -- the image stays at 32 KB + lists and four workgroups share a CU.
+#include "admm_small.h"
+
+#include "admm_solve.h"    // admm_small_solve<1>, AdmmArgs
+#include "cd_chain.h"      // readlane_d
+#include "dev_util.h"
+#include "philox.h"
+
+namespace qcqpmi {
+namespace {
+
+// the constraints on a lane's coordinate, in entry order
+template <int MAXC>
+struct AsList {
+    int cnt;
+    double p[MAXC], q[MAXC], r[MAXC];
+    int rel[MAXC];
+};
+
+// One projection pass at z (the body of admm_unit_step_kernel with s_h = +1): the duals move, the sum of the operands is returned,
+// viol = max violation of z over the coordinate's constraints (0 without one, like the zeroed mvbits of the serial kernels).
+// ONE copy of the solve's code for the up to MAXC entries: the loop is not unrolled and the entry is picked with selects (with four
+// inlined copies per call site the <4> kernels took 223 VGPRs: two waves per SIMD).
+template <int MAXC>
+__device__ inline double as_project(const AsList<MAXC> &K, double z, bool first, double (&u)[MAXC], double &viol) {
+    double acc = 0.0;
+    viol = 0.0;
+#pragma nounroll
+    for (int c = 0; c < K.cnt; c++) {
+        double L[1], Qh[1], V[1], Zq[1], X[1];
+        double rk = K.r[0], uo = u[0];
+        int relop = K.rel[0];
+        L[0] = K.p[0]; Qh[0] = K.q[0];
+#pragma unroll
+        for (int s = 1; s < MAXC; s++) {
+            const bool pick = c == s;
+            L[0] = pick ? K.p[s] : L[0]; Qh[0] = pick ? K.q[s] : Qh[0]; rk = pick ? K.r[s] : rk; relop = pick ? K.rel[s] : relop;
+            uo = pick ? u[s] : uo;
+        }
+        Zq[0] = z;
+        uo = first ? 0.0 : uo;
+        V[0] = Zq[0] + uo;
+        double fz = 0.0, fv = 0.0;
+        fz += L[0] * (Zq[0] * Zq[0]) + Qh[0] * Zq[0];
+        fv += L[0] * (V[0] * V[0]) + Qh[0] * V[0];
+        fz += rk; fv += rk;
+        const double w = (relop == RELOP_EQ) ? fabs(fz) : (fz > 0.0 ? fz : 0.0);
+        viol = w > viol ? w : viol;
+        // the bracket of one row (admm_brackets, capi_admm.inc)
+        double br[2];
+        br[0] = L[0] > 0.0 ? -1.0 / L[0] : -QM_INF;
+        br[1] = L[0] < 0.0 ? -1.0 / L[0] : QM_INF;
+        AdmmArgs sa;
+        sa.slo = &br[0]; sa.ehi = &br[1]; sa.sec_tol = 1e-6; sa.no_shortcut = 0;      // what admm_small_solve reads (utilities.py:149)
+        admm_small_solve<1>(sa, 0, L, Qh, V, rk, relop, fv, X);
+        const double un = V[0] - X[0];
+#pragma unroll
+        for (int s = 0; s < MAXC; s++) u[s] = (c == s) ? un : u[s];
+        acc += 2.0 * X[0] - V[0] - Zq[0];
+    }
+    return acc;
+}
+
+// max violation of the lane's coordinate at z without a projection (the start)
+template <int MAXC>
+__device__ inline double as_viol(const AsList<MAXC> &K, double z) {
+    double viol = 0.0;
+#pragma unroll
+    for (int c = 0; c < MAXC; c++) {
+        if (c < K.cnt) {
+            double fz = 0.0;
+            fz += K.p[c] * (z * z) + K.q[c] * z;
+            fz += K.r[c];
+            const double w = (K.rel[c] == RELOP_EQ) ? fabs(fz) : (fz > 0.0 ? fz : 0.0);
+            viol = w > viol ? w : viol;
+        }
+    }
+    return viol;
+}
+
+// f0(x) = sum_j (row_j + q_j) x_j + r0, row_j = sum_k P0[k][j] x_k, both in ascending index order (the sums of sm_refresh, cd_small.hip);
+// P0 from global memory (symmetric: column j as word k n + j), x zero in the lanes >= n
+__device__ inline double as_f0(const double *__restrict__ Pg, const double *qs, double r0, int n, int lane, double x) {
+    const int lc = lane < n ? lane : 0;
+    double row = 0.0;
+    for (int k = 0; k < n; k++) row += Pg[k * n + lc] * readlane_d(x, k);
+    const double term = (row + qs[lc]) * x;
+    double acc = 0.0;
+    for (int k = 0; k < n; k++) acc += readlane_d(term, k);
+    return acc + r0;
+}
+
+// does QCQPForm.better return its FIRST argument?  (utilities.py:135-146; admm_book_kernel)
+__device__ inline bool as_better_first(double f1, double v1, double f2, double v2) {
+    const long long b1 = (long long)(v1 / 1e-4), b2 = (long long)(v2 / 1e-4);
+    return b1 < b2 || (b1 == b2 && f1 < f2);
+}
+
+template <int MAXC>
+__device__ inline void as_restart(const AdmmSmallArgs &a, const double *Ms, const double *qs, int64_t b, int64_t r, int lane) {
+    const DevProblem &P = a.P;
+    const int n = (int)P.n;
+    const bool on = lane < n;
+    const int lc = on ? lane : 0;
+    const uint64_t seed = a.seed + (uint64_t)b * a.seed_stride;
+    const uint64_t gr = a.first_index + (uint64_t)r;
+    const int64_t o = b * a.R + r;
+    const double r0 = a.r0s[b], rho = a.rhos[b], mm = (double)P.m, rho_m = rho * mm;
+    const double *Pg = a.P0s + b * n * n;
+    const double ql = qs[lc];
+
+    AsList<MAXC> K;
+    K.cnt = 0;
+#pragma unroll
+    for (int c = 0; c < MAXC; c++) { K.p[c] = 0.0; K.q[c] = 0.0; K.r[c] = 0.0; K.rel[c] = RELOP_LE; }
+    if (on) {
+        const int e0 = P.cptr[lane], e1 = P.cptr[lane + 1];
+        K.cnt = e1 - e0 < MAXC ? e1 - e0 : MAXC;
+#pragma unroll
+        for (int c = 0; c < MAXC; c++)
+            if (c < K.cnt) { K.p[c] = P.cp[e0 + c]; K.q[c] = P.cq[e0 + c]; K.r[c] = P.cr[e0 + c]; K.rel[c] = P.crel[e0 + c]; }
+    }
+    double u[MAXC];
+#pragma unroll
+    for (int c = 0; c < MAXC; c++) u[c] = 0.0;
+
+    double x0 = 0.0;
+    if (on) x0 = a.generate ? keyed_normal(seed, gr, (uint64_t)lane) : a.X0[o * n + lane];
+    const double mv0 = wave_max(as_viol<MAXC>(K, x0));
+    const double f_x0 = as_f0(Pg, qs, r0, n, lane, x0);
+
+    // ---- phase 1 (qcqp.py:195-212; orc_admm_phase1), x1 = better(x0, z1) (qcqp.py:281), phase 2 (qcqp.py:215-251; orc_admm_phase2).
+    // The two phases are ONE loop nest, so that the projection is inlined once: a phase is its z-update, the projections they share
+    // and its exits.
+    double x1 = x0, f1 = f_x0, mv1 = mv0;
+    double best = x0, bf = f_x0, bmv = mv0;
+    int64_t it1 = 0, it2 = 0;
+    bool took = false;
+    for (int ph = a.phase1 ? 1 : 2; ph <= 2; ph++) {
+        double z = x1, last = x1, mvz = mv1, acc = 0.0;       // (phase 1 starts from x1 = x0)
+        bool have_last = false;
+        for (int64_t t = 0; t < a.num_iters; t++) {
+            double f0z = 0.0;
+            if (ph == 1) {
+                if (mvz < a.tol) break;                        // qcqp.py:203
+                double sm = acc;
+                sm += mm * z;
+                z = on ? sm / mm : 0.0;                        // qcqp.py:205
+                it1++;
+            } else {
+                it2++;
+                double sm = acc;
+                sm += mm * z;
+                const double rhs = on ? 2.0 * rho * sm - ql : 0.0;      // qcqp.py:231
+                double zn = 0.0;
+                for (int k = 0; k < n; k++) zn += Ms[k * n + lc] * readlane_d(rhs, k);
+                z = on ? zn : 0.0;
+                // f0(z) from the solve's own right-hand side (admm_take_z_kernel)
+                f0z = wave_sum_tree(((0.5 * rhs - rho_m * z) + ql) * z) + r0;
+            }
+            double vl;
+            acc = as_project<MAXC>(K, z, t == 0, u, vl);
+            mvz = wave_max(vl);
+            if (ph == 2) {
+                if (have_last) {
+                    const double d = last - z;
+                    if (sqrt(wave_sum_tree(d * d)) < a.tol) break;      // qcqp.py:241-242 (before bestx)
+                }
+                last = z; have_last = true;
+                if (mvz > a.viol_lim) break;                             // qcqp.py:248
+                if (as_better_first(f0z, mvz, bf, bmv)) { best = z; bf = f0z; bmv = mvz; took = true; }
+            }
+        }
+        if (ph == 1) {
+            if (it1 > 0) {                                     // (no iteration: z1 is x0 itself and `better` keeps its second argument)
+                const double f_z = as_f0(Pg, qs, r0, n, lane, z);
+                if (!as_better_first(f_x0, mv0, f_z, mvz)) { x1 = z; f1 = f_z; mv1 = mvz; }
+            }
+            best = x1; bf = f1; bmv = mv1;                     // bestx = x1 (qcqp.py:218)
+        }
+    }
+    // ---- x2 = better(x1, bestx) (qcqp.py:284); what is compared and reported is f0 of the best point through P0 itself
+    if (took) {
+        bf = as_f0(Pg, qs, r0, n, lane, best);
+        if (as_better_first(f1, mv1, bf, bmv)) { best = x1; bf = f1; bmv = mv1; }
+    }
+    if (lane == 0) { a.iters1[o] = it1; a.iters2[o] = it2; a.f0[o] = bf; a.maxviol[o] = bmv; }
+    if (on) a.X[o * n + lane] = best;
+}
+
+// PC: per-problem constraint coefficients.  The ticket's workgroup stages problem b's (p, q, r) of every list entry in LDS beside Minv_b
+// and q0_b -- entry e of the context's lists (cptr order) is constraint cidx[e] of a.cons [B][m][3] -- and its waves read their lists
+// through the kernel's copy of the context's DevProblem, whose cp / cq / cr point at that image (cd_small_kernel's view).
+template <int MAXC, bool PC = false>
+__global__ __launch_bounds__(256) void admm_small_kernel(AdmmSmallArgs a) {
+    extern __shared__ double as_lds[];
+    const int n = (int)a.P.n, m = PC ? (int)a.P.m : 0;
+    double *Ms = as_lds, *qs = as_lds + n * n;
+    double *cs = qs + n;             // PC: [3][m] the staged coefficients, p then q then r
+    int *ctl = (int *)(cs + 3 * m);  // [0] the workgroup's ticket, [1] next restart of its chunk
+    const int *cidx = a.P.cidx;
+    if constexpr (PC) { a.P.cp = cs; a.P.cq = cs + m; a.P.cr = cs + 2 * m; }      // the view: cptr and crel stay the context's
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int64_t tickets = a.B * a.chunks;
+    for (;;) {
+        __syncthreads();             // every wave is done with the LDS image of the previous ticket
+        if (tid == 0) {
+            ctl[0] = __hip_atomic_fetch_add(a.ticket, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            ctl[1] = 0;
+        }
+        __syncthreads();
+        const int64_t tk = ctl[0];
+        if (tk >= tickets) break;
+        const int64_t b = tk / a.chunks, r_lo = (tk % a.chunks) * a.RC;
+        const int64_t r_hi = r_lo + a.RC < a.R ? r_lo + a.RC : a.R;
+        const double *Mg = a.Minvs + b * n * n, *Pg = a.P0s + b * n * n;
+        for (int e = tid; e < n * n; e += 256) Ms[e] = Mg[e];
+        if (tid < n) qs[tid] = a.q0s[b * n + tid];
+        if constexpr (PC) {
+            const double *cg = a.cons + b * m * 3;
+            for (int e = tid; e < m; e += 256) {
+                const double *ck = cg + (cidx[e] - 1) * 3;
+                cs[e] = ck[0]; cs[m + e] = ck[1]; cs[2 * m + e] = ck[2];
+            }
+        }
+        __syncthreads();
+        // columns are read as rows: a Minv_b or P0_b that is not symmetric (or holds a NaN) makes the call fail
+        bool asym = false;
+        for (int e = tid; e < n * n; e += 256) {
+            const int i = e / n, j = e - i * n;
+            asym = asym || (j > i && (!(Ms[e] == Ms[j * n + i]) || !(Pg[e] == Pg[j * n + i])));
+        }
+        if (asym) a.ticket[1] = 1;
+        for (;;) {
+            int k = 0;
+            if (lane == 0) k = atomicAdd(&ctl[1], 1);
+            k = __builtin_amdgcn_readfirstlane(k);
+            if (r_lo + k >= r_hi) break;
+            as_restart<MAXC>(a, Ms, qs, b, r_lo + k, lane);
+        }
+    }
+}
+
+typedef void (*AdmmSmallKernel)(AdmmSmallArgs);
+
+AdmmSmallKernel admm_small_pick(int maxc, bool pc) {
+    if (pc) return maxc <= 1 ? admm_small_kernel<1, true> : admm_small_kernel<4, true>;
+    return maxc <= 1 ? admm_small_kernel<1> : admm_small_kernel<4>;
+}
+
+}  // namespace
+
+size_t admm_small_lds_bytes(int64_t n, int64_t pc_entries) { return (size_t)(n * n + n + 3 * pc_entries) * sizeof(double) + 2 * sizeof(int); }
+
+int admm_small_workgroups(int64_t n, int maxc, int64_t pc_entries, int64_t tickets, int device) {
+    int cus = 0, per = 0;
+    hipError_t e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device);
+    if (e != hipSuccess) return -(int)e;
+    e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, admm_small_pick(maxc, pc_entries > 0), 256, admm_small_lds_bytes(n, pc_entries));
+    if (e != hipSuccess) return -(int)e;
+    if (per < 1) per = 1;
+    const int64_t cap = (int64_t)cus * per;
+    return (int)(tickets < cap ? tickets : cap);
+}
+
+int admm_small_launch(const AdmmSmallArgs &a, int maxc, int wgs, hipStream_t st) {
+    const bool pc = a.cons != nullptr;
+    hipLaunchKernelGGL(admm_small_pick(maxc, pc), dim3((unsigned)wgs), dim3(256), admm_small_lds_bytes(a.P.n, pc ? a.P.m : 0), st, a);
+    return (int)hipGetLastError();
+}
+
+const char *admm_small_name(int maxc, bool pc) {
+    if (pc) return maxc <= 1 ? "admm_small_kernel<1,pc>" : "admm_small_kernel<4,pc>";
+    return maxc <= 1 ? "admm_small_kernel<1>" : "admm_small_kernel<4>";
+}
+
+}  // namespace qcqpmi

@@ -21,6 +21,7 @@
 #include "cd_queue.h"
 #include "cd_life.h"
 #include "cd_small.h"
+#include "admm_small.h"
 #include "sdr_small.h"
 #include "gemm_pk.h"
 #include "cd_general.h"
@@ -1919,6 +1920,126 @@ int qcqpmi_cd_batch_run(qcqpmi_ctx *c, int64_t B, const double *P0s, const doubl
     return cd_small_batch(c, CD_WIDE_MAXN, cons != nullptr, cons, B, P0s, q0s, r0s, R, generate, X0, phase1, num_iters, viol_tol, tol, seed, seed_stride,
                           first_index, select_tol, sweeps1, sweeps2, visits2, accepted2, ran_phase2, status1, status2, f0, maxviol, X, best_index,
                           best_f0, best_maxviol, best_x);
+}
+
+// ---- improve(ADMM) for B small problems (n <= 64) over the context's separable constraint lists, R restarts each, in ONE launch of
+// admm_small_kernel (csrc/admm_small.hip).  Works in the buffer of the small-batch calls: the resident population, its evaluation, an
+// installed ADMM basis and qcqpmi_last_cd_kernel are not touched, whether the call succeeds or is refused.
+int qcqpmi_admm_small_batch_run(qcqpmi_ctx *c, int64_t B, const double *P0s, const double *q0s, const double *r0s, const double *cons,
+                                const double *rhos, const double *Minvs, int64_t R, int generate, const double *X0, int phase1,
+                                int64_t num_iters, double tol, double viol_lim, uint64_t seed, uint64_t seed_stride, uint64_t first_index,
+                                double select_tol, int64_t *iters1, int64_t *iters2, double *f0, double *maxviol, double *X,
+                                int64_t *best_index, double *best_f0, double *best_maxviol, double *best_x) {
+    int rc = check_ready(c, false);
+    if (rc) return rc;
+    if (!c->sep) return fail(c, QCQPMI_EUNSUPPORTED, "admm_small_batch_run: the constraints are not separable (a constraint couples coordinates, or a coordinate carries more than 4)");
+    if (c->n > ADMM_SMALL_MAXN) return fail(c, QCQPMI_EUNSUPPORTED, "admm_small_batch_run: n = %lld, the small-problem kernel takes n <= %d (one lane per coordinate)", (long long)c->n, ADMM_SMALL_MAXN);
+    if (B < 1 || R < 1 || num_iters < 0 || !P0s || !q0s || !r0s || !rhos || !Minvs || (!generate && !X0))
+        return fail(c, QCQPMI_EINVAL, "admm_small_batch_run: bad B / R / num_iters, or a missing input array");
+    if (B >= (1LL << 30) || R >= (1LL << 30) || B * R >= (1LL << 30)) return fail(c, QCQPMI_EINVAL, "admm_small_batch_run: B R = %lld restarts, at most 2^30 - 1 per call", (long long)(B * R));
+    const int64_t m = c->m;
+    if (m < 1) return fail(c, QCQPMI_EINVAL, "admm_small_batch_run: the context has no constraint (the consensus average divides by m)");
+    for (int64_t b = 0; b < B; b++)
+        if (!(rhos[b] > 0.0) || !std::isfinite(rhos[b]))
+            return fail(c, QCQPMI_EINVAL, "admm_small_batch_run: rho of problem %lld is not positive and finite", (long long)b);
+    for (int64_t k = 0; cons && k < B * m; k++) {
+        const double p = cons[3 * k], q = cons[3 * k + 1], r = cons[3 * k + 2];
+        if (!std::isfinite(p) || !std::isfinite(q) || !std::isfinite(r))
+            return fail(c, QCQPMI_EINVAL, "admm_small_batch_run: constraint %lld of problem %lld holds a coefficient that is not finite", (long long)(k % m + 1), (long long)(k / m));
+        if (p == 0.0 && q == 0.0)
+            return fail(c, QCQPMI_EINVAL, "admm_small_batch_run: constraint %lld of problem %lld has p == 0 and q == 0: it touches no coordinate", (long long)(k % m + 1), (long long)(k / m));
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    const int64_t n = c->n, T = B * R;
+    // ---- carve the work buffer (every piece 256-byte aligned)
+    size_t off = 0;
+    auto take = [&off](size_t bytes) { const size_t o = off; off += (bytes + 255) / 256 * 256; return o; };
+    const size_t oP = take((size_t)B * n * n * 8), oM = take((size_t)B * n * n * 8), oq = take((size_t)B * n * 8), or0 = take((size_t)B * 8);
+    const size_t orho = take((size_t)B * 8);
+    const size_t oX0 = take(generate ? 0 : (size_t)T * n * 8), oX = take((size_t)T * n * 8);
+    const size_t oout = take((size_t)T * 32);      // 2 x int64, 2 x double per restart, array after array
+    const size_t oticket = take(2 * sizeof(int));
+    const size_t obi = take((size_t)B * 2 * sizeof(int64_t)), obk = take((size_t)B * 2 * sizeof(double)), obx = take((size_t)B * n * 8);
+    const size_t ocons = take(cons ? (size_t)B * m * 24 : 0);
+    if (off > c->sb_work_cap) {
+        HIPCHK(c, spin_sync(c->stream));
+        if (c->sb_work) (void)hipFree(c->sb_work);
+        c->sb_work = nullptr; c->sb_work_cap = 0;
+        HIPCHK(c, hipMalloc((void **)&c->sb_work, off));
+        c->sb_work_cap = off;
+    }
+    char *w = c->sb_work;
+    HIPCHK(c, hipMemcpyAsync(w + oP, P0s, (size_t)B * n * n * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(w + oM, Minvs, (size_t)B * n * n * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(w + oq, q0s, (size_t)B * n * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(w + or0, r0s, (size_t)B * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(w + orho, rhos, (size_t)B * 8, hipMemcpyHostToDevice, c->stream));
+    if (!generate) HIPCHK(c, hipMemcpyAsync(w + oX0, X0, (size_t)T * n * 8, hipMemcpyHostToDevice, c->stream));
+    if (cons) HIPCHK(c, hipMemcpyAsync(w + ocons, cons, (size_t)B * m * 24, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemsetAsync(w + oticket, 0, 2 * sizeof(int), c->stream));
+    AdmmSmallArgs a;
+    a.P = c->dp; a.B = B; a.R = R;
+    a.P0s = (const double *)(w + oP); a.Minvs = (const double *)(w + oM); a.q0s = (const double *)(w + oq); a.r0s = (const double *)(w + or0);
+    a.rhos = (const double *)(w + orho);
+    a.X0 = generate ? nullptr : (const double *)(w + oX0);
+    a.cons = cons ? (const double *)(w + ocons) : nullptr;
+    a.generate = generate ? 1 : 0; a.phase1 = phase1 ? 1 : 0; a.num_iters = num_iters; a.tol = tol; a.viol_lim = viol_lim;
+    a.seed = seed; a.seed_stride = seed_stride; a.first_index = first_index;
+    a.ticket = (int *)(w + oticket);
+    char *o = w + oout;
+    a.iters1 = (int64_t *)o; a.iters2 = (int64_t *)(o + 8 * T); a.f0 = (double *)(o + 16 * T); a.maxviol = (double *)(o + 24 * T);
+    a.X = (double *)(w + oX);
+    // tickets: whole problems when there are enough of them to fill the device, else chunks of at least one restart per wave of a workgroup
+    const int maxc = c->maxc <= 1 ? 1 : 4;
+    int wgs = admm_small_workgroups(n, maxc, cons ? m : 0, B * R, c->device);
+    if (wgs < 1) return fail(c, QCQPMI_EHIP, "admm_small_batch_run: occupancy query failed: %s", hipGetErrorString((hipError_t)(-wgs)));
+    int64_t chunks = B >= wgs ? 1 : (wgs + B - 1) / B;
+    if (chunks > (R + 3) / 4) chunks = (R + 3) / 4;
+    a.RC = (R + chunks - 1) / chunks;
+    a.chunks = (R + a.RC - 1) / a.RC;
+    if (wgs > B * a.chunks) wgs = (int)(B * a.chunks);
+    hipError_t qe = (hipError_t)admm_small_launch(a, maxc, wgs, c->stream);
+    if (qe != hipSuccess) return fail(c, QCQPMI_EHIP, "admm_small_batch_run: %s", hipGetErrorString(qe));
+    c->last_admm_kernel = admm_small_name(maxc, cons != nullptr);
+    c->last_admm_C = 0;
+    const bool want_best = best_index || best_f0 || best_maxviol || best_x;
+    if (want_best) {       // QCQPForm.better folded over every problem's restarts, ties -> lowest index: one workgroup per problem
+        hipLaunchKernelGGL(select_best_kernel, dim3((unsigned)B), dim3(1024), 0, c->stream, (const double *)a.f0, (const double *)a.maxviol, R,
+                           select_tol, (int64_t *)(w + obi), (double *)(w + obk));
+        HIPCHK(c, hipGetLastError());
+        if (best_x) {
+            HIPCHK(c, hipMemsetAsync(w + obx, 0, (size_t)B * n * 8, c->stream));
+            qe = (hipError_t)cd_small_gather_launch(a.X, n, R, B, (const int64_t *)(w + obi), (double *)(w + obx), c->stream);
+            if (qe != hipSuccess) return fail(c, QCQPMI_EHIP, "admm_small_batch_run: %s", hipGetErrorString(qe));
+        }
+    }
+    std::vector<char> hout((size_t)T * 32);
+    std::vector<int64_t> bidx(want_best ? (size_t)B * 2 : 0);
+    std::vector<double> bkey(want_best ? (size_t)B * 2 : 0);
+    int flags[2] = {0, 0};
+    HIPCHK(c, hipMemcpyAsync(flags, w + oticket, sizeof(flags), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, spin_sync(c->stream));
+    if (flags[1]) return fail(c, QCQPMI_EINVAL, "admm_small_batch_run: a matrix P0_b or Minv_b is not symmetric (or holds a NaN)");
+    HIPCHK(c, hipMemcpyAsync(hout.data(), o, hout.size(), hipMemcpyDeviceToHost, c->stream));
+    if (X) HIPCHK(c, hipMemcpyAsync(X, a.X, (size_t)T * n * 8, hipMemcpyDeviceToHost, c->stream));
+    if (want_best) {
+        HIPCHK(c, hipMemcpyAsync(bidx.data(), w + obi, bidx.size() * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(bkey.data(), w + obk, bkey.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        if (best_x) HIPCHK(c, hipMemcpyAsync(best_x, w + obx, (size_t)B * n * 8, hipMemcpyDeviceToHost, c->stream));
+    }
+    HIPCHK(c, spin_sync(c->stream));
+    const char *h = hout.data();
+    const size_t n8 = (size_t)T * 8;
+    if (iters1) memcpy(iters1, h, n8);
+    if (iters2) memcpy(iters2, h + n8, n8);
+    if (f0) memcpy(f0, h + 2 * n8, n8);
+    if (maxviol) memcpy(maxviol, h + 3 * n8, n8);
+    for (int64_t b = 0; b < B && want_best; b++) {
+        if (best_index) best_index[b] = bidx[(size_t)2 * b];
+        if (best_f0) best_f0[b] = bkey[(size_t)2 * b];
+        if (best_maxviol) best_maxviol[b] = bkey[(size_t)2 * b + 1];
+    }
+    return 0;
 }
 
 // ---- suggest(SDR) for B small problems (n <= 64) of the unit-diagonal family that share the context's constraints x_i^2 == d_i: the

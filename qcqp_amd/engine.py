@@ -385,6 +385,43 @@ class Engine(object):
                                          _ip(out['iters2']), _dp(out['f0']), _dp(out['maxviol'])))
         return out
 
+    def admm_small_batch_run(self, P0s, q0s, r0s, R, rhos, Minvs, X0=None, phase1=True, num_iters=1000, tol=1e-2, viol_lim=1e4, seed=0,
+                             seed_stride=1, first_index=0, select_tol=1e-4, want_x=True, cons=None):
+        """improve_admm (qcqp.py:254-285) for B small problems (n <= 64) over this context's separable constraints -- P0s (B, n, n)
+        symmetric, q0s (B, n), r0s (B,), rhos (B,), Minvs (B, n, n) = (2 (P0_b + rho_b m I))^-1 -- with R restarts each in ONE launch
+        (qcqpmi_admm_small_batch_run).  Restart (b, r) starts from the keyed normals (seed + b seed_stride, first_index + r), or from
+        X0 (B, R, n).  Returns the dictionary of admm_run with arrays of shape (B, R) -- iters1, iters2 (the reference's counts), f0,
+        maxviol --, X (B, R, n) if want_x, and per problem best_index / best_f0 / best_maxviol (B,) and best_x (B, n).  cons (B, m, 3):
+        per-problem constraint coefficients as cd_small_batch_run takes them.  The resident population is not touched."""
+        P0s = np.ascontiguousarray(P0s, dtype=np.float64)
+        q0s = np.ascontiguousarray(q0s, dtype=np.float64)
+        r0s = np.ascontiguousarray(r0s, dtype=np.float64).ravel()
+        rhos = np.ascontiguousarray(rhos, dtype=np.float64).ravel()
+        Minvs = np.ascontiguousarray(Minvs, dtype=np.float64)
+        B, R, n = int(P0s.shape[0]) if P0s.ndim == 3 else 0, int(R), self.n
+        if P0s.shape != (B, n, n) or q0s.shape != (B, n) or r0s.shape != (B,) or rhos.shape != (B,) or Minvs.shape != (B, n, n):
+            raise ValueError('admm_small_batch_run: expected P0s and Minvs (B, n, n), q0s (B, n), r0s and rhos (B,) with n = %d' % n)
+        if X0 is not None:
+            X0 = np.ascontiguousarray(X0, dtype=np.float64)
+            if X0.shape != (B, R, n):
+                raise ValueError('admm_small_batch_run: expected X0 of shape (B, R, n)')
+        if cons is not None:
+            cons = np.ascontiguousarray(cons, dtype=np.float64)
+            if cons.shape != (B, self.m, 3):
+                raise ValueError('admm_small_batch_run: expected cons of shape (B, m, 3) with m = %d' % self.m)
+        T = max(B * R, 0)
+        out = dict(iters1=np.zeros(T, dtype=np.int64), iters2=np.zeros(T, dtype=np.int64), f0=np.empty(T), maxviol=np.empty(T),
+                   X=np.empty((B, max(R, 0), n)) if want_x else None, best_index=np.zeros(B, dtype=np.int64), best_f0=np.empty(B),
+                   best_maxviol=np.empty(B), best_x=np.zeros((B, n)))
+        self._chk(self.L.qcqpmi_admm_small_batch_run(
+            self.h, B, _dp(P0s), _dp(q0s), _dp(r0s), _dp(cons), _dp(rhos), _dp(Minvs), R, 0 if X0 is not None else 1, _dp(X0),
+            int(bool(phase1)), int(num_iters), float(tol), float(viol_lim), int(seed), int(seed_stride), int(first_index), float(select_tol),
+            _ip(out['iters1']), _ip(out['iters2']), _dp(out['f0']), _dp(out['maxviol']), _dp(out['X']), _ip(out['best_index']),
+            _dp(out['best_f0']), _dp(out['best_maxviol']), _dp(out['best_x'])))
+        for k in ('iters1', 'iters2', 'f0', 'maxviol'):
+            out[k] = out[k].reshape(B, R)
+        return out
+
     def admm_fused(self, enable=True):
         """Fused persistent ADMM kernel on / off (off = the multi-launch path everywhere: the cross-check); 2 = the fused kernel
         with four-wave workgroups, two per compute unit (an experiment kept as a second cross-check)."""
