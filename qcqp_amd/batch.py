@@ -222,12 +222,15 @@ class QCQPBatch(object):
         run = self.engine.cd_small_batch_run if self.n <= MAX_N_SMALL else self.engine.cd_batch_run
         out = run(self.P0s, self.q0s, self.r0s, R, X0=self._starts, phase1=phase1, num_iters=num_iters, viol_tol=viol_tol,
                   tol=tol, seed=sd, seed_stride=stride, first_index=first_index, want_x=False, cons=self.cons)
+        failed = int(np.count_nonzero((out['status1'] != 0) | (out['status2'] != 0)))
+        return self._publish(out, method, R, failed_restarts=failed, kernel=self.engine.last_cd_kernel())
+
+    def _publish(self, out, method, R, **stats):
+        """Publishes an improve launch (.x, .best_index, .population_f / _v, .last_stats); returns (f, v) of every problem's best restart."""
         self.x = out['best_x']
         self.best_index = out['best_index']
         self.population_f, self.population_v = out['f0'], out['maxviol']
-        failed = int(np.count_nonzero((out['status1'] != 0) | (out['status2'] != 0)))
-        self.last_stats = dict(out, method=method, num_problems=self.B, num_restarts=R, failed_restarts=failed,
-                               kernel=self.engine.last_cd_kernel())
+        self.last_stats = dict(out, method=method, num_problems=self.B, num_restarts=R, **stats)
         return out['best_f0'], out['best_maxviol']
 
     def _improve_admm(self, R, sd, first_index, stride, num_iters, tol, viol_lim, rho, phase1):
@@ -236,12 +239,7 @@ class QCQPBatch(object):
         out = self.engine.admm_small_batch_run(self.P0s, self.q0s, self.r0s, R, rhos, admm_minvs(self.P0s, rhos, m), X0=self._starts,
                                                phase1=phase1, num_iters=num_iters, tol=tol, viol_lim=viol_lim, seed=sd,
                                                seed_stride=stride, first_index=first_index, want_x=False, cons=self.cons)
-        self.x = out['best_x']
-        self.best_index = out['best_index']
-        self.population_f, self.population_v = out['f0'], out['maxviol']
-        self.last_stats = dict(out, method=s.ADMM, num_problems=self.B, num_restarts=R, rho=rhos,
-                               kernel=self.engine.last_admm_kernel()[0])
-        return out['best_f0'], out['best_maxviol']
+        return self._publish(out, s.ADMM, R, rho=rhos, kernel=self.engine.last_admm_kernel()[0])
 
     def close(self):
         self.engine.close()

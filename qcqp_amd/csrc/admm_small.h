@@ -1,4 +1,4 @@
-// Small-problem ADMM batch kernel: interface between capi.hip and admm_small.hip (own translation unit).
+// Small-problem ADMM batch kernel: interface between capi.hip (its driver: capi_small.inc) and admm_small.hip (own translation unit).
 //
 // improve_admm (qcqp.py:254-285: phase 1, `better`, phase 2 with its bestx bookkeeping, `better`) for B problems of n <= 64 variables
 // with separable constraints (up to four per coordinate: the lists of qcqpmi_cd_small_batch_run) that differ in their objective
@@ -12,6 +12,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "kernels.h"
+#include "small_batch.h"      // the LDS image, the ticket frame
 
 namespace qcqpmi {
 
@@ -39,9 +40,7 @@ struct AdmmSmallArgs {
     double *X;                   // [B][R][n] final points
 };
 
-// pc_entries: 0, or the m list entries whose (p, q, r) the per-problem-constraint kernels stage beside Minv_b and q0_b
-size_t admm_small_lds_bytes(int64_t n, int64_t pc_entries);
-// workgroups of the launch (persistent: at most what the device holds at once), or < 0: -hipError_t
+// workgroups of the launch (small_workgroup_cap; pc_entries: as small_image_bytes takes it), or < 0: -hipError_t
 int admm_small_workgroups(int64_t n, int maxc, int64_t pc_entries, int64_t tickets, int device);
 int admm_small_launch(const AdmmSmallArgs &a, int maxc, int wgs, hipStream_t st);      // a.cons != nullptr: the <MAXC, pc> kernels
 const char *admm_small_name(int maxc, bool pc);

@@ -1,11 +1,8 @@
 // admm_small_kernel -- improve_admm (qcqp.py:254-285) for a batch of SMALL problems (n <= 64) with separable constraints, R restarts
 // each, inside one persistent launch (admm_small.h).
 //
-// Layout: that of cd_small_kernel.  ONE WAVEFRONT PER (problem, restart), LANE = COORDINATE.  A workgroup of four waves draws a ticket
-// -- a problem and a chunk of its restarts -- from a global counter (an ordinary atomic add), stages Minv_b = (2 (P0_b + rho_b m I))^-1
-// (n x n doubles, at most 32 KB), q0_b and -- with per-problem coefficients -- the [3][m] image of problem b's (p, q, r) in LDS once, and
-// its waves take the chunk's restarts one by one from a counter in LDS.  After the barrier that follows the staging a wave never
-// waits for another one: no flags, no spinning.
+// Layout: the ticket frame of small_batch.h around Minv_b = (2 (P0_b + rho_b m I))^-1 (n x n doubles, at most 32 KB), workgroups of
+// four waves, LANE = COORDINATE.
 //   consensus state   separable constraints move one coordinate each, so the copies x_k and duals u_k of the reference collapse to what
 //                     admm_unit_step_kernel keeps: per lane z_i, one dual per constraint on the coordinate (registers) and the sum
 //                     S_i of the operands 2 xhat - vhat - z of its constraints; the consensus sum is m z + S;
@@ -117,6 +114,7 @@ __device__ inline bool as_better_first(double f1, double v1, double f2, double v
     return b1 < b2 || (b1 == b2 && f1 < f2);
 }
 
+// NOT marked always_inline, like sm_restart (cd_small.hip): that no kernel calls it rests on the inliner; tools/asm_digest.py shows it.
 template <int MAXC>
 __device__ inline void as_restart(const AdmmSmallArgs &a, const double *Ms, const double *qs, int64_t b, int64_t r, int lane) {
     const DevProblem &P = a.P;
@@ -209,57 +207,18 @@ __device__ inline void as_restart(const AdmmSmallArgs &a, const double *Ms, cons
     if (on) a.X[o * n + lane] = best;
 }
 
-// PC: per-problem constraint coefficients.  The ticket's workgroup stages problem b's (p, q, r) of every list entry in LDS beside Minv_b
-// and q0_b -- entry e of the context's lists (cptr order) is constraint cidx[e] of a.cons [B][m][3] -- and its waves read their lists
-// through the kernel's copy of the context's DevProblem, whose cp / cq / cr point at that image (cd_small_kernel's view).
+// PC: per-problem constraint coefficients, staged by the frame (small_batch.h)
 template <int MAXC, bool PC = false>
 __global__ __launch_bounds__(256) void admm_small_kernel(AdmmSmallArgs a) {
     extern __shared__ double as_lds[];
-    const int n = (int)a.P.n, m = PC ? (int)a.P.m : 0;
-    double *Ms = as_lds, *qs = as_lds + n * n;
-    double *cs = qs + n;             // PC: [3][m] the staged coefficients, p then q then r
-    int *ctl = (int *)(cs + 3 * m);  // [0] the workgroup's ticket, [1] next restart of its chunk
-    const int *cidx = a.P.cidx;
-    if constexpr (PC) { a.P.cp = cs; a.P.cq = cs + m; a.P.cr = cs + 2 * m; }      // the view: cptr and crel stay the context's
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int64_t tickets = a.B * a.chunks;
-    for (;;) {
-        __syncthreads();             // every wave is done with the LDS image of the previous ticket
-        if (tid == 0) {
-            ctl[0] = __hip_atomic_fetch_add(a.ticket, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            ctl[1] = 0;
-        }
-        __syncthreads();
-        const int64_t tk = ctl[0];
-        if (tk >= tickets) break;
-        const int64_t b = tk / a.chunks, r_lo = (tk % a.chunks) * a.RC;
-        const int64_t r_hi = r_lo + a.RC < a.R ? r_lo + a.RC : a.R;
-        const double *Mg = a.Minvs + b * n * n, *Pg = a.P0s + b * n * n;
-        for (int e = tid; e < n * n; e += 256) Ms[e] = Mg[e];
-        if (tid < n) qs[tid] = a.q0s[b * n + tid];
-        if constexpr (PC) {
-            const double *cg = a.cons + b * m * 3;
-            for (int e = tid; e < m; e += 256) {
-                const double *ck = cg + (cidx[e] - 1) * 3;
-                cs[e] = ck[0]; cs[m + e] = ck[1]; cs[2 * m + e] = ck[2];
-            }
-        }
-        __syncthreads();
-        // columns are read as rows: a Minv_b or P0_b that is not symmetric (or holds a NaN) makes the call fail
-        bool asym = false;
-        for (int e = tid; e < n * n; e += 256) {
-            const int i = e / n, j = e - i * n;
-            asym = asym || (j > i && (!(Ms[e] == Ms[j * n + i]) || !(Pg[e] == Pg[j * n + i])));
-        }
-        if (asym) a.ticket[1] = 1;
-        for (;;) {
-            int k = 0;
-            if (lane == 0) k = atomicAdd(&ctl[1], 1);
-            k = __builtin_amdgcn_readfirstlane(k);
-            if (r_lo + k >= r_hi) break;
-            as_restart<MAXC>(a, Ms, qs, b, r_lo + k, lane);
-        }
-    }
+    small_ticket_frame<PC>(      // the scan covers P0_b too: its columns are read as rows from global memory
+        a, as_lds, 256,
+        [&a](int64_t off, double *Ms, int nn, int tid, int nt) __attribute__((always_inline)) {
+            const double *Mg = a.Minvs + off, *Pg = a.P0s + off;
+            small_stage_matrix(Ms, Mg, nn, tid, nt);
+            return Pg;
+        },
+        [&a](const double *Ms, const double *qs, int64_t b, int64_t r, int lane) __attribute__((always_inline)) { as_restart<MAXC>(a, Ms, qs, b, r, lane); });
 }
 
 typedef void (*AdmmSmallKernel)(AdmmSmallArgs);
@@ -271,22 +230,16 @@ AdmmSmallKernel admm_small_pick(int maxc, bool pc) {
 
 }  // namespace
 
-size_t admm_small_lds_bytes(int64_t n, int64_t pc_entries) { return (size_t)(n * n + n + 3 * pc_entries) * sizeof(double) + 2 * sizeof(int); }
-
 int admm_small_workgroups(int64_t n, int maxc, int64_t pc_entries, int64_t tickets, int device) {
-    int cus = 0, per = 0;
-    hipError_t e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device);
+    int per = 0;
+    const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, admm_small_pick(maxc, pc_entries > 0), 256, small_image_bytes(n, pc_entries));
     if (e != hipSuccess) return -(int)e;
-    e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, admm_small_pick(maxc, pc_entries > 0), 256, admm_small_lds_bytes(n, pc_entries));
-    if (e != hipSuccess) return -(int)e;
-    if (per < 1) per = 1;
-    const int64_t cap = (int64_t)cus * per;
-    return (int)(tickets < cap ? tickets : cap);
+    return small_workgroup_cap(device, per, tickets);
 }
 
 int admm_small_launch(const AdmmSmallArgs &a, int maxc, int wgs, hipStream_t st) {
     const bool pc = a.cons != nullptr;
-    hipLaunchKernelGGL(admm_small_pick(maxc, pc), dim3((unsigned)wgs), dim3(256), admm_small_lds_bytes(a.P.n, pc ? a.P.m : 0), st, a);
+    hipLaunchKernelGGL(admm_small_pick(maxc, pc), dim3((unsigned)wgs), dim3(256), small_image_bytes(a.P.n, pc ? a.P.m : 0), st, a);
     return (int)hipGetLastError();
 }
 

@@ -177,7 +177,7 @@ struct qcqpmi_ctx {
     ncclComm_t comm = nullptr;
     int rank = 0, world = 1;
     double *d_comm = nullptr, *d_comm_big = nullptr;
-    int64_t comm_big_cap = 0;
+    size_t comm_big_cap = 0;     // bytes
     long long *d_prof = nullptr;
     int cd_stage = 0;                   // qcqpmi_cd_run_stage: last stage completed of a split run
     int64_t Xi_cap = 0;                 // doubles reserved for the standard normals of pop_sdr_sample
@@ -216,8 +216,8 @@ struct qcqpmi_ctx {
     bool cd_ref_order = false;   // qcqpmi_cd_reference_order: coupled constraints in the reference's summation order
     bool force_generic = false;  // debug/tests: run the general phase-2 kernel even when the pipelined one applies
     std::vector<int> last_st1, last_st2;   // per-restart status codes of the last coordinate-descent run (qcqpmi_cd_status)
-    // qcqpmi_cd_small_batch_run: ONE device buffer for the objectives, starts, per-restart outputs, points and winners of a call
-    // (grown on demand; the resident population and its buffers are never used by that call)
+    // capi_small.inc, the CD and ADMM batch calls: ONE device buffer for the objectives, starts, per-restart outputs, points and winners
+    // of a call (grown on demand; the resident population and its buffers are never used by that call)
     char *sb_work = nullptr;
     size_t sb_work_cap = 0;
     // qcqpmi_sdr_small_batch: d (n) when every coordinate carries exactly one constraint p x_i^2 + r == 0 with d_i = -r / p > 0 (the
@@ -716,6 +716,8 @@ int cd_run_general(qcqpmi_ctx *c, int phase1, int64_t num_iters, double viol_tol
     if ((rc = cd_apply_status(c, st, st1, f0, maxviol, GEN_CAP))) return rc;
     return 0;
 }
+
+#include "capi_small.inc"
 
 // ============================================================================================
 
@@ -1756,377 +1758,6 @@ int qcqpmi_cd_stream_run(qcqpmi_ctx *c, int64_t K, int64_t R, int generate, int 
     return 0;
 }
 
-// ---- B small problems (n <= 64) that share the context's separable constraints, R restarts each, in ONE launch of cd_small_kernel
-// (csrc/cd_small.hip).  Works in a buffer of its own: the resident population, its evaluation and its status codes are not touched,
-// whether the call succeeds or is refused.
-// cons == nullptr: the context's coefficients; else [B][m][3], per_problem set: qcqpmi_cd_small_batch_run_pc
-// maxn: CD_SMALL_MAXN for the two small-batch symbols; CD_WIDE_MAXN for qcqpmi_cd_batch_run, whose problems of more than CD_SMALL_MAXN
-// variables run the wide kernels (two coordinates per lane) -- everything else is the same call
-static int cd_small_batch(qcqpmi_ctx *c, int64_t maxn, bool per_problem, const double *cons, int64_t B, const double *P0s, const double *q0s, const double *r0s,
-                          int64_t R, int generate, const double *X0, int phase1, int64_t num_iters, double viol_tol, double tol, uint64_t seed,
-                          uint64_t seed_stride, uint64_t first_index, double select_tol, int64_t *sweeps1, int64_t *sweeps2,
-                          int64_t *visits2, int64_t *accepted2, uint8_t *ran_phase2, int *status1, int *status2, double *f0,
-                          double *maxviol, double *X, int64_t *best_index, double *best_f0, double *best_maxviol, double *best_x) {
-    int rc = check_ready(c, false);
-    if (rc) return rc;
-    if (!c->sep) return fail(c, QCQPMI_EUNSUPPORTED, "cd_small_batch_run: the constraints are not separable (a constraint couples coordinates, or a coordinate carries more than 4)");
-    if (c->n > maxn) return fail(c, QCQPMI_EUNSUPPORTED, "cd_small_batch_run: n = %lld, the small-problem kernel takes n <= %lld (%s)", (long long)c->n, (long long)maxn,
-                                 maxn > CD_SMALL_MAXN ? "two coordinates per lane" : "one lane per coordinate");
-    if (B < 1 || R < 1 || num_iters < 0 || !(tol > 0.0) || !P0s || !q0s || !r0s || (!generate && !X0))
-        return fail(c, QCQPMI_EINVAL, "cd_small_batch_run: bad B / R / num_iters / tol, or a missing input array");
-    if (B >= (1LL << 30) || R >= (1LL << 30) || B * R >= (1LL << 30)) return fail(c, QCQPMI_EINVAL, "cd_small_batch_run: B R = %lld restarts, at most 2^30 - 1 per call", (long long)(B * R));
-    const int64_t m = c->m;
-    if (per_problem) {
-        if (!cons) return fail(c, QCQPMI_EINVAL, "cd_small_batch_run_pc: missing cons (B x m x 3 coefficients)");
-        for (int64_t k = 0; k < B * m; k++) {
-            const double p = cons[3 * k], q = cons[3 * k + 1], r = cons[3 * k + 2];
-            if (!std::isfinite(p) || !std::isfinite(q) || !std::isfinite(r))
-                return fail(c, QCQPMI_EINVAL, "cd_small_batch_run_pc: constraint %lld of problem %lld holds a coefficient that is not finite", (long long)(k % m + 1), (long long)(k / m));
-            if (p == 0.0 && q == 0.0)
-                return fail(c, QCQPMI_EINVAL, "cd_small_batch_run_pc: constraint %lld of problem %lld has p == 0 and q == 0: it touches no coordinate", (long long)(k % m + 1), (long long)(k / m));
-        }
-        if (m == 0) cons = nullptr;       // nothing to stage: the shared kernels
-    }
-    HIPCHK(c, hipSetDevice(c->device));
-    const int64_t n = c->n, T = B * R;
-    // ---- carve the work buffer (every piece 256-byte aligned)
-    size_t off = 0;
-    auto take = [&off](size_t bytes) { const size_t o = off; off += (bytes + 255) / 256 * 256; return o; };
-    const size_t oP = take((size_t)B * n * n * 8), oq = take((size_t)B * n * 8), or0 = take((size_t)B * 8);
-    const size_t oX0 = take(generate ? 0 : (size_t)T * n * 8), oX = take((size_t)T * n * 8);
-    const size_t oout = take((size_t)T * 57);      // 4 x int64, 2 x double, 2 x int, 1 x uint8 per restart, array after array
-    const size_t oticket = take(2 * sizeof(int));
-    const size_t obi = take((size_t)B * 2 * sizeof(int64_t)), obk = take((size_t)B * 2 * sizeof(double)), obx = take((size_t)B * n * 8);
-    const size_t ocons = take(cons ? (size_t)B * m * 24 : 0);
-    if (off > c->sb_work_cap) {
-        HIPCHK(c, spin_sync(c->stream));
-        if (c->sb_work) (void)hipFree(c->sb_work);
-        c->sb_work = nullptr; c->sb_work_cap = 0;
-        HIPCHK(c, hipMalloc((void **)&c->sb_work, off));
-        c->sb_work_cap = off;
-    }
-    char *w = c->sb_work;
-    HIPCHK(c, hipMemcpyAsync(w + oP, P0s, (size_t)B * n * n * 8, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(w + oq, q0s, (size_t)B * n * 8, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(w + or0, r0s, (size_t)B * 8, hipMemcpyHostToDevice, c->stream));
-    if (!generate) HIPCHK(c, hipMemcpyAsync(w + oX0, X0, (size_t)T * n * 8, hipMemcpyHostToDevice, c->stream));
-    if (cons) HIPCHK(c, hipMemcpyAsync(w + ocons, cons, (size_t)B * m * 24, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemsetAsync(w + oticket, 0, 2 * sizeof(int), c->stream));
-    CdSmallArgs a;
-    a.P = c->dp; a.B = B; a.R = R;
-    a.P0s = (const double *)(w + oP); a.q0s = (const double *)(w + oq); a.r0s = (const double *)(w + or0);
-    a.X0 = generate ? nullptr : (const double *)(w + oX0);
-    a.cons = cons ? (const double *)(w + ocons) : nullptr;
-    a.generate = generate ? 1 : 0; a.phase1 = phase1 ? 1 : 0; a.num_iters = num_iters; a.viol_tol = viol_tol; a.tol = tol;
-    a.seed = seed; a.seed_stride = seed_stride; a.first_index = first_index;
-    a.ticket = (int *)(w + oticket);
-    char *o = w + oout;
-    a.sweeps1 = (int64_t *)o; a.sweeps2 = (int64_t *)(o + 8 * T); a.visits2 = (int64_t *)(o + 16 * T); a.accepted2 = (int64_t *)(o + 24 * T);
-    a.f0 = (double *)(o + 32 * T); a.maxviol = (double *)(o + 40 * T);
-    a.status1 = (int *)(o + 48 * T); a.status2 = (int *)(o + 52 * T); a.ran2 = (uint8_t *)(o + 56 * T);
-    a.X = (double *)(w + oX);
-    // tickets: whole problems when there are enough of them to fill the device, else chunks of at least one restart per wave of a workgroup
-    const int maxc = c->maxc <= 1 ? 1 : 4;
-    int threads = 0;
-    int wgs = cd_small_workgroups(n, maxc, cons ? m : 0, B * R, c->device, &threads);
-    if (wgs < 1) return fail(c, QCQPMI_EHIP, "cd_small_batch_run: occupancy query failed: %s", hipGetErrorString((hipError_t)(-wgs)));
-    int64_t chunks = B >= wgs ? 1 : (wgs + B - 1) / B;
-    const int64_t waves = threads / 64;
-    if (chunks > (R + waves - 1) / waves) chunks = (R + waves - 1) / waves;
-    a.RC = (R + chunks - 1) / chunks;
-    a.chunks = (R + a.RC - 1) / a.RC;
-    if (wgs > B * a.chunks) wgs = (int)(B * a.chunks);
-    (void)hipEventRecord(c->timers[2].beg, c->stream);
-    hipError_t qe = (hipError_t)cd_small_launch(a, maxc, wgs, threads, c->stream);
-    (void)hipEventRecord(c->timers[2].end, c->stream);
-    c->timers[2].valid = true;
-    if (qe != hipSuccess) return fail(c, QCQPMI_EHIP, "cd_small_batch_run: %s", hipGetErrorString(qe));
-    c->last_cd2_kernel = cd_small_name(maxc, cons != nullptr, n > CD_SMALL_MAXN);
-    const bool want_best = best_index || best_f0 || best_maxviol || best_x;
-    if (want_best) {       // QCQPForm.better folded over every problem's restarts, ties -> lowest index: one workgroup per problem
-        hipLaunchKernelGGL(select_best_kernel, dim3((unsigned)B), dim3(1024), 0, c->stream, (const double *)a.f0, (const double *)a.maxviol, R,
-                           select_tol, (int64_t *)(w + obi), (double *)(w + obk));
-        HIPCHK(c, hipGetLastError());
-        if (best_x) {
-            HIPCHK(c, hipMemsetAsync(w + obx, 0, (size_t)B * n * 8, c->stream));
-            qe = (hipError_t)cd_small_gather_launch(a.X, n, R, B, (const int64_t *)(w + obi), (double *)(w + obx), c->stream);
-            if (qe != hipSuccess) return fail(c, QCQPMI_EHIP, "cd_small_batch_run: %s", hipGetErrorString(qe));
-        }
-    }
-    std::vector<char> hout((size_t)T * 57);
-    std::vector<int64_t> bidx(want_best ? (size_t)B * 2 : 0);
-    std::vector<double> bkey(want_best ? (size_t)B * 2 : 0);
-    int flags[2] = {0, 0};
-    HIPCHK(c, hipMemcpyAsync(flags, w + oticket, sizeof(flags), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, spin_sync(c->stream));
-    if (flags[1]) return fail(c, QCQPMI_EINVAL, "cd_small_batch_run: an objective matrix P0_b is not symmetric (or holds a NaN)");
-    HIPCHK(c, hipMemcpyAsync(hout.data(), o, hout.size(), hipMemcpyDeviceToHost, c->stream));
-    if (X) HIPCHK(c, hipMemcpyAsync(X, a.X, (size_t)T * n * 8, hipMemcpyDeviceToHost, c->stream));
-    if (want_best) {
-        HIPCHK(c, hipMemcpyAsync(bidx.data(), w + obi, bidx.size() * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipMemcpyAsync(bkey.data(), w + obk, bkey.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-        if (best_x) HIPCHK(c, hipMemcpyAsync(best_x, w + obx, (size_t)B * n * 8, hipMemcpyDeviceToHost, c->stream));
-    }
-    HIPCHK(c, spin_sync(c->stream));
-    const char *h = hout.data();
-    const size_t n8 = (size_t)T * 8;
-    if (sweeps1) memcpy(sweeps1, h, n8);
-    if (sweeps2) memcpy(sweeps2, h + n8, n8);
-    if (visits2) memcpy(visits2, h + 2 * n8, n8);
-    if (accepted2) memcpy(accepted2, h + 3 * n8, n8);
-    if (f0) memcpy(f0, h + 4 * n8, n8);
-    if (maxviol) memcpy(maxviol, h + 5 * n8, n8);
-    if (status1) memcpy(status1, h + 6 * n8, (size_t)T * 4);
-    if (status2) memcpy(status2, h + 6 * n8 + (size_t)T * 4, (size_t)T * 4);
-    if (ran_phase2) memcpy(ran_phase2, h + 7 * n8, (size_t)T);
-    for (int64_t b = 0; b < B && want_best; b++) {
-        if (best_index) best_index[b] = bidx[(size_t)2 * b];
-        if (best_f0) best_f0[b] = bkey[(size_t)2 * b];
-        if (best_maxviol) best_maxviol[b] = bkey[(size_t)2 * b + 1];
-    }
-    return 0;
-}
-
-int qcqpmi_cd_small_batch_run(qcqpmi_ctx *c, int64_t B, const double *P0s, const double *q0s, const double *r0s, int64_t R, int generate,
-                              const double *X0, int phase1, int64_t num_iters, double viol_tol, double tol, uint64_t seed,
-                              uint64_t seed_stride, uint64_t first_index, double select_tol, int64_t *sweeps1, int64_t *sweeps2,
-                              int64_t *visits2, int64_t *accepted2, uint8_t *ran_phase2, int *status1, int *status2, double *f0,
-                              double *maxviol, double *X, int64_t *best_index, double *best_f0, double *best_maxviol, double *best_x) {
-    return cd_small_batch(c, CD_SMALL_MAXN, false, nullptr, B, P0s, q0s, r0s, R, generate, X0, phase1, num_iters, viol_tol, tol, seed, seed_stride, first_index,
-                          select_tol, sweeps1, sweeps2, visits2, accepted2, ran_phase2, status1, status2, f0, maxviol, X, best_index, best_f0,
-                          best_maxviol, best_x);
-}
-
-// ---- the same launch with PER-PROBLEM constraint coefficients: the context fixes the structure (which coordinate constraint k touches,
-// its relop), cons [B][m][3] holds (p, q, r) of constraint k of problem b (cd_small_kernel<MAXC, pc> stages them in LDS with P0_b).
-int qcqpmi_cd_small_batch_run_pc(qcqpmi_ctx *c, int64_t B, const double *P0s, const double *q0s, const double *r0s, const double *cons,
-                                 int64_t R, int generate, const double *X0, int phase1, int64_t num_iters, double viol_tol, double tol,
-                                 uint64_t seed, uint64_t seed_stride, uint64_t first_index, double select_tol, int64_t *sweeps1,
-                                 int64_t *sweeps2, int64_t *visits2, int64_t *accepted2, uint8_t *ran_phase2, int *status1, int *status2,
-                                 double *f0, double *maxviol, double *X, int64_t *best_index, double *best_f0, double *best_maxviol,
-                                 double *best_x) {
-    return cd_small_batch(c, CD_SMALL_MAXN, true, cons, B, P0s, q0s, r0s, R, generate, X0, phase1, num_iters, viol_tol, tol, seed, seed_stride, first_index,
-                          select_tol, sweeps1, sweeps2, visits2, accepted2, ran_phase2, status1, status2, f0, maxviol, X, best_index, best_f0,
-                          best_maxviol, best_x);
-}
-
-// ---- the batch for 1 <= n <= 128: what the two symbols above run for n <= 64 (cons == NULL: shared constraints), the wide kernels
-// cd_small_kernel<MAXC, pc, 2> (one wavefront per restart, two coordinates per lane) for 65 <= n <= 128
-int qcqpmi_cd_batch_run(qcqpmi_ctx *c, int64_t B, const double *P0s, const double *q0s, const double *r0s, const double *cons, int64_t R,
-                        int generate, const double *X0, int phase1, int64_t num_iters, double viol_tol, double tol, uint64_t seed,
-                        uint64_t seed_stride, uint64_t first_index, double select_tol, int64_t *sweeps1, int64_t *sweeps2, int64_t *visits2,
-                        int64_t *accepted2, uint8_t *ran_phase2, int *status1, int *status2, double *f0, double *maxviol, double *X,
-                        int64_t *best_index, double *best_f0, double *best_maxviol, double *best_x) {
-    return cd_small_batch(c, CD_WIDE_MAXN, cons != nullptr, cons, B, P0s, q0s, r0s, R, generate, X0, phase1, num_iters, viol_tol, tol, seed, seed_stride,
-                          first_index, select_tol, sweeps1, sweeps2, visits2, accepted2, ran_phase2, status1, status2, f0, maxviol, X, best_index,
-                          best_f0, best_maxviol, best_x);
-}
-
-// ---- improve(ADMM) for B small problems (n <= 64) over the context's separable constraint lists, R restarts each, in ONE launch of
-// admm_small_kernel (csrc/admm_small.hip).  Works in the buffer of the small-batch calls: the resident population, its evaluation, an
-// installed ADMM basis and qcqpmi_last_cd_kernel are not touched, whether the call succeeds or is refused.
-int qcqpmi_admm_small_batch_run(qcqpmi_ctx *c, int64_t B, const double *P0s, const double *q0s, const double *r0s, const double *cons,
-                                const double *rhos, const double *Minvs, int64_t R, int generate, const double *X0, int phase1,
-                                int64_t num_iters, double tol, double viol_lim, uint64_t seed, uint64_t seed_stride, uint64_t first_index,
-                                double select_tol, int64_t *iters1, int64_t *iters2, double *f0, double *maxviol, double *X,
-                                int64_t *best_index, double *best_f0, double *best_maxviol, double *best_x) {
-    int rc = check_ready(c, false);
-    if (rc) return rc;
-    if (!c->sep) return fail(c, QCQPMI_EUNSUPPORTED, "admm_small_batch_run: the constraints are not separable (a constraint couples coordinates, or a coordinate carries more than 4)");
-    if (c->n > ADMM_SMALL_MAXN) return fail(c, QCQPMI_EUNSUPPORTED, "admm_small_batch_run: n = %lld, the small-problem kernel takes n <= %d (one lane per coordinate)", (long long)c->n, ADMM_SMALL_MAXN);
-    if (B < 1 || R < 1 || num_iters < 0 || !P0s || !q0s || !r0s || !rhos || !Minvs || (!generate && !X0))
-        return fail(c, QCQPMI_EINVAL, "admm_small_batch_run: bad B / R / num_iters, or a missing input array");
-    if (B >= (1LL << 30) || R >= (1LL << 30) || B * R >= (1LL << 30)) return fail(c, QCQPMI_EINVAL, "admm_small_batch_run: B R = %lld restarts, at most 2^30 - 1 per call", (long long)(B * R));
-    const int64_t m = c->m;
-    if (m < 1) return fail(c, QCQPMI_EINVAL, "admm_small_batch_run: the context has no constraint (the consensus average divides by m)");
-    for (int64_t b = 0; b < B; b++)
-        if (!(rhos[b] > 0.0) || !std::isfinite(rhos[b]))
-            return fail(c, QCQPMI_EINVAL, "admm_small_batch_run: rho of problem %lld is not positive and finite", (long long)b);
-    for (int64_t k = 0; cons && k < B * m; k++) {
-        const double p = cons[3 * k], q = cons[3 * k + 1], r = cons[3 * k + 2];
-        if (!std::isfinite(p) || !std::isfinite(q) || !std::isfinite(r))
-            return fail(c, QCQPMI_EINVAL, "admm_small_batch_run: constraint %lld of problem %lld holds a coefficient that is not finite", (long long)(k % m + 1), (long long)(k / m));
-        if (p == 0.0 && q == 0.0)
-            return fail(c, QCQPMI_EINVAL, "admm_small_batch_run: constraint %lld of problem %lld has p == 0 and q == 0: it touches no coordinate", (long long)(k % m + 1), (long long)(k / m));
-    }
-    HIPCHK(c, hipSetDevice(c->device));
-    const int64_t n = c->n, T = B * R;
-    // ---- carve the work buffer (every piece 256-byte aligned)
-    size_t off = 0;
-    auto take = [&off](size_t bytes) { const size_t o = off; off += (bytes + 255) / 256 * 256; return o; };
-    const size_t oP = take((size_t)B * n * n * 8), oM = take((size_t)B * n * n * 8), oq = take((size_t)B * n * 8), or0 = take((size_t)B * 8);
-    const size_t orho = take((size_t)B * 8);
-    const size_t oX0 = take(generate ? 0 : (size_t)T * n * 8), oX = take((size_t)T * n * 8);
-    const size_t oout = take((size_t)T * 32);      // 2 x int64, 2 x double per restart, array after array
-    const size_t oticket = take(2 * sizeof(int));
-    const size_t obi = take((size_t)B * 2 * sizeof(int64_t)), obk = take((size_t)B * 2 * sizeof(double)), obx = take((size_t)B * n * 8);
-    const size_t ocons = take(cons ? (size_t)B * m * 24 : 0);
-    if (off > c->sb_work_cap) {
-        HIPCHK(c, spin_sync(c->stream));
-        if (c->sb_work) (void)hipFree(c->sb_work);
-        c->sb_work = nullptr; c->sb_work_cap = 0;
-        HIPCHK(c, hipMalloc((void **)&c->sb_work, off));
-        c->sb_work_cap = off;
-    }
-    char *w = c->sb_work;
-    HIPCHK(c, hipMemcpyAsync(w + oP, P0s, (size_t)B * n * n * 8, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(w + oM, Minvs, (size_t)B * n * n * 8, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(w + oq, q0s, (size_t)B * n * 8, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(w + or0, r0s, (size_t)B * 8, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(w + orho, rhos, (size_t)B * 8, hipMemcpyHostToDevice, c->stream));
-    if (!generate) HIPCHK(c, hipMemcpyAsync(w + oX0, X0, (size_t)T * n * 8, hipMemcpyHostToDevice, c->stream));
-    if (cons) HIPCHK(c, hipMemcpyAsync(w + ocons, cons, (size_t)B * m * 24, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemsetAsync(w + oticket, 0, 2 * sizeof(int), c->stream));
-    AdmmSmallArgs a;
-    a.P = c->dp; a.B = B; a.R = R;
-    a.P0s = (const double *)(w + oP); a.Minvs = (const double *)(w + oM); a.q0s = (const double *)(w + oq); a.r0s = (const double *)(w + or0);
-    a.rhos = (const double *)(w + orho);
-    a.X0 = generate ? nullptr : (const double *)(w + oX0);
-    a.cons = cons ? (const double *)(w + ocons) : nullptr;
-    a.generate = generate ? 1 : 0; a.phase1 = phase1 ? 1 : 0; a.num_iters = num_iters; a.tol = tol; a.viol_lim = viol_lim;
-    a.seed = seed; a.seed_stride = seed_stride; a.first_index = first_index;
-    a.ticket = (int *)(w + oticket);
-    char *o = w + oout;
-    a.iters1 = (int64_t *)o; a.iters2 = (int64_t *)(o + 8 * T); a.f0 = (double *)(o + 16 * T); a.maxviol = (double *)(o + 24 * T);
-    a.X = (double *)(w + oX);
-    // tickets: whole problems when there are enough of them to fill the device, else chunks of at least one restart per wave of a workgroup
-    const int maxc = c->maxc <= 1 ? 1 : 4;
-    int wgs = admm_small_workgroups(n, maxc, cons ? m : 0, B * R, c->device);
-    if (wgs < 1) return fail(c, QCQPMI_EHIP, "admm_small_batch_run: occupancy query failed: %s", hipGetErrorString((hipError_t)(-wgs)));
-    int64_t chunks = B >= wgs ? 1 : (wgs + B - 1) / B;
-    if (chunks > (R + 3) / 4) chunks = (R + 3) / 4;
-    a.RC = (R + chunks - 1) / chunks;
-    a.chunks = (R + a.RC - 1) / a.RC;
-    if (wgs > B * a.chunks) wgs = (int)(B * a.chunks);
-    hipError_t qe = (hipError_t)admm_small_launch(a, maxc, wgs, c->stream);
-    if (qe != hipSuccess) return fail(c, QCQPMI_EHIP, "admm_small_batch_run: %s", hipGetErrorString(qe));
-    c->last_admm_kernel = admm_small_name(maxc, cons != nullptr);
-    c->last_admm_C = 0;
-    const bool want_best = best_index || best_f0 || best_maxviol || best_x;
-    if (want_best) {       // QCQPForm.better folded over every problem's restarts, ties -> lowest index: one workgroup per problem
-        hipLaunchKernelGGL(select_best_kernel, dim3((unsigned)B), dim3(1024), 0, c->stream, (const double *)a.f0, (const double *)a.maxviol, R,
-                           select_tol, (int64_t *)(w + obi), (double *)(w + obk));
-        HIPCHK(c, hipGetLastError());
-        if (best_x) {
-            HIPCHK(c, hipMemsetAsync(w + obx, 0, (size_t)B * n * 8, c->stream));
-            qe = (hipError_t)cd_small_gather_launch(a.X, n, R, B, (const int64_t *)(w + obi), (double *)(w + obx), c->stream);
-            if (qe != hipSuccess) return fail(c, QCQPMI_EHIP, "admm_small_batch_run: %s", hipGetErrorString(qe));
-        }
-    }
-    std::vector<char> hout((size_t)T * 32);
-    std::vector<int64_t> bidx(want_best ? (size_t)B * 2 : 0);
-    std::vector<double> bkey(want_best ? (size_t)B * 2 : 0);
-    int flags[2] = {0, 0};
-    HIPCHK(c, hipMemcpyAsync(flags, w + oticket, sizeof(flags), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, spin_sync(c->stream));
-    if (flags[1]) return fail(c, QCQPMI_EINVAL, "admm_small_batch_run: a matrix P0_b or Minv_b is not symmetric (or holds a NaN)");
-    HIPCHK(c, hipMemcpyAsync(hout.data(), o, hout.size(), hipMemcpyDeviceToHost, c->stream));
-    if (X) HIPCHK(c, hipMemcpyAsync(X, a.X, (size_t)T * n * 8, hipMemcpyDeviceToHost, c->stream));
-    if (want_best) {
-        HIPCHK(c, hipMemcpyAsync(bidx.data(), w + obi, bidx.size() * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipMemcpyAsync(bkey.data(), w + obk, bkey.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-        if (best_x) HIPCHK(c, hipMemcpyAsync(best_x, w + obx, (size_t)B * n * 8, hipMemcpyDeviceToHost, c->stream));
-    }
-    HIPCHK(c, spin_sync(c->stream));
-    const char *h = hout.data();
-    const size_t n8 = (size_t)T * 8;
-    if (iters1) memcpy(iters1, h, n8);
-    if (iters2) memcpy(iters2, h + n8, n8);
-    if (f0) memcpy(f0, h + 2 * n8, n8);
-    if (maxviol) memcpy(maxviol, h + 3 * n8, n8);
-    for (int64_t b = 0; b < B && want_best; b++) {
-        if (best_index) best_index[b] = bidx[(size_t)2 * b];
-        if (best_f0) best_f0[b] = bkey[(size_t)2 * b];
-        if (best_maxviol) best_maxviol[b] = bkey[(size_t)2 * b + 1];
-    }
-    return 0;
-}
-
-// ---- suggest(SDR) for B small problems (n <= 64) of the unit-diagonal family that share the context's constraints x_i^2 == d_i: the
-// relaxation (mixing method), its multipliers and S samples per problem in ONE launch of sdr_small_kernel (csrc/sdr_small.hip).  Works
-// in a buffer of its own: the resident population, its evaluation, its status codes and qcqpmi_last_cd_kernel are not touched, whether
-// the call succeeds or is refused.
-// ds == nullptr: the context's d for every problem; else [B][n], per_problem set: qcqpmi_sdr_small_batch_pc
-static int sdr_small_batch(qcqpmi_ctx *c, bool per_problem, const double *ds, int64_t B, const double *P0s, const double *q0s, const double *r0s,
-                           int64_t S, int max_sweeps, double tol, uint64_t seed, uint64_t seed_stride, uint64_t first_index, const double *V0s,
-                           double *V, double *primal, double *y, int64_t *sweeps, double *X) {
-    int rc = check_ready(c, false);
-    if (rc) return rc;
-    if (c->n > SDR_SMALL_MAXN) return fail(c, QCQPMI_EUNSUPPORTED, "sdr_small_batch: n = %lld, the small-problem kernel takes n <= %d", (long long)c->n, SDR_SMALL_MAXN);
-    if (!c->sep || c->unit_d.empty()) return fail(c, QCQPMI_EUNSUPPORTED, "sdr_small_batch: the constraints are not of the unit-diagonal family (every coordinate exactly one constraint p x_i^2 + r == 0 with -r / p > 0)");
-    if (B < 1 || S < 0 || max_sweeps < 0 || !(tol >= 0.0) || !P0s || !q0s || !r0s)
-        return fail(c, QCQPMI_EINVAL, "sdr_small_batch: bad B / S / max_sweeps / tol, or a missing input array");
-    if (B >= (1LL << 30) || S >= (1LL << 30) || B * (S > 0 ? S : 1) >= (1LL << 30)) return fail(c, QCQPMI_EINVAL, "sdr_small_batch: B = %lld problems with S = %lld samples, at most 2^30 - 1 per call", (long long)B, (long long)S);
-    const int64_t n = c->n, N = n + 1;
-    if (per_problem) {
-        if (!ds) return fail(c, QCQPMI_EINVAL, "sdr_small_batch_pc: missing ds (B x n)");
-        for (int64_t k = 0; k < B * n; k++)
-            if (!(ds[k] > 0.0) || !std::isfinite(ds[k]))
-                return fail(c, QCQPMI_EINVAL, "sdr_small_batch_pc: d of coordinate %lld of problem %lld is not a positive finite number", (long long)(k % n), (long long)(k / n));
-    }
-    HIPCHK(c, hipSetDevice(c->device));
-    const int64_t ns = ds ? B * n : n;      // entries of s
-    // ---- carve the work buffer (every piece 256-byte aligned)
-    size_t off = 0;
-    auto take = [&off](size_t bytes) { const size_t o = off; off += (bytes + 255) / 256 * 256; return o; };
-    const size_t oP = take((size_t)B * n * n * 8), oq = take((size_t)B * n * 8), or0 = take((size_t)B * 8), os = take((size_t)ns * 8);
-    const size_t oV0 = take(V0s ? (size_t)B * N * SDR_SMALL_K * 8 : 0), oV = take((size_t)B * N * SDR_SMALL_K * 8);
-    const size_t opr = take((size_t)B * 8), oy = take((size_t)B * N * 8), osw = take((size_t)B * 8), oX = take((size_t)B * S * n * 8);
-    const size_t oticket = take(2 * sizeof(int));
-    if (off > c->ss_work_cap) {
-        HIPCHK(c, spin_sync(c->stream));
-        if (c->ss_work) (void)hipFree(c->ss_work);
-        c->ss_work = nullptr; c->ss_work_cap = 0;
-        HIPCHK(c, hipMalloc((void **)&c->ss_work, off));
-        c->ss_work_cap = off;
-    }
-    char *w = c->ss_work;
-    std::vector<double> sv((size_t)ns);
-    for (int64_t i = 0; i < ns; i++) sv[(size_t)i] = sqrt(ds ? ds[i] : c->unit_d[(size_t)i]);
-    HIPCHK(c, hipMemcpyAsync(w + oP, P0s, (size_t)B * n * n * 8, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(w + oq, q0s, (size_t)B * n * 8, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(w + or0, r0s, (size_t)B * 8, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(w + os, sv.data(), (size_t)ns * 8, hipMemcpyHostToDevice, c->stream));
-    if (V0s) HIPCHK(c, hipMemcpyAsync(w + oV0, V0s, (size_t)B * N * SDR_SMALL_K * 8, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemsetAsync(w + oticket, 0, 2 * sizeof(int), c->stream));
-    HIPCHK(c, spin_sync(c->stream));      // sv goes out of scope; the pageable copies above have been staged
-    SdrSmallArgs a;
-    a.n = (int)n; a.B = B; a.S = S;
-    a.s = (const double *)(w + os); a.s_stride = ds ? n : 0; a.P0s = (const double *)(w + oP); a.q0s = (const double *)(w + oq); a.r0s = (const double *)(w + or0);
-    a.V0s = V0s ? (const double *)(w + oV0) : nullptr;
-    a.max_sweeps = max_sweeps; a.tol = tol; a.seed = seed; a.seed_stride = seed_stride; a.first_index = first_index;
-    a.ticket = (int *)(w + oticket);
-    a.V = (double *)(w + oV); a.primal = (double *)(w + opr); a.y = (double *)(w + oy); a.sweeps = (int64_t *)(w + osw); a.X = (double *)(w + oX);
-    const int wgs = sdr_small_workgroups((int)n, B, c->device);
-    if (wgs < 1) return fail(c, QCQPMI_EHIP, "sdr_small_batch: occupancy query failed: %s", hipGetErrorString((hipError_t)(-wgs)));
-    const hipError_t qe = (hipError_t)sdr_small_launch(a, wgs, c->stream);
-    if (qe != hipSuccess) return fail(c, QCQPMI_EHIP, "sdr_small_batch: %s", hipGetErrorString(qe));
-    int flags[2] = {0, 0};
-    HIPCHK(c, hipMemcpyAsync(flags, w + oticket, sizeof(flags), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, spin_sync(c->stream));
-    if (flags[1]) return fail(c, QCQPMI_EINVAL, "sdr_small_batch: an objective matrix P0_b is not symmetric (or holds a NaN)");
-    if (V) HIPCHK(c, hipMemcpyAsync(V, a.V, (size_t)B * N * SDR_SMALL_K * 8, hipMemcpyDeviceToHost, c->stream));
-    if (primal) HIPCHK(c, hipMemcpyAsync(primal, a.primal, (size_t)B * 8, hipMemcpyDeviceToHost, c->stream));
-    if (y) HIPCHK(c, hipMemcpyAsync(y, a.y, (size_t)B * N * 8, hipMemcpyDeviceToHost, c->stream));
-    if (sweeps) HIPCHK(c, hipMemcpyAsync(sweeps, a.sweeps, (size_t)B * 8, hipMemcpyDeviceToHost, c->stream));
-    if (X && S > 0) HIPCHK(c, hipMemcpyAsync(X, a.X, (size_t)B * S * n * 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, spin_sync(c->stream));
-    return 0;
-}
-
-int qcqpmi_sdr_small_batch(qcqpmi_ctx *c, int64_t B, const double *P0s, const double *q0s, const double *r0s, int64_t S, int max_sweeps,
-                           double tol, uint64_t seed, uint64_t seed_stride, uint64_t first_index, const double *V0s, double *V,
-                           double *primal, double *y, int64_t *sweeps, double *X) {
-    return sdr_small_batch(c, false, nullptr, B, P0s, q0s, r0s, S, max_sweeps, tol, seed, seed_stride, first_index, V0s, V, primal, y, sweeps, X);
-}
-
-// ---- the same launch with PER-PROBLEM d: ds [B][n] replaces the context's d problem by problem (the context must still be of the family)
-int qcqpmi_sdr_small_batch_pc(qcqpmi_ctx *c, int64_t B, const double *P0s, const double *q0s, const double *r0s, const double *ds, int64_t S,
-                              int max_sweeps, double tol, uint64_t seed, uint64_t seed_stride, uint64_t first_index, const double *V0s,
-                              double *V, double *primal, double *y, int64_t *sweeps, double *X) {
-    return sdr_small_batch(c, true, ds, B, P0s, q0s, r0s, S, max_sweeps, tol, seed, seed_stride, first_index, V0s, V, primal, y, sweeps, X);
-}
-
 int qcqpmi_cd_stream_reserve(qcqpmi_ctx *c, int64_t K, int64_t R) {
     int rc = check_ready(c, false);
     if (rc) return rc;
@@ -2335,13 +1966,8 @@ int qcqpmi_comm_allreduce(qcqpmi_ctx *c, double *values, int64_t count, int op) 
     HIPCHK(c, hipSetDevice(c->device));
     double *buf = c->d_comm;
     if (count > 4) {      // the exchange of a streamed run (keys of all populations, then the winners' points): a buffer of its own
-        if (count > c->comm_big_cap) {
-            HIPCHK(c, spin_sync(c->stream));
-            if (c->d_comm_big) (void)hipFree(c->d_comm_big);
-            c->d_comm_big = nullptr; c->comm_big_cap = 0;
-            HIPCHK(c, hipMalloc((void **)&c->d_comm_big, (size_t)count * sizeof(double)));
-            c->comm_big_cap = count;
-        }
+        const int rc = grow_device_buffer(c, &c->d_comm_big, &c->comm_big_cap, (size_t)count * sizeof(double));
+        if (rc) return rc;
         buf = c->d_comm_big;
     }
     HIPCHK(c, hipMemcpyAsync(buf, values, (size_t)count * sizeof(double), hipMemcpyHostToDevice, c->stream));
@@ -2357,13 +1983,8 @@ int qcqpmi_comm_allgather(qcqpmi_ctx *c, const void *send, int64_t nbytes, void 
     if (!c->comm) return fail(c, QCQPMI_ESTATE, "comm_init has not been called");
     HIPCHK(c, hipSetDevice(c->device));
     const int64_t need = ((int64_t)(c->world + 1) * nbytes + 7) / 8;      // doubles: send area + receive area
-    if (need > c->comm_big_cap) {
-        HIPCHK(c, spin_sync(c->stream));
-        if (c->d_comm_big) (void)hipFree(c->d_comm_big);
-        c->d_comm_big = nullptr; c->comm_big_cap = 0;
-        HIPCHK(c, hipMalloc((void **)&c->d_comm_big, (size_t)need * sizeof(double)));
-        c->comm_big_cap = need;
-    }
+    const int rc = grow_device_buffer(c, &c->d_comm_big, &c->comm_big_cap, (size_t)need * sizeof(double));
+    if (rc) return rc;
     char *d_send = (char *)c->d_comm_big, *d_recv = d_send + nbytes;
     HIPCHK(c, hipMemcpyAsync(d_send, send, (size_t)nbytes, hipMemcpyHostToDevice, c->stream));
     NCCLCHK(c, rccl()->AllGather(d_send, d_recv, (size_t)nbytes, ncclInt8, c->comm, c->stream));

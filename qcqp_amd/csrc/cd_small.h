@@ -1,4 +1,4 @@
-// Small-problem batch kernel: interface between capi.hip and cd_small.hip (own translation unit).
+// Small-problem batch kernel: interface between capi.hip (its driver: capi_small.inc) and cd_small.hip (own translation unit).
 //
 // improve_coord_descent (qcqp.py:181-192) for B problems of n <= 64 variables that share ONE set of separable constraint lists
 // and differ in their objective (P0_b, q0_b, r0_b) -- a frame of MIMO detection problems: thousands of Boolean least squares
@@ -19,6 +19,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "kernels.h"
+#include "small_batch.h"      // the LDS image, the ticket frame, small_gather_launch
 
 namespace qcqpmi {
 
@@ -51,15 +52,11 @@ struct CdSmallArgs {
     const double *cons;          // per-problem constraint coefficients [B][m][3] = (p, q, r) in CONSTRAINT order, or nullptr: P's
 };
 
-// pc_entries: 0, or the m list entries whose (p, q, r) the per-problem-constraint kernels stage beside P0_b and q0_b
-size_t cd_small_lds_bytes(int64_t n, int64_t pc_entries);
-// workgroups of the launch (persistent: at most what the device holds at once), or < 0: -hipError_t; *threads: the size of a workgroup
+// workgroups of the launch (small_workgroup_cap; pc_entries: as small_image_bytes takes it), or < 0: -hipError_t; *threads: the size of a workgroup
 // -- 256 for n <= CD_SMALL_MAXN; for the wide kernels 256 or CD_WIDE_THREADS, whichever the occupancy query gives more resident waves
 // (a tie goes to the larger one)
 int cd_small_workgroups(int64_t n, int maxc, int64_t pc_entries, int64_t tickets, int device, int *threads);
 int cd_small_launch(const CdSmallArgs &a, int maxc, int wgs, int threads, hipStream_t st);      // a.cons != nullptr: the <MAXC, pc> kernels
 const char *cd_small_name(int maxc, bool pc, bool wide);
-// the winners' points: out[b][0..n) = X[b][idx[2 b]][0..n)  (idx as select_best_kernel leaves it; < 0: row left as it is)
-int cd_small_gather_launch(const double *X, int64_t n, int64_t R, int64_t B, const int64_t *idx, double *out, hipStream_t st);
 
 }  // namespace qcqpmi

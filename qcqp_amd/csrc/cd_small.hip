@@ -2,10 +2,7 @@
 // constraints and differ in their objective, R restarts each, inside one persistent launch (cd_small.h); in the per-problem-constraint
 // mode (cd_small_kernel<MAXC, true>) they share the STRUCTURE of the lists and problem b's coefficients are staged with its objective.
 //
-// Layout.  ONE WAVEFRONT PER (problem, restart), LANE = COORDINATE.  A workgroup of four waves draws a ticket -- a problem and a
-// chunk of its restarts -- from a global counter (an ordinary atomic add), stages P0_b (n x n doubles, at most 32 KB) and q0_b in
-// LDS once, and its waves take the chunk's restarts one by one from a counter in LDS.  After the barrier that follows the staging
-// a wave never waits for another one: no flags, no spinning; the next barrier is the one before the LDS image is replaced.
+// Layout: the ticket frame of small_batch.h around P0_b (n x n doubles, at most 32 KB), workgroups of four waves, LANE = COORDINATE.
 //   suggest(RANDOM)   lane j draws the keyed normal (seed_b, first_index + r, j) of qcqpmi_pop_randn;
 //   phase 1           every lane visits its own coordinate through p1_sep_visit (cd_phase1_sep.h) -- a sweep is element-wise for
 //                     separable constraints --, the sweep's max violation and "any update" are wave reductions; the loop and
@@ -109,7 +106,8 @@ __device__ inline double sm_point_viol(const DevProblem &P, int n, int lane, con
 }
 
 // a.P: the constraint lists the restart reads -- the context's, or the view of problem b's staged coefficients (cd_small_kernel).
-// PC only names the caller: every kernel keeps an instance of its own, inlined as the single-caller function it was.
+// PC only names the caller: every kernel keeps an instance of its own, inlined as the single-caller function it was.  It is NOT marked
+// always_inline (the mark costs a VGPR in two wide kernels): that no kernel calls it rests on the inliner; tools/asm_digest.py shows it.
 template <int MAXC, bool PC, int W>
 __device__ inline void sm_restart(const CdSmallArgs &a, const double *Ps, const double *qs, int64_t b, int64_t r, int lane) {
     const DevProblem &P = a.P;
@@ -261,74 +259,23 @@ __device__ inline void sm_restart(const CdSmallArgs &a, const double *Ps, const 
     }
 }
 
-// PC: per-problem constraint coefficients (cd_small.h).  The ticket's workgroup stages problem b's (p, q, r) of every list entry in
-// LDS beside P0_b and q0_b -- entry e of the context's lists (cptr order) is constraint cidx[e] of a.cons [B][m][3] -- and its waves
-// read their lists through the kernel's copy of the context's DevProblem, whose cp / cq / cr point at that image: cptr and crel stay
-// the context's, and the visit arithmetic is the one copy above.
+// PC: per-problem constraint coefficients (cd_small.h), staged by the frame; the visit arithmetic is the one copy above.
 // W = 2: the wide kernels (64 < n <= 128).  Their workgroup is CD_WIDE_THREADS threads or fewer (the launch decides; blockDim.x).
 template <int MAXC, bool PC = false, int W = 1>
 __global__ __launch_bounds__(W == 1 ? 256 : CD_WIDE_THREADS) void cd_small_kernel(CdSmallArgs a) {
     extern __shared__ double sm_lds[];
-    const int n = (int)a.P.n, m = PC ? (int)a.P.m : 0;
-    const int nt = W == 1 ? 256 : (int)blockDim.x;
-    double *Ps = sm_lds, *qs = sm_lds + n * n;
-    double *cs = qs + n;             // PC: [3][m] the staged coefficients, p then q then r
-    int *ctl = (int *)(cs + 3 * m);  // [0] the workgroup's ticket, [1] next restart of its chunk
-    const int *cidx = a.P.cidx;
-    if constexpr (PC) { a.P.cp = cs; a.P.cq = cs + m; a.P.cr = cs + 2 * m; }      // the view: cptr and crel stay the context's
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int64_t tickets = a.B * a.chunks;
-    for (;;) {
-        __syncthreads();             // every wave is done with the LDS image of the previous ticket
-        if (tid == 0) {
-            ctl[0] = __hip_atomic_fetch_add(a.ticket, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            ctl[1] = 0;
-        }
-        __syncthreads();
-        const int64_t tk = ctl[0];
-        if (tk >= tickets) break;
-        const int64_t b = tk / a.chunks, r_lo = (tk % a.chunks) * a.RC;
-        const int64_t r_hi = r_lo + a.RC < a.R ? r_lo + a.RC : a.R;
-        const double *Pg = a.P0s + b * n * n;
-        for (int e = tid; e < n * n; e += nt) Ps[e] = Pg[e];
-        if (tid < n) qs[tid] = a.q0s[b * n + tid];
-        if constexpr (PC) {
-            const double *cg = a.cons + b * m * 3;
-            for (int e = tid; e < m; e += nt) {
-                const double *ck = cg + (cidx[e] - 1) * 3;
-                cs[e] = ck[0]; cs[m + e] = ck[1]; cs[2 * m + e] = ck[2];
-            }
-        }
-        __syncthreads();
-        // the visits read column i as row i: a matrix that is not symmetric (or holds a NaN) makes the call fail
-        bool asym = false;
-        for (int e = tid; e < n * n; e += nt) {
-            const int i = e / n, j = e - i * n;
-            asym = asym || (j > i && !(Ps[e] == Ps[j * n + i]));
-        }
-        if (asym) a.ticket[1] = 1;
-        for (;;) {
-            int k = 0;
-            if (lane == 0) k = atomicAdd(&ctl[1], 1);
-            k = __builtin_amdgcn_readfirstlane(k);
-            if (r_lo + k >= r_hi) break;
-            sm_restart<MAXC, PC, W>(a, Ps, qs, b, r_lo + k, lane);
-        }
-    }
+    small_ticket_frame<PC>(
+        a, sm_lds, W == 1 ? 256 : (int)blockDim.x,
+        [&a](int64_t off, double *Ps, int nn, int tid, int nt) __attribute__((always_inline)) { small_stage_matrix(Ps, a.P0s + off, nn, tid, nt); return nullptr; },
+        [&a](const double *Ps, const double *qs, int64_t b, int64_t r, int lane) __attribute__((always_inline)) { sm_restart<MAXC, PC, W>(a, Ps, qs, b, r, lane); });
 }
 
-__global__ void cd_small_gather_kernel(const double *__restrict__ X, int64_t n, int64_t R, const int64_t *__restrict__ idx,
-                                       double *__restrict__ out) {
+__global__ void small_gather_kernel(const double *__restrict__ X, int64_t n, int64_t R, const int64_t *__restrict__ idx,
+                                    double *__restrict__ out) {
     const int64_t b = blockIdx.x, w = idx[2 * b];
     if (w < 0) return;
     for (int64_t j = threadIdx.x; j < n; j += blockDim.x) out[b * n + j] = X[(b * R + w) * n + j];
 }
-
-}  // namespace
-
-size_t cd_small_lds_bytes(int64_t n, int64_t pc_entries) { return (size_t)(n * n + n + 3 * pc_entries) * sizeof(double) + 2 * sizeof(int); }
-
-namespace {
 
 typedef void (*CdSmallKernel)(CdSmallArgs);
 
@@ -355,10 +302,9 @@ static int cd_wide_threads_asked() {
 }
 
 int cd_small_workgroups(int64_t n, int maxc, int64_t pc_entries, int64_t tickets, int device, int *threads) {
-    int cus = 0, per = 0;
-    hipError_t e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device);
-    if (e != hipSuccess) return -(int)e;
-    const size_t lds = cd_small_lds_bytes(n, pc_entries);
+    int per = 0;
+    hipError_t e;
+    const size_t lds = small_image_bytes(n, pc_entries);
     const CdSmallKernel k = cd_small_pick(n, maxc, pc_entries > 0);
     *threads = 256;
     if (n > CD_SMALL_MAXN) {      // the image passes 64 KB from n = 91
@@ -381,14 +327,12 @@ int cd_small_workgroups(int64_t n, int maxc, int64_t pc_entries, int64_t tickets
         e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, k, 256, lds);
         if (e != hipSuccess) return -(int)e;
     }
-    if (per < 1) per = 1;
-    const int64_t cap = (int64_t)cus * per;
-    return (int)(tickets < cap ? tickets : cap);
+    return small_workgroup_cap(device, per, tickets);
 }
 
 int cd_small_launch(const CdSmallArgs &a, int maxc, int wgs, int threads, hipStream_t st) {
     const bool pc = a.cons != nullptr;
-    const size_t lds = cd_small_lds_bytes(a.P.n, pc ? a.P.m : 0);
+    const size_t lds = small_image_bytes(a.P.n, pc ? a.P.m : 0);
     const CdSmallKernel k = cd_small_pick(a.P.n, maxc, pc);
     if (a.P.n > CD_SMALL_MAXN) {
         const hipError_t e = hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -407,8 +351,8 @@ const char *cd_small_name(int maxc, bool pc, bool wide) {
     return maxc <= 1 ? "cd_small_kernel<1>" : "cd_small_kernel<4>";
 }
 
-int cd_small_gather_launch(const double *X, int64_t n, int64_t R, int64_t B, const int64_t *idx, double *out, hipStream_t st) {
-    hipLaunchKernelGGL(cd_small_gather_kernel, dim3((unsigned)B), dim3(64), 0, st, X, n, R, idx, out);
+int small_gather_launch(const double *X, int64_t n, int64_t R, int64_t B, const int64_t *idx, double *out, hipStream_t st) {
+    hipLaunchKernelGGL(small_gather_kernel, dim3((unsigned)B), dim3(64), 0, st, X, n, R, idx, out);
     return (int)hipGetLastError();
 }
 

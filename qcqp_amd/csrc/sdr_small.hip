@@ -19,6 +19,7 @@
 
 #include "philox.h"
 #include "dev_util.h"
+#include "small_batch.h"    // small_workgroup_cap
 
 namespace qcqpmi {
 namespace {
@@ -158,17 +159,13 @@ size_t sdr_small_lds_bytes(int n) {
 }
 
 int sdr_small_workgroups(int n, int64_t B, int device) {
-    int cus = 0, per = 0;
-    hipError_t e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device);
-    if (e != hipSuccess) return -(int)e;
+    int per = 0;
     const size_t lds = sdr_small_lds_bytes(n);
-    e = hipFuncSetAttribute((const void *)sdr_small_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipError_t e = hipFuncSetAttribute((const void *)sdr_small_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return -(int)e;
     e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, sdr_small_kernel, 64, lds);
     if (e != hipSuccess) return -(int)e;
-    if (per < 1) per = 1;
-    const int64_t cap = (int64_t)cus * per;
-    return (int)(B < cap ? B : cap);
+    return small_workgroup_cap(device, per, B);
 }
 
 int sdr_small_launch(const SdrSmallArgs &a, int wgs, hipStream_t st) {

@@ -1,0 +1,107 @@
+// Small-problem batch: what the batch kernels (cd_small.hip, admm_small.hip, sdr_small.hip) and their drivers (capi_small.inc) share.
+//
+// The ticket frame.  A persistent workgroup draws a ticket -- a problem b and a chunk [r_lo, r_hi) of its R restarts -- from a global
+// counter (an ordinary atomic add), stages the problem's LDS image once
+//        A_b [n][n] | q0_b [n] | per-problem coefficients [3][m] (p, then q, then r; PC only) | two control words
+// and its waves take the chunk's restarts one by one from a counter in LDS: ONE WAVEFRONT PER (problem, restart).  After the barrier
+// that follows the staging a wave never waits for another one: no flags, no spinning; the next barrier is the one before the image
+// is replaced.  The restarts read column i of A_b as ROW i of the image, so a matrix that is not symmetric (or holds a NaN) sets
+// ticket[1] and the call fails.  sdr_small_kernel has a loop of its own (one wave per problem) and shares the host helpers only.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include <type_traits>
+
+namespace qcqpmi {
+
+// bytes of the LDS image; pc_entries: 0, or the m list entries whose (p, q, r) the per-problem-constraint kernels stage
+inline size_t small_image_bytes(int64_t n, int64_t pc_entries) { return (size_t)(n * n + n + 3 * pc_entries) * sizeof(double) + 2 * sizeof(int); }
+
+// workgroups of a persistent launch: what the device holds at once (`per` workgroups on each CU: the occupancy query's answer, taken
+// as at least one), at most one per ticket; or < 0: -hipError_t
+inline int small_workgroup_cap(int device, int per, int64_t tickets) {
+    int cus = 0;
+    const hipError_t e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device);
+    if (e != hipSuccess) return -(int)e;
+    const int64_t cap = (int64_t)cus * (per < 1 ? 1 : per);
+    return (int)(tickets < cap ? tickets : cap);
+}
+
+// the winners' points: out[b][0..n) = X[b][idx[2 b]][0..n)  (idx as select_best_kernel leaves it; < 0: row left as it is); cd_small.hip
+int small_gather_launch(const double *X, int64_t n, int64_t R, int64_t B, const int64_t *idx, double *out, hipStream_t st);
+
+// ---- staging, by the nt threads of the workgroup (nn = n n entries; off: problem b's offset b n in q0s)
+__device__ __attribute__((always_inline)) inline void small_stage_matrix(double *As, const double *Ag, int nn, int tid, int nt) {
+    for (int e = tid; e < nn; e += nt) As[e] = Ag[e];
+}
+
+__device__ __attribute__((always_inline)) inline void small_stage_q(double *qs, const double *q0s, int64_t off, int n, int tid) {
+    if (tid < n) qs[tid] = q0s[off + tid];
+}
+
+// entry e of the context's lists (cptr order) is constraint cidx[e] of cg [m][3] = (p, q, r) in CONSTRAINT order
+__device__ __attribute__((always_inline)) inline void small_stage_cons(double *cs, const double *cg, const int *cidx, int m, int tid, int nt) {
+    for (int e = tid; e < m; e += nt) {
+        const double *ck = cg + (cidx[e] - 1) * 3;
+        cs[e] = ck[0]; cs[m + e] = ck[1]; cs[2 * m + e] = ck[2];
+    }
+}
+
+// does the staged image As -- or G, a second n x n matrix the restarts read from global memory (nullptr, the constant: none) -- differ
+// from its transpose somewhere (a NaN differs from itself)?  This thread's share of the entries.
+template <class Second>
+__device__ __attribute__((always_inline)) inline bool small_asym_scan(const double *As, Second G, int n, int nn, int tid, int nt) {
+    bool asym = false;
+    for (int e = tid; e < nn; e += nt) {
+        const int i = e / n, j = e - i * n;
+        if constexpr (std::is_null_pointer_v<Second>) asym = asym || (j > i && !(As[e] == As[j * n + i]));
+        else asym = asym || (j > i && (!(As[e] == As[j * n + i]) || !(G[e] == G[j * n + i])));
+    }
+    return asym;
+}
+
+// The frame.  a: the kernel's argument struct (P, B, R, RC, chunks, q0s, cons, ticket); lds: small_image_bytes of dynamic LDS; nt: threads.
+//   stage(off, As, nn, tid, nt)    copies problem b's matrix into the image (off = b n n) and returns the G of small_asym_scan;
+//   restart(As, qs, b, r, lane)    one restart, by one wave.
+// Both are lambdas marked __attribute__((always_inline)): the kernel stays ONE function.  The frame hands down n n and the offsets
+// so that the kernels keep the register counts of the frame written out (profiles/r15_small_batch_refactor.md).
+// PC: problem b's (p, q, r) of every list entry are staged too and the restarts read them through a.P, the kernel's copy of the
+// context's DevProblem, whose cp / cq / cr point at that image; cptr and crel stay the context's.
+template <bool PC, class Args, class Stage, class Restart>
+__device__ __attribute__((always_inline)) inline void small_ticket_frame(Args &a, double *lds, int nt, Stage stage, Restart restart) {
+    const int n = (int)a.P.n, nn = n * n, m = PC ? (int)a.P.m : 0;
+    double *As = lds, *qs = lds + nn;
+    double *cs = qs + n;             // PC: [3][m] the staged coefficients, p then q then r
+    int *ctl = (int *)(cs + 3 * m);  // [0] the workgroup's ticket, [1] next restart of its chunk
+    const int *cidx = a.P.cidx;
+    if constexpr (PC) { a.P.cp = cs; a.P.cq = cs + m; a.P.cr = cs + 2 * m; }      // the view
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int64_t tickets = a.B * a.chunks;
+    for (;;) {
+        __syncthreads();             // every wave is done with the LDS image of the previous ticket
+        if (tid == 0) {
+            ctl[0] = __hip_atomic_fetch_add(a.ticket, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            ctl[1] = 0;
+        }
+        __syncthreads();
+        const int64_t tk = ctl[0];
+        if (tk >= tickets) break;
+        const int64_t b = tk / a.chunks, r_lo = (tk % a.chunks) * a.RC;
+        const int64_t r_hi = r_lo + a.RC < a.R ? r_lo + a.RC : a.R;
+        const int64_t bn = b * n;    // problem b's offset in q0s; bn n: in the [B][n][n] arrays
+        const auto G = stage(bn * n, As, nn, tid, nt);
+        small_stage_q(qs, a.q0s, bn, n, tid);
+        if constexpr (PC) small_stage_cons(cs, a.cons + b * m * 3, cidx, m, tid, nt);
+        __syncthreads();
+        if (small_asym_scan(As, G, n, nn, tid, nt)) a.ticket[1] = 1;
+        for (;;) {
+            int k = 0;
+            if (lane == 0) k = atomicAdd(&ctl[1], 1);
+            k = __builtin_amdgcn_readfirstlane(k);
+            if (r_lo + k >= r_hi) break;
+            restart(As, qs, b, r_lo + k, lane);
+        }
+    }
+}
+
+}  // namespace qcqpmi

@@ -236,14 +236,19 @@ class Engine(object):
         return self._cd_batch('cd_batch_run', P0s, q0s, r0s, R, X0, phase1, num_iters, viol_tol, tol, seed, seed_stride, first_index,
                               select_tol, want_x, cons)
 
-    def _cd_batch(self, name, P0s, q0s, r0s, R, X0, phase1, num_iters, viol_tol, tol, seed, seed_stride, first_index, select_tol, want_x,
-                  cons):
+    def _batch_inputs(self, name, P0s, q0s, r0s, R, X0, cons, extra=None):
+        """The arrays of a small-problem batch call as contiguous float64, checked against B = len(P0s) and this context's n and m.
+        extra: (rhos, Minvs) of the ADMM call.  Returns B, R, P0s, q0s, r0s, X0, cons, extra."""
         P0s = np.ascontiguousarray(P0s, dtype=np.float64)
         q0s = np.ascontiguousarray(q0s, dtype=np.float64)
         r0s = np.ascontiguousarray(r0s, dtype=np.float64).ravel()
         B, R, n = int(P0s.shape[0]) if P0s.ndim == 3 else 0, int(R), self.n
-        if P0s.shape != (B, n, n) or q0s.shape != (B, n) or r0s.shape != (B,):
-            raise ValueError('%s: expected P0s (B, n, n), q0s (B, n), r0s (B,) with n = %d' % (name, n))
+        ok, expected = P0s.shape == (B, n, n) and q0s.shape == (B, n) and r0s.shape == (B,), 'P0s (B, n, n), q0s (B, n), r0s (B,)'
+        if extra is not None:
+            extra = (np.ascontiguousarray(extra[0], dtype=np.float64).ravel(), np.ascontiguousarray(extra[1], dtype=np.float64))
+            ok, expected = ok and extra[0].shape == (B,) and extra[1].shape == (B, n, n), 'P0s and Minvs (B, n, n), q0s (B, n), r0s and rhos (B,)'
+        if not ok:
+            raise ValueError('%s: expected %s with n = %d' % (name, expected, n))
         if X0 is not None:
             X0 = np.ascontiguousarray(X0, dtype=np.float64)
             if X0.shape != (B, R, n):
@@ -252,7 +257,12 @@ class Engine(object):
             cons = np.ascontiguousarray(cons, dtype=np.float64)
             if cons.shape != (B, self.m, 3):
                 raise ValueError('%s: expected cons of shape (B, m, 3) with m = %d' % (name, self.m))
-        T = B * R
+        return B, R, P0s, q0s, r0s, X0, cons, extra
+
+    def _cd_batch(self, name, P0s, q0s, r0s, R, X0, phase1, num_iters, viol_tol, tol, seed, seed_stride, first_index, select_tol, want_x,
+                  cons):
+        B, R, P0s, q0s, r0s, X0, cons, _ = self._batch_inputs(name, P0s, q0s, r0s, R, X0, cons)
+        n, T = self.n, B * R
         out = dict(sweeps1=np.zeros(T, dtype=np.int64), sweeps2=np.zeros(T, dtype=np.int64), visits2=np.zeros(T, dtype=np.int64),
                    accepted2=np.zeros(T, dtype=np.int64), ran_phase2=np.zeros(T, dtype=np.uint8), status1=np.zeros(T, dtype=np.int32),
                    status2=np.zeros(T, dtype=np.int32), f0=np.empty(T), maxviol=np.empty(T), X=np.empty((B, R, n)) if want_x else None,
@@ -393,23 +403,8 @@ class Engine(object):
         X0 (B, R, n).  Returns the dictionary of admm_run with arrays of shape (B, R) -- iters1, iters2 (the reference's counts), f0,
         maxviol --, X (B, R, n) if want_x, and per problem best_index / best_f0 / best_maxviol (B,) and best_x (B, n).  cons (B, m, 3):
         per-problem constraint coefficients as cd_small_batch_run takes them.  The resident population is not touched."""
-        P0s = np.ascontiguousarray(P0s, dtype=np.float64)
-        q0s = np.ascontiguousarray(q0s, dtype=np.float64)
-        r0s = np.ascontiguousarray(r0s, dtype=np.float64).ravel()
-        rhos = np.ascontiguousarray(rhos, dtype=np.float64).ravel()
-        Minvs = np.ascontiguousarray(Minvs, dtype=np.float64)
-        B, R, n = int(P0s.shape[0]) if P0s.ndim == 3 else 0, int(R), self.n
-        if P0s.shape != (B, n, n) or q0s.shape != (B, n) or r0s.shape != (B,) or rhos.shape != (B,) or Minvs.shape != (B, n, n):
-            raise ValueError('admm_small_batch_run: expected P0s and Minvs (B, n, n), q0s (B, n), r0s and rhos (B,) with n = %d' % n)
-        if X0 is not None:
-            X0 = np.ascontiguousarray(X0, dtype=np.float64)
-            if X0.shape != (B, R, n):
-                raise ValueError('admm_small_batch_run: expected X0 of shape (B, R, n)')
-        if cons is not None:
-            cons = np.ascontiguousarray(cons, dtype=np.float64)
-            if cons.shape != (B, self.m, 3):
-                raise ValueError('admm_small_batch_run: expected cons of shape (B, m, 3) with m = %d' % self.m)
-        T = max(B * R, 0)
+        B, R, P0s, q0s, r0s, X0, cons, (rhos, Minvs) = self._batch_inputs('admm_small_batch_run', P0s, q0s, r0s, R, X0, cons, extra=(rhos, Minvs))
+        n, T = self.n, max(B * R, 0)
         out = dict(iters1=np.zeros(T, dtype=np.int64), iters2=np.zeros(T, dtype=np.int64), f0=np.empty(T), maxviol=np.empty(T),
                    X=np.empty((B, max(R, 0), n)) if want_x else None, best_index=np.zeros(B, dtype=np.int64), best_f0=np.empty(B),
                    best_maxviol=np.empty(B), best_x=np.zeros((B, n)))

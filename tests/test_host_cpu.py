@@ -873,7 +873,8 @@ def test_shared_device_helpers_are_defined_once():
     """The helpers several kernel files use have ONE definition under csrc/ (they used to be copied under per-file prefixes: a
     fix had to be made in two or three places and nothing failed when one was missed)."""
     from qcqp_amd import _build
-    names = ['block_rows_times_X', 'keyed_normal_pair', 'ordered_key', 'ordered_unkey', 'wave_max', 'p1_class_visit']
+    names = ['block_rows_times_X', 'keyed_normal_pair', 'ordered_key', 'ordered_unkey', 'wave_max', 'p1_class_visit',
+             'small_ticket_frame', 'small_stage_matrix', 'small_stage_q', 'small_stage_cons', 'small_asym_scan']
     text = {f: open(os.path.join(_build.SRC, f)).read() for f in os.listdir(_build.SRC) if f.endswith(('.hip', '.h', '.inc'))}
     for name in names:
         # a line that starts the definition: qualifiers and a return type at the start of the line, then NAME( -- a call sits
