@@ -479,7 +479,7 @@ int qcqpmi_admm_small_batch_run(qcqpmi_ctx *ctx, int64_t B, const double *P0s, c
                                 uint64_t first_index, double select_tol, int64_t *iters1, int64_t *iters2, double *f0, double *maxviol,
                                 double *X, int64_t *best_index, double *best_f0, double *best_maxviol, double *best_x);
 /* Device and pinned-host buffers for a qcqpmi_cd_stream_run(K, R) to come (population, per-restart outputs, per-population
- * winners): allocation only, so that a timed or latency-sensitive run does not start with hipMalloc / hipHostMalloc.  A
+ * winners; with an objective factor set, the buffers of the factored kernel's pre-passes: slacks and Y0 = L^T x0): allocation only, so that a timed or latency-sensitive run does not start with hipMalloc / hipHostMalloc.  A
  * resident population smaller than K R points is dropped (like any reallocation of the population). */
 int qcqpmi_cd_stream_reserve(qcqpmi_ctx *ctx, int64_t K, int64_t R);
 /* Which lifecycle kernel qcqpmi_cd_stream_run launches: 0 (default) the faster one for the shape -- cd_life_kernel (csrc/cd_life.hip,

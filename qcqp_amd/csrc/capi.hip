@@ -208,6 +208,7 @@ struct qcqpmi_ctx {
     int *l2_abort = nullptr;
     int *l2_cuslot = nullptr;    // [4096] arrival counters per compute unit of cd_life_kernel (zeroed before every launch)
     double *l2_preslack = nullptr; int64_t l2_preslack_cap = 0;    // [K R] slack of the prebuilt columns (cd_life2_prep_launch)
+    double *l2_y0 = nullptr; size_t l2_y0_cap = 0;                 // [tile][16 lr_RB][16] Y0 = L^T x0 of the preloaded restarts (cd_life2_y0_launch)
     // factored objective P0 = L L^T (qcqpmi_cd_set_objective_factor): L (n16 x 16 lr_RB, zero-padded) and its fragment packs
     double *lr_L = nullptr, *lr_G = nullptr, *lr_U = nullptr; int lr_RB = 0;
     int life_version = 0;        // qcqpmi_cd_life_version: 0 = the faster one for the shape, 2 = cd_life_kernel wherever it applies, 1 = cd_phase2_qs_kernel<lifecycle> only
@@ -769,7 +770,7 @@ void qcqpmi_ctx_destroy(qcqpmi_ctx *c) {
     admm_free(c, false);
     for (void *p : c->prob_allocs) (void)hipFree(p);
     void *ptrs[] = {c->d_Fpack, c->d_Frow, c->d_mu, c->d_best_idx, c->d_best_key, c->d_comm, c->d_comm_big,   // d_gP is in prob_allocs
-                    c->dn_G, c->dn_Dg, c->dn_Ft, c->dn_prof, c->dn_state, c->d_planes, c->d_out, c->d_wS, c->d_wY, c->d_ww, c->d_wz, c->af_work, c->d_qnext, c->d_life, c->d_life_prof, c->d_bestK_idx, c->d_bestK_key, c->d_bestK_x, c->l2_scratch, c->l2_D, c->l2_S, c->l2_abort, c->l2_cuslot, c->l2_preslack, c->lr_L, c->lr_G, c->lr_U, c->sb_work, c->ss_work};
+                    c->dn_G, c->dn_Dg, c->dn_Ft, c->dn_prof, c->dn_state, c->d_planes, c->d_out, c->d_wS, c->d_wY, c->d_ww, c->d_wz, c->af_work, c->d_qnext, c->d_life, c->d_life_prof, c->d_bestK_idx, c->d_bestK_key, c->d_bestK_x, c->l2_scratch, c->l2_D, c->l2_S, c->l2_abort, c->l2_cuslot, c->l2_preslack, c->l2_y0, c->lr_L, c->lr_G, c->lr_U, c->sb_work, c->ss_work};
     if (c->h_out) (void)hipHostFree(c->h_out);
     if (c->h_pin) (void)hipHostFree(c->h_pin);
     for (void *p : ptrs) if (p) (void)hipFree(p);
@@ -1575,6 +1576,35 @@ static int cd_life2_reserve(qcqpmi_ctx *c, int nmw, int cus) {
     return 0;
 }
 
+// Preloaded restarts of a prebuilt factored run of KR restarts (CdLife::y0_count): the leading ones, as many as QCQPMI_L2_Y0_MAX allows
+// (unset: all; 0: none -- every restart takes its loading sweep inside the launch, the A / B reference) and as fit L2_Y0_BUDGET bytes of
+// Y0 (whole tiles of 16 restarts x 16 RB rows; the headline's 81 920 restarts at rank 256 take 168 MB).  The rest load in-kernel: the
+// same bits either way, no second code path.
+constexpr int64_t L2_Y0_BUDGET = (int64_t)2 << 30;
+static int64_t cd_life2_y0_count(int64_t KR, int RB) {
+    int64_t cnt = KR;
+    if (const char *ev = getenv("QCQPMI_L2_Y0_MAX")) { const long long m = atoll(ev); cnt = m < 0 ? 0 : (m < cnt ? m : cnt); }
+    const int64_t fit = L2_Y0_BUDGET / ((int64_t)RB * 16 * 16 * (int64_t)sizeof(double)) * 16;
+    return cnt < fit ? cnt : fit;
+}
+
+// buffers of the pre-passes of a prebuilt factored run of KR restarts: the slacks (cd_life_prep_kernel) and Y0 (cd_life_y0_kernel)
+static int cd_life2_pre_reserve(qcqpmi_ctx *c, int64_t KR, int RB) {
+    int rc;
+    if (KR > c->l2_preslack_cap) {
+        if (c->l2_preslack) { HIPCHK(c, spin_sync(c->stream)); (void)hipFree(c->l2_preslack); c->l2_preslack = nullptr; c->l2_preslack_cap = 0; }
+        if ((rc = dev_alloc(c, &c->l2_preslack, (size_t)KR))) return rc;
+        c->l2_preslack_cap = KR;
+    }
+    const size_t need = (size_t)((cd_life2_y0_count(KR, RB) + 15) / 16) * (size_t)RB * 256;
+    if (need > c->l2_y0_cap) {
+        if (c->l2_y0) { HIPCHK(c, spin_sync(c->stream)); (void)hipFree(c->l2_y0); c->l2_y0 = nullptr; c->l2_y0_cap = 0; }
+        if ((rc = dev_alloc(c, &c->l2_y0, need, false))) return rc;      // (every element a restart reads is written by the pre-pass)
+        c->l2_y0_cap = need;
+    }
+    return 0;
+}
+
 // ---- lifecycle run: K populations of R restarts through ONE persistent slot-queue launch (cd_queue.h, CdLife)
 // Takes (cd_life2_config): separable constraints, up to four classes with up to two constraints per coordinate on a diagonal of P0 that is
 // positive everywhere or zero everywhere; ONE class with one constraint per coordinate on a diagonal of mixed sign (round 7, the SGN
@@ -1639,14 +1669,15 @@ int qcqpmi_cd_stream_run(qcqpmi_ctx *c, int64_t K, int64_t R, int generate, int 
     const char *pre_ev = getenv("QCQPMI_L2_PREBUILT");
     const bool pre = lr && !(pre_ev && atoi(pre_ev) == 0);
     L.prebuilt = pre ? 1 : 0; L.preslack = nullptr;
+    L.y0_count = 0; L.y0 = nullptr;
     if (pre) {
-        if (K * R > c->l2_preslack_cap) {
-            if (c->l2_preslack) { HIPCHK(c, spin_sync(c->stream)); (void)hipFree(c->l2_preslack); c->l2_preslack = nullptr; c->l2_preslack_cap = 0; }
-            if ((rc = dev_alloc(c, &c->l2_preslack, (size_t)(K * R)))) return rc;
-            c->l2_preslack_cap = K * R;
-        }
+        // (qcqpmi_cd_stream_reserve has done this for a caller that wants no allocation here)
+        if ((rc = cd_life2_pre_reserve(c, K * R, factor_rb))) return rc;
         L.preslack = c->l2_preslack;
+        L.y0_count = cd_life2_y0_count(K * R, factor_rb);
+        L.y0 = c->l2_y0;
     }
+    const int64_t y0_count = L.y0_count;
     if (c->profile) {      // qcqpmi_debug_profile: tick sums of the launch (qcqpmi_debug_life_profile)
         if (!c->d_life_prof) HIPCHK(c, hipMalloc((void **)&c->d_life_prof, 24 * sizeof(long long)));
         HIPCHK(c, hipMemsetAsync(c->d_life_prof, 0, 24 * sizeof(long long), c->stream));
@@ -1686,6 +1717,8 @@ int qcqpmi_cd_stream_run(qcqpmi_ctx *c, int64_t K, int64_t R, int generate, int 
         (void)hipEventRecord(c->timers[2].beg, c->stream);       // (the event window spans the pre-pass too)
         const double l1 = stnow();
         hipError_t qe = pre ? (hipError_t)cd_life2_prep_launch(c->dp, c->d_life, c->X, K * R, num_iters, tol, c->stream) : hipSuccess;
+        if (qe == hipSuccess && y0_count > 0)
+            qe = (hipError_t)cd_life2_y0_launch(c->X, c->lr_U, c->l2_y0, (int)(c->n16 / 16), factor_rb, c->n16, y0_count, c->stream);
         if (qe == hipSuccess) qe = (hipError_t)cd_life2_launch(qa, nmw, cs2, kind, tiles, (int)wgs, c->stream);
         const double l2 = stnow();
         (void)hipEventRecord(c->timers[2].end, c->stream);
@@ -1772,6 +1805,12 @@ int qcqpmi_cd_stream_reserve(qcqpmi_ctx *c, int64_t K, int64_t R) {
         int nmw = 0, cs2 = 0, kind = 0, cus = 0;
         HIPCHK(c, hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device));
         if (c->life_version != 1 && c->sep && cd_life2_config(c->dp, c->Kreal, c->objclass, c->symcls, c->lr_RB, &nmw, &cs2, &kind) && (rc = cd_life2_reserve(c, nmw, cus))) return rc;
+        // the factored instantiation's pre-passes (the same conditions as qcqpmi_cd_stream_run)
+        const int factor_rb = (c->lr_RB > 0 && c->life_version != 3 && cd_life2_factor_ok(c->dp, 16 * (int64_t)c->lr_RB)) ? c->lr_RB : 0;
+        const bool lr = factor_rb > 0 && c->life_version != 1 && !c->force_generic && !(c->dbg & 64) && c->sep &&
+                        cd_life2_config(c->dp, c->Kreal, c->objclass, c->symcls, factor_rb, &nmw, &cs2, &kind) && nmw == 3 && (kind == L2_KIND_BAND || kind == L2_KIND_GEN);
+        const char *pre_ev = getenv("QCQPMI_L2_PREBUILT");
+        if (lr && !(pre_ev && atoi(pre_ev) == 0) && (rc = cd_life2_pre_reserve(c, K * R, factor_rb))) return rc;
     }
     return 0;
 }

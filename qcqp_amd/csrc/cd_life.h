@@ -80,6 +80,9 @@ int cd_life2_pack(const DevProblem &P, double *Dpack, double *Spack, hipStream_t
 // the column build of every restart of a run of `life` ahead of the lifecycle launch (sets nothing in `life`: the caller sets
 // life->prebuilt, life->preslack [Rtotal]); X: the population [ceil(Rtotal / 16)][n16][16], start points in (generate = 0) and out
 int cd_life2_prep_launch(const DevProblem &P, const CdLife *life, double *X, int64_t Rtotal, int64_t num_iters, double tol, hipStream_t st);
+// Y0 = L^T x0 of restarts [0, count) of a prebuilt run (cd_life_y0_kernel), after cd_life2_prep_launch on the same stream: X the population,
+// Upack the factor's update fragments (cd_life2_pack_factor), Y0 [ceil(count / 16)][16 RB][16] (the caller sets life->y0_count, life->y0)
+int cd_life2_y0_launch(const double *X, const double *Upack, double *Y0, int NB, int RB, int64_t n16, int64_t count, hipStream_t st);
 int cd_life2_launch(const CdLife2Args &a, int nmw, int cs, int kind, int tiles, int wgs, hipStream_t st);
 const char *cd_life2_name(int nmw, int kind, int tiles, int lr);
 

@@ -1362,13 +1362,22 @@ __global__ __launch_bounds__((NMW == 3 && TILES == 1) ? 256 : 512, 2) void cd_li
             }
             if (LR) {
                 // ---- factored objective: a column that starts here (or an empty slot) has Y = 0 and no pending moves; the chain's
-                // loading sweep makes Y = L^T x0 of it
+                // loading sweep makes Y = L^T x0 of it.  A PRELOADED restart (index below CdLife::y0_count, cd_life_y0_kernel) starts in the
+                // state that sweep would leave: Y0 with the blocks up to NB - 3 applied, the "moves" of blocks NB - 2 and NB - 1 -- the
+                // points themselves, padded coordinates included: from the tile, not from the population -- pending
                 const int r16 = 16 * a0.RB;
+                const int y0n = lf_pre ? (int)lf->y0_count : 0;
+                GLB const double *y0g = glb(lf->y0);
                 for (int w = tid; w < NS * (32 + r16); w += NT) {
                     const int c = w % NS, ct = c >> 4, cc = c & 15, rowz = w / NS;
-                    if (l2_tl(snew, ct, TD)[cc] || l2_tl(sid, ct, TD)[cc] < 0) {
-                        if (rowz < 32) l2_tl(pend, ct, TD)[rowz * 16 + cc] = 0.0;
-                        else l2_tl(ytile, ct, TD)[(rowz - 32) * 16 + cc] = 0.0;
+                    const int id = l2_tl(sid, ct, TD)[cc];
+                    if (l2_tl(snew, ct, TD)[cc] || id < 0) {
+                        double v = 0.0;
+                        if (id >= 0 && id < y0n)
+                            v = rowz < 32 ? (Xg0 + (int64_t)ct * n16 * 16)[(16 * (int64_t)(NB - 2) + rowz) * 16 + cc]
+                                          : y0g[((int64_t)(id >> 4) * r16 + (rowz - 32)) * 16 + (id & 15)];
+                        if (rowz < 32) l2_tl(pend, ct, TD)[rowz * 16 + cc] = v;
+                        else l2_tl(ytile, ct, TD)[(rowz - 32) * 16 + cc] = v;
                     }
                 }
                 __syncthreads();
@@ -1390,9 +1399,15 @@ __global__ __launch_bounds__((NMW == 3 && TILES == 1) ? 256 : 512, 2) void cd_li
                 // the restart is not sweeping yet: gate not passed -> one frozen sweep (flag 1) that evaluates its objective;
                 // passed, linear kind -> a frozen sweep first (flag 4) that evaluates f0 at the start of phase 2
                 const int pass = l2_tl(gatep, rtile, TD)[r];
+                // (factored objective: the loading sweep first -- unless the refill preloaded the slot's Y, see there)
+                bool load = LR != 0;
+                if (LR) {
+                    GLB const CdLife *lf = glb(lifep);
+                    if (lf->prebuilt && l2_tl(sid, rtile, TD)[r] < (int)lf->y0_count) load = false;
+                }
                 cs_[6 * 64 + lane] = 0;
-                cs_[4 * 64 + lane] = (pass && !PRE && !LR) ? 0 : 1;
-                cs_[7 * 64 + lane] = (pass ? (PRE ? 4 : 0) : 1) | (LR ? 8 : 0);      // (factored objective: the loading sweep first)
+                cs_[4 * 64 + lane] = (pass && !PRE && !load) ? 0 : 1;
+                cs_[7 * 64 + lane] = (pass ? (PRE ? 4 : 0) : 1) | (load ? 8 : 0);
                 cs_[8 * 64 + lane] = 0;
             } else if (l2_tl(sid, rtile, TD)[r] < 0) {
                 cs_[4 * 64 + lane] = 1; cs_[6 * 64 + lane] = 0;
@@ -1609,6 +1624,83 @@ __global__ __launch_bounds__(L2P_NT) void cd_life_prep_kernel(DevProblem P, cons
     }
 }
 
+// ---- Y0 pre-pass (CdLife::y0_count, factored objective with prebuilt columns): Y0 = L[0 : 16 (NB - 2), :]^T X0[0 : 16 (NB - 2), :] for
+// the tiles of 16 restarts the prep kernel left in the population buffer -- what a restart's loading sweep builds inside the launch, one
+// slot-sweep in eleven at the headline, as a plain batched product at full occupancy.  Per column the bits of the loading sweep: the
+// accumulator of block beta starts at +0 and takes block b = 0 .. NB - 3, k-step v = 0 .. 3 in that order, with the Upack fragment as A
+// and the tile's rows 16 b + 4 v .. + 3 as B, exactly as l2_mfma_lr_role applies the moves of a loading column (MFMA columns are
+// independent).  Blocks NB - 2 and NB - 1 are NOT part of Y: they are the pending moves the refill takes from its own tile.
+// A wave keeps L2Y_BW blocks of Y x L2Y_TW tiles = 16 independent chains in its accumulators, so a pass over its fragments serves four
+// tiles and a fragment / a tile row is loaded once per 4 matrix instructions; the four waves of a workgroup are consecutive
+// (tile group, block group) pairs -- at RB = 16 the four block groups of one tile group.  Waves beyond the last block of Y / the last tile
+// compute on clamped addresses and store nothing; lanes of restarts beyond the run compute on whatever the tile holds.
+constexpr int L2Y_NT = 256, L2Y_BW = 4, L2Y_TW = 4;
+__global__ __launch_bounds__(L2Y_NT, 2) void cd_life_y0_kernel(const double *__restrict__ X, const double *__restrict__ Upack, double *__restrict__ Y0,
+                                                               int NB, int RB, int ntiles, int64_t n16) {
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int nbg = (RB + L2Y_BW - 1) / L2Y_BW;
+    const int64_t gw = (int64_t)blockIdx.x * (L2Y_NT / 64) + wave;
+    const int beta0 = (int)(gw % nbg) * L2Y_BW;
+    const int64_t t0 = gw / nbg * L2Y_TW;
+    if (t0 >= ntiles) return;
+    GLB const v2d_ *ua[L2Y_BW];
+    GLB const double *xt[L2Y_TW];
+#pragma unroll
+    for (int u = 0; u < L2Y_BW; u++) ua[u] = (GLB const v2d_ *)glb(Upack) + (int64_t)(beta0 + u < RB ? beta0 + u : RB - 1) * 128 + lane;
+#pragma unroll
+    for (int k = 0; k < L2Y_TW; k++) xt[k] = glb(X) + (t0 + k < ntiles ? t0 + k : (int64_t)ntiles - 1) * n16 * 16 + lane;
+    v4d_ y[L2Y_BW][L2Y_TW];
+#pragma unroll
+    for (int u = 0; u < L2Y_BW; u++)
+#pragma unroll
+        for (int k = 0; k < L2Y_TW; k++) y[u][k] = v4d_{0.0, 0.0, 0.0, 0.0};
+    const int nblk = NB - 2;
+    v2d_ a[L2Y_BW][2];
+    double x[L2Y_TW][4];
+#pragma unroll
+    for (int u = 0; u < L2Y_BW; u++) { a[u][0] = ua[u][0]; a[u][1] = ua[u][64]; }
+#pragma unroll
+    for (int k = 0; k < L2Y_TW; k++)
+#pragma unroll
+        for (int v = 0; v < 4; v++) x[k][v] = xt[k][v * 64];
+    for (int b = 0; b < nblk; b++) {
+        // the operands of the next block are requested before this block's 64 matrix instructions (the last block: its own again)
+        const int bn = b + 1 < nblk ? b + 1 : b;
+        v2d_ an[L2Y_BW][2];
+        double xn[L2Y_TW][4];
+#pragma unroll
+        for (int u = 0; u < L2Y_BW; u++) { an[u][0] = ua[u][(int64_t)bn * RB * 128]; an[u][1] = ua[u][(int64_t)bn * RB * 128 + 64]; }
+#pragma unroll
+        for (int k = 0; k < L2Y_TW; k++)
+#pragma unroll
+            for (int v = 0; v < 4; v++) xn[k][v] = xt[k][(int64_t)bn * 256 + v * 64];
+#pragma unroll
+        for (int v = 0; v < 4; v++)
+#pragma unroll
+            for (int u = 0; u < L2Y_BW; u++)
+#pragma unroll
+                for (int k = 0; k < L2Y_TW; k++) y[u][k] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[u][v >> 1][v & 1], x[k][v], y[u][k], 0, 0, 0);
+#pragma unroll
+        for (int u = 0; u < L2Y_BW; u++) { a[u][0] = an[u][0]; a[u][1] = an[u][1]; }
+#pragma unroll
+        for (int k = 0; k < L2Y_TW; k++)
+#pragma unroll
+            for (int v = 0; v < 4; v++) x[k][v] = xn[k][v];
+    }
+    // [tile][16 RB][16]: element v of lane l is row 16 beta + 4 v + (l >> 4), column l & 15 -- a 128-byte row per 16 lanes
+    const int64_t r16 = 16 * (int64_t)RB;
+#pragma unroll
+    for (int u = 0; u < L2Y_BW; u++)
+#pragma unroll
+        for (int k = 0; k < L2Y_TW; k++)
+            if (beta0 + u < RB && t0 + k < ntiles) {      // wave-uniform
+                GLB double *dst = glb(Y0) + ((t0 + k) * r16 + 16 * (beta0 + u)) * 16 + lane;
+#pragma unroll
+                for (int v = 0; v < 4; v++) dst[v * 64] = y[u][k][v];
+            }
+}
+
 // strictly upper triangle of the diagonal blocks (zeros elsewhere) and the per-block scalars the chain stages
 // (rcp2d is 1 / (2 P0[i,i]) wherever P0[i,i] != 0, negative entries included, and 0 where it is 0: the mixed-sign kind reads
 //  1 / P0[i,i] only where it is positive and P0[i,i] itself elsewhere)
@@ -1675,6 +1767,15 @@ int cd_life2_pack_factor(const double *Lrow, double *Gpack, double *Upack, int N
 
 int cd_life2_prep_launch(const DevProblem &P, const CdLife *life, double *X, int64_t Rtotal, int64_t num_iters, double tol, hipStream_t st) {
     hipLaunchKernelGGL(cd_life_prep_kernel, dim3((unsigned)((Rtotal + 15) / 16)), dim3(L2P_NT), 0, st, P, life, X, num_iters, tol);
+    return (int)hipGetLastError();
+}
+
+int cd_life2_y0_launch(const double *X, const double *Upack, double *Y0, int NB, int RB, int64_t n16, int64_t count, hipStream_t st) {
+    if (count < 1) return (int)hipSuccess;
+    if (NB < 3 || RB < 1) return (int)hipErrorInvalidValue;
+    const int64_t ntiles = (count + 15) / 16;
+    const int64_t waves = (ntiles + L2Y_TW - 1) / L2Y_TW * ((RB + L2Y_BW - 1) / L2Y_BW);
+    hipLaunchKernelGGL(cd_life_y0_kernel, dim3((unsigned)((waves + L2Y_NT / 64 - 1) / (L2Y_NT / 64))), dim3(L2Y_NT), 0, st, X, Upack, Y0, NB, RB, (int)ntiles, n16);
     return (int)hipGetLastError();
 }
 

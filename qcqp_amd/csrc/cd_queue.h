@@ -47,6 +47,10 @@ struct CdLife {
     // phase 1, sweeps1 / status1 / ran2 its phase-1 sweeps, status and gate, preslack [Rtotal] its slack; the refill copies them
     int prebuilt;
     const double *preslack;
+    // factored cd_life_kernel with prebuilt columns: restarts [0, y0_count) of the run come with Y0 = L^T x0 (cd_life2_y0_launch) in
+    // y0 [ceil(y0_count / 16)][16 RB][16] -- the refill copies the column and the restart skips its loading sweep; the others load in-kernel
+    int64_t y0_count;
+    const double *y0;
 };
 
 struct CdQueueArgs {
