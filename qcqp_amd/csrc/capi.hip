@@ -27,6 +27,7 @@
 #include "cd_general.h"
 #include "cd_dense.h"
 #include "sdr_solve.h"
+#include "dev_buf.h"
 
 using namespace qcqpmi;
 
@@ -91,17 +92,8 @@ RcclApi *rccl() {
 
 }  // namespace
 
-// Busy-wait for the stream.  hipStreamSynchronize and the implicit wait of a pageable copy go to sleep in slices once a kernel
-// has run for a few milliseconds and wake up 10-30 ms late in about one call of four on this stack (measured round 6 with the 34 ms
-// lifecycle launch: tools/timed_region_probe.py, profiles/r06_timed_region.md); the long launches of the coordinate-descent paths
-// are therefore awaited by polling hipStreamQuery -- one host core spins for the length of the launch.
-hipError_t spin_sync(hipStream_t st) {
-    for (;;) {
-        const hipError_t e = hipStreamQuery(st);
-        if (e != hipErrorNotReady) return e;
-    }
-}
-
+// Every device or pinned pointer the context OWNS is a DevBuf / PinBuf (dev_buf.h): freed when the context is deleted, grown with
+// reserve().  Raw pointers below only view another allocation (dn_Gpack, dn_q, ..., dp.*: all of them in prob_allocs).
 struct qcqpmi_ctx {
     int device = 0;
     int64_t n = 0, n16 = 0, m = 0;
@@ -115,30 +107,29 @@ struct qcqpmi_ctx {
     int objclass = 0;  // 1: every P0[i,i] > 0, 2: every P0[i,i] == 0, 0: mixed (negative entries, or zero in places: cd_life_kernel's SGN kind)
     bool symcls = false;  // one constraint class of the form p x_i^2 + r == 0 (feasible sets mirrored about 0)
     DevProblem dp{};
-    std::vector<void *> prob_allocs;
-    // population
+    std::vector<DevBuf<char>> prob_allocs;   // the problem's arrays (dp.*, dn_*, d_gP): allocated at finalize, never grown
+    // population: the group below grows together (pop_reserve, Rcap restarts); Xi and d_F are sized on demand and dropped with it
     int64_t R = 0, Rpad = 0, Rcap = 0;
-    double *X = nullptr, *Xi = nullptr;
-    double *d_f0 = nullptr, *d_mv = nullptr, *d_F = nullptr;
-    int64_t *d_visits = nullptr, *d_acc = nullptr, *d_sweeps = nullptr, *d_sweeps1 = nullptr;
-    int *d_status = nullptr, *d_status1 = nullptr;
-    uint8_t *d_flag = nullptr;
-    int64_t *d_best_idx = nullptr;
-    double *d_best_key = nullptr;
-    double *d_stage = nullptr;  // host-layout staging (n x Rcap)
-    int64_t F_cap = 0;
+    DevBuf<double> X, Xi;        // Xi: the standard normals of pop_sdr_sample
+    DevBuf<double> d_f0, d_mv, d_F;
+    DevBuf<int64_t> d_visits, d_acc, d_sweeps, d_sweeps1;
+    DevBuf<int> d_status, d_status1;
+    DevBuf<uint8_t> d_flag;
+    DevBuf<int64_t> d_best_idx;
+    DevBuf<double> d_best_key;
+    DevBuf<double> d_stage;  // host-layout staging (n x Rcap)
     bool evaluated = false;
     // SDR factor
-    double *d_Fpack = nullptr, *d_Frow = nullptr, *d_mu = nullptr;
+    DevBuf<double> d_Fpack, d_Frow, d_mu;
     Timer timers[5];
     // ADMM: the stacked bases B = [B_1 ... B_m] packed for the two products (gemm_pk.h), eigenvalues, B^T q, brackets
     // unit bases (every basis vector is +-e_i: separable constraints): ZQ = W^T Z is a gather, S = W D a scatter (no GEMM)
-    int *ad_uidx = nullptr, *ad_uptr = nullptr, *ad_ulist = nullptr;       // [Mh16] coordinate of basis row h (-1: padding); CSR coordinate -> rows
-    double *ad_usgn = nullptr;                                             // [Mh16] its sign
+    DevBuf<int> ad_uidx, ad_uptr, ad_ulist;                                // [Mh16] coordinate of basis row h (-1: padding); CSR coordinate -> rows
+    DevBuf<double> ad_usgn;                                                // [Mh16] its sign
     bool ad_unit = false, ad_unit_off = false;
-    double *ad_WTpk = nullptr, *ad_Wpk = nullptr, *ad_lam = nullptr, *ad_qhat = nullptr, *ad_rk = nullptr, *ad_slo = nullptr, *ad_ehi = nullptr;
-    double *ad_Minvpk = nullptr;
-    int *ad_relop = nullptr;
+    DevBuf<double> ad_WTpk, ad_Wpk, ad_lam, ad_qhat, ad_rk, ad_slo, ad_ehi;
+    DevBuf<double> ad_Minvpk;
+    DevBuf<int> ad_relop;
     int64_t ad_rows = 0, ad_Mh16 = 0;   // hat rows per constraint (n, or rp of a reduced basis); m * rows padded to 16
     int ad_lowrank = 0;
     bool ad_qzero = false;              // every B_k^T q_k is zero
@@ -146,41 +137,35 @@ struct qcqpmi_ctx {
     bool p0_diag = false;               // P0 has no off-diagonal entries (z-update and f0 need no product then)
     std::vector<double> p0_diag_host;
     // outputs of a run packed into one device buffer, copied with ONE transfer into pinned host memory
-    char *d_out = nullptr, *h_out = nullptr;
-    char *h_pin = nullptr;                // pinned bounce buffer of the relaxation solver's downloads (pin_reserve)
-    size_t h_pin_cap = 0;
-    int64_t out_cap = 0;
+    DevBuf<char> d_out;
+    PinBuf<char> h_out;
+    PinBuf<char> h_pin;                   // pinned bounce buffer of the relaxation solver's downloads
     int eval_zs = 1;   // planes of the last dense evaluation
-    double *d_wS = nullptr, *d_wY = nullptr, *d_ww = nullptr, *d_wz = nullptr;   // qcqpmi_pop_weighted_product work buffers
-    int64_t wY_cap = 0;
-    double *d_planes = nullptr;   // partial planes of x'P0x from the GEMM evaluation
-    int64_t planes_cap = 0;
-    double *d_gP = nullptr;   // dense constraint matrices [m][n][n] (problems whose constraints couple coordinates)
+    DevBuf<double> d_wS, d_wY, d_ww, d_wz;   // qcqpmi_pop_weighted_product work buffers
+    DevBuf<double> d_planes;   // partial planes of x'P0x from the GEMM evaluation
+    double *d_gP = nullptr;   // dense constraint matrices [m][n][n] (problems whose constraints couple coordinates): in prob_allocs
     // dense-constraint path (cd_dense.h): all matrices in block-major fragment order + work buffers
     const double *dn_Gpack = nullptr, *dn_q = nullptr, *dn_qT = nullptr, *dn_r = nullptr;
     const int *dn_relop = nullptr;
-    double *dn_G = nullptr, *dn_Dg = nullptr, *dn_Ft = nullptr;
+    DevBuf<double> dn_G, dn_Dg, dn_Ft;    // dn_Ft grows with dn_G
     int dense_chain_mode = 0;             // 0: four waves per restart where it applies, 1: one wave per restart (cross-check)
-    long long *dn_prof = nullptr;         // 32 tick sums of the dense chain kernel (debug profile)
-    int64_t dn_G_cap = 0, dn_state_cap = 0;
-    void *dn_state = nullptr;
+    DevBuf<long long> dn_prof;            // 32 tick sums of the dense chain kernel (debug profile)
+    DevBuf<char> dn_state;                // per-restart state of a dense phase (dense_state lays it out for Rpad restarts)
     hipStream_t stream2 = nullptr;   // second stream of the dense path: products of block b+1 while the chain walks b
     hipEvent_t dn_ev[3] = {nullptr, nullptr, nullptr};
     hipEvent_t dn_evn[2] = {nullptr, nullptr};   // "live count of sweep t copied" (dense path: the host runs one sweep ahead)
-    int *dn_hn = nullptr;                        // pinned: the two live counts in flight
+    PinBuf<int> dn_hn;                           // pinned: the two live counts in flight
     bool dn_force = false;    // generated functions: the dense path is the only one that holds them
     // streaming upload (coupled constraints beyond `stream_limit` bytes of row-major storage): every function is packed for the
     // matrix cores as it arrives; neither the host nor the device ever holds a second copy
     double stream_limit = 16e9;
-    double *dn_gp_pre = nullptr, *dn_tmp = nullptr;
+    DevBuf<double> dn_gp_pre, dn_tmp;     // the packed matrices until finalize takes them over; the row-major staging of one function
     // comm
     ncclComm_t comm = nullptr;
     int rank = 0, world = 1;
-    double *d_comm = nullptr, *d_comm_big = nullptr;
-    size_t comm_big_cap = 0;     // bytes
-    long long *d_prof = nullptr;
+    DevBuf<double> d_comm, d_comm_big;
+    DevBuf<long long> d_prof;
     int cd_stage = 0;                   // qcqpmi_cd_run_stage: last stage completed of a split run
-    int64_t Xi_cap = 0;                 // doubles reserved for the standard normals of pop_sdr_sample
     bool sdr_factor_resident = false;   // d_Fpack / d_mu hold the pair of the last pop_sdr_sample
     double ad_Minv_rho = 0.0;           // rho of the z-solver matrix formed by qcqpmi_admm_zsolver_device
     bool ad_Minv_device = false;
@@ -188,8 +173,7 @@ struct qcqpmi_ctx {
     bool profile = false;
     int dbg = 0;
     // fused persistent ADMM kernel (admm_fused.h): one work buffer kept across runs, grown on demand
-    char *af_work = nullptr;
-    size_t af_work_cap = 0;
+    DevBuf<char> af_work;
     bool ad_fused = true;                 // qcqpmi_admm_fused: use the fused kernel where it applies
     int ad_fused_nt = 512;                // threads per workgroup of the fused kernel (256: qcqpmi_admm_fused(ctx, 2))
     const char *last_admm_kernel = "";    // "admm_fused_kernel" / "admm_multi_launch"
@@ -197,40 +181,38 @@ struct qcqpmi_ctx {
     long long af_prof[16] = {0};          // stage cycle counters of the last fused run (when qcqpmi_debug_profile enabled them)
     int cd_queue = 2;                     // qcqpmi_cd_queue: 0 off, 1 restart-level scheduling (cd_phase2_qs_kernel) wherever it applies,
                                           // 2 auto: when there are more tiles than CUs
-    int *d_qnext = nullptr;               // [0] queue head of the slot-queue kernel
+    DevBuf<int> d_qnext;                  // [0] queue head of the slot-queue kernel
     bool q_prepared = false;              // the queue of the resident population has been reset
-    CdLife *d_life = nullptr;    // qcqpmi_cd_stream_run: parameters of the lifecycle launch
+    DevBuf<CdLife> d_life;       // qcqpmi_cd_stream_run: parameters of the lifecycle launch
     // second-generation lifecycle kernel (cd_life.h): the workgroups' X tiles, the staged diagonal blocks, the watchdog word
     int Kreal = 0;               // constraint classes among the REAL coordinates (the padded ones of n16 carry no constraint)
     double fbound = 0.0;         // sum |P0| + sum |q0| + |r0|
-    double *l2_scratch = nullptr; size_t l2_scratch_cap = 0;
-    double *l2_D = nullptr, *l2_S = nullptr;
-    int *l2_abort = nullptr;
-    int *l2_cuslot = nullptr;    // [4096] arrival counters per compute unit of cd_life_kernel (zeroed before every launch)
-    double *l2_preslack = nullptr; int64_t l2_preslack_cap = 0;    // [K R] slack of the prebuilt columns (cd_life2_prep_launch)
-    double *l2_y0 = nullptr; size_t l2_y0_cap = 0;                 // [tile][16 lr_RB][16] Y0 = L^T x0 of the preloaded restarts (cd_life2_y0_launch)
+    DevBuf<double> l2_scratch;
+    DevBuf<double> l2_D, l2_S;
+    DevBuf<int> l2_abort;
+    DevBuf<int> l2_cuslot;       // [4096] arrival counters per compute unit of cd_life_kernel (zeroed before every launch)
+    DevBuf<double> l2_preslack;  // [K R] slack of the prebuilt columns (cd_life2_prep_launch)
+    DevBuf<double> l2_y0;        // [tile][16 lr_RB][16] Y0 = L^T x0 of the preloaded restarts (cd_life2_y0_launch)
     // factored objective P0 = L L^T (qcqpmi_cd_set_objective_factor): L (n16 x 16 lr_RB, zero-padded) and its fragment packs
-    double *lr_L = nullptr, *lr_G = nullptr, *lr_U = nullptr; int lr_RB = 0;
+    DevBuf<double> lr_L, lr_G, lr_U; int lr_RB = 0;
     int life_version = 0;        // qcqpmi_cd_life_version: 0 = the faster one for the shape, 2 = cd_life_kernel wherever it applies, 1 = cd_phase2_qs_kernel<lifecycle> only
-    long long *d_life_prof = nullptr;
-    int64_t *d_bestK_idx = nullptr; double *d_bestK_key = nullptr, *d_bestK_x = nullptr; int64_t bestK_cap = 0;
+    DevBuf<long long> d_life_prof;
+    DevBuf<int64_t> d_bestK_idx; DevBuf<double> d_bestK_key, d_bestK_x;
     bool cd_ref_order = false;   // qcqpmi_cd_reference_order: coupled constraints in the reference's summation order
     bool force_generic = false;  // debug/tests: run the general phase-2 kernel even when the pipelined one applies
     std::vector<int> last_st1, last_st2;   // per-restart status codes of the last coordinate-descent run (qcqpmi_cd_status)
     // capi_small.inc, the CD and ADMM batch calls: ONE device buffer for the objectives, starts, per-restart outputs, points and winners
     // of a call (grown on demand; the resident population and its buffers are never used by that call)
-    char *sb_work = nullptr;
-    size_t sb_work_cap = 0;
+    DevBuf<char> sb_work;
     // qcqpmi_sdr_small_batch: d (n) when every coordinate carries exactly one constraint p x_i^2 + r == 0 with d_i = -r / p > 0 (the
     // unit-diagonal family of the relaxation), else empty; and the call's own device buffer, like sb_work
     std::vector<double> unit_d;
-    char *ss_work = nullptr;
-    size_t ss_work_cap = 0;
+    DevBuf<char> ss_work;
 };
 
 namespace {
 
-void admm_free(qcqpmi_ctx *c, bool keep_zsolver);
+void admm_drop_handle(qcqpmi_ctx *c);      // capi_admm.inc: the rocBLAS handle of qcqpmi_admm_setup
 
 int fail(qcqpmi_ctx *c, int code, const char *fmt, ...) {
     char buf[1024];
@@ -250,21 +232,21 @@ int fail(qcqpmi_ctx *c, int code, const char *fmt, ...) {
                         __FILE__, __LINE__);                                                  \
     } while (0)
 
+// `count` elements of the problem's own storage: owned by prob_allocs until the context goes
 template <typename T>
-int dev_alloc(qcqpmi_ctx *c, T **p, size_t count, bool zero = true) {
-    void *v = nullptr;
-    HIPCHK(c, hipMalloc(&v, std::max<size_t>(count, 1) * sizeof(T)));
-    if (zero) HIPCHK(c, hipMemsetAsync(v, 0, std::max<size_t>(count, 1) * sizeof(T), c->stream));
-    *p = (T *)v;
+int prob_alloc(qcqpmi_ctx *c, T **dst, size_t count) {
+    DevBuf<char> b;
+    HIPCHK(c, b.reserve(c->stream, std::max<size_t>(count, 1) * sizeof(T), false));
+    *dst = (T *)b.p;
+    c->prob_allocs.push_back(std::move(b));
     return 0;
 }
 
 template <typename T>
 int prob_upload(qcqpmi_ctx *c, const T **dst, const std::vector<T> &src) {
     T *p = nullptr;
-    int rc = dev_alloc(c, &p, src.size(), false);
+    int rc = prob_alloc(c, &p, src.size());
     if (rc) return rc;
-    c->prob_allocs.push_back(p);
     if (!src.empty())
         HIPCHK(c, hipMemcpyAsync(p, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice, c->stream));
     *dst = p;
@@ -272,13 +254,10 @@ int prob_upload(qcqpmi_ctx *c, const T **dst, const std::vector<T> &src) {
 }
 
 void free_population(qcqpmi_ctx *c) {
-    void *ptrs[] = {c->X, c->Xi, c->d_f0, c->d_mv, c->d_F, c->d_visits, c->d_acc, c->d_sweeps,
-                    c->d_sweeps1, c->d_status, c->d_status1, c->d_flag, c->d_stage};
-    for (void *p : ptrs) if (p) (void)hipFree(p);
-    c->X = c->Xi = c->d_f0 = c->d_mv = c->d_F = c->d_stage = nullptr;
-    c->d_visits = c->d_acc = c->d_sweeps = c->d_sweeps1 = nullptr;
-    c->d_status = nullptr; c->d_status1 = nullptr; c->d_flag = nullptr;
-    c->Rcap = 0; c->F_cap = 0;
+    c->X.release(); c->Xi.release(); c->d_f0.release(); c->d_mv.release(); c->d_F.release(); c->d_stage.release();
+    c->d_visits.release(); c->d_acc.release(); c->d_sweeps.release(); c->d_sweeps1.release();
+    c->d_status.release(); c->d_status1.release(); c->d_flag.release();
+    c->Rcap = 0;
 }
 
 int pop_reserve(qcqpmi_ctx *c, int64_t R) {
@@ -287,19 +266,18 @@ int pop_reserve(qcqpmi_ctx *c, int64_t R) {
     if (Rpad > c->Rcap) {
         HIPCHK(c, spin_sync(c->stream));
         free_population(c);
-        int rc = 0;
-        size_t xe = (size_t)Rpad * (size_t)c->n16;
-        if ((rc = dev_alloc(c, &c->X, xe))) return rc;
-        if ((rc = dev_alloc(c, &c->d_stage, (size_t)Rpad * (size_t)c->n))) return rc;
-        if ((rc = dev_alloc(c, &c->d_f0, Rpad))) return rc;
-        if ((rc = dev_alloc(c, &c->d_mv, Rpad))) return rc;
-        if ((rc = dev_alloc(c, &c->d_visits, Rpad))) return rc;
-        if ((rc = dev_alloc(c, &c->d_acc, Rpad))) return rc;
-        if ((rc = dev_alloc(c, &c->d_sweeps, Rpad))) return rc;
-        if ((rc = dev_alloc(c, &c->d_sweeps1, Rpad))) return rc;
-        if ((rc = dev_alloc(c, &c->d_status, Rpad))) return rc;
-        if ((rc = dev_alloc(c, &c->d_status1, Rpad))) return rc;
-        if ((rc = dev_alloc(c, &c->d_flag, Rpad))) return rc;
+        const size_t Rp = (size_t)Rpad;
+        HIPCHK(c, c->X.reserve(c->stream, Rp * (size_t)c->n16));
+        HIPCHK(c, c->d_stage.reserve(c->stream, Rp * (size_t)c->n));
+        HIPCHK(c, c->d_f0.reserve(c->stream, Rp));
+        HIPCHK(c, c->d_mv.reserve(c->stream, Rp));
+        HIPCHK(c, c->d_visits.reserve(c->stream, Rp));
+        HIPCHK(c, c->d_acc.reserve(c->stream, Rp));
+        HIPCHK(c, c->d_sweeps.reserve(c->stream, Rp));
+        HIPCHK(c, c->d_sweeps1.reserve(c->stream, Rp));
+        HIPCHK(c, c->d_status.reserve(c->stream, Rp));
+        HIPCHK(c, c->d_status1.reserve(c->stream, Rp));
+        HIPCHK(c, c->d_flag.reserve(c->stream, Rp));
         c->Rcap = Rpad;
     }
     c->R = R;
@@ -337,42 +315,22 @@ __global__ void pack_cd_outputs_kernel(char *out, int64_t R, const int64_t *s1, 
 // pinned host memory for downloads that are repeated thousands of times (a 2-D copy into pageable memory is staged row by
 // row by the runtime: 1025 rows of 47 doubles cost 15 ms)
 int pin_reserve(qcqpmi_ctx *c, size_t bytes) {
-    if (bytes <= c->h_pin_cap) return 0;
-    HIPCHK(c, spin_sync(c->stream));
-    if (c->h_pin) (void)hipHostFree(c->h_pin);
-    c->h_pin = nullptr; c->h_pin_cap = 0;
-    HIPCHK(c, hipHostMalloc((void **)&c->h_pin, bytes, hipHostMallocDefault));
-    c->h_pin_cap = bytes;
+    HIPCHK(c, c->h_pin.reserve(c->stream, bytes, false));
     return 0;
 }
 
 // staging buffers (device + pinned host) of fetch_cd_outputs for R restarts
 int cd_outputs_reserve(qcqpmi_ctx *c, int64_t R) {
-    const int64_t bytes = 57 * R;
-    if (bytes > c->out_cap) {
-        HIPCHK(c, spin_sync(c->stream));
-        if (c->d_out) (void)hipFree(c->d_out);
-        if (c->h_out) (void)hipHostFree(c->h_out);
-        c->d_out = c->h_out = nullptr;
-        HIPCHK(c, hipMalloc((void **)&c->d_out, (size_t)bytes));
-        HIPCHK(c, hipHostMalloc((void **)&c->h_out, (size_t)bytes, hipHostMallocDefault));
-        c->out_cap = bytes;
-    }
+    HIPCHK(c, c->d_out.reserve(c->stream, (size_t)(57 * R), false));
+    HIPCHK(c, c->h_out.reserve(c->stream, (size_t)(57 * R), false));
     return 0;
 }
 
 // device buffers of the per-population winners of a streamed run (K populations)
 int cd_bestK_reserve(qcqpmi_ctx *c, int64_t K) {
-    if (K > c->bestK_cap) {
-        if (c->d_bestK_idx) (void)hipFree(c->d_bestK_idx);
-        if (c->d_bestK_key) (void)hipFree(c->d_bestK_key);
-        if (c->d_bestK_x) (void)hipFree(c->d_bestK_x);
-        c->d_bestK_idx = nullptr; c->d_bestK_key = nullptr; c->d_bestK_x = nullptr;
-        HIPCHK(c, hipMalloc((void **)&c->d_bestK_idx, (size_t)K * 2 * sizeof(int64_t)));
-        HIPCHK(c, hipMalloc((void **)&c->d_bestK_key, (size_t)K * 2 * sizeof(double)));
-        HIPCHK(c, hipMalloc((void **)&c->d_bestK_x, (size_t)K * c->n * sizeof(double)));
-        c->bestK_cap = K;
-    }
+    HIPCHK(c, c->d_bestK_idx.reserve(c->stream, (size_t)K * 2, false));
+    HIPCHK(c, c->d_bestK_key.reserve(c->stream, (size_t)K * 2, false));
+    HIPCHK(c, c->d_bestK_x.reserve(c->stream, (size_t)K * c->n, false));
     return 0;
 }
 
@@ -438,15 +396,7 @@ int cd_apply_status(qcqpmi_ctx *c, const std::vector<int> &st, const std::vector
 
 int launch_eval(qcqpmi_ctx *c, bool want_F) {
     if (dense_on(c)) return launch_eval_dense(c, false);   // coupled constraints: every function on the matrix cores
-    if (want_F) {
-        int64_t need = (c->m + 1) * c->Rpad;
-        if (need > c->F_cap) {
-            if (c->d_F) { HIPCHK(c, spin_sync(c->stream)); (void)hipFree(c->d_F); c->d_F = nullptr; }
-            int rc = dev_alloc(c, &c->d_F, need);
-            if (rc) return rc;
-            c->F_cap = need;
-        }
-    }
+    if (want_F) HIPCHK(c, c->d_F.reserve(c->stream, (size_t)((c->m + 1) * c->Rpad)));
     EvalArgs a;
     a.P = c->dp; a.X = c->X; a.R = c->R; a.f0 = c->d_f0; a.maxviol = c->d_mv;
     a.F = want_F ? c->d_F : nullptr; a.Rpad = c->Rpad;
@@ -457,12 +407,7 @@ int launch_eval(qcqpmi_ctx *c, bool want_F) {
         // x'P0x through the LDS-tiled GEMM: 8 row blocks x 8 tiles per workgroup share their operands
         // (the per-tile MFMA loop of eval_kernel re-reads all of P0 from L2 for every tile)
         const int groups = (NB + DP_FG - 1) / DP_FG, nplanes = 2 * groups;
-        if ((int64_t)nplanes * c->Rpad > c->planes_cap) {
-            if (c->d_planes) { HIPCHK(c, spin_sync(c->stream)); (void)hipFree(c->d_planes); c->d_planes = nullptr; }
-            int rc = dev_alloc(c, &c->d_planes, (size_t)nplanes * c->Rpad);
-            if (rc) return rc;
-            c->planes_cap = (int64_t)nplanes * c->Rpad;
-        }
+        HIPCHK(c, c->d_planes.reserve(c->stream, (size_t)nplanes * c->Rpad));
         DenseProdArgs pa;
         pa.D.Gpack = c->dp.Apack; pa.D.q = nullptr; pa.D.qT = nullptr; pa.D.r = nullptr; pa.D.relop = nullptr;
         pa.D.n = c->n; pa.D.n16 = c->n16; pa.D.NB = NB; pa.D.KS = (int)(c->n16 / 4); pa.D.m1 = 1; pa.D.m1p = 64;
@@ -499,7 +444,7 @@ bool cd_queue_applies(qcqpmi_ctx *c, bool profiling) {
 // reset the queue of the resident population and the per-restart outputs the kernel only writes for the restarts it runs,
 // then publish the population (generation number) to whoever may pull from it
 int cd_queue_prepare(qcqpmi_ctx *c) {
-    if (!c->d_qnext) { int rcq = dev_alloc(c, &c->d_qnext, 16); if (rcq) return rcq; }
+    HIPCHK(c, c->d_qnext.reserve(c->stream, 16));
     HIPCHK(c, hipMemsetAsync(c->d_visits, 0, (size_t)c->Rpad * sizeof(int64_t), c->stream));
     HIPCHK(c, hipMemsetAsync(c->d_acc, 0, (size_t)c->Rpad * sizeof(int64_t), c->stream));
     HIPCHK(c, hipMemsetAsync(c->d_sweeps, 0, (size_t)c->Rpad * sizeof(int64_t), c->stream));
@@ -766,21 +711,13 @@ void qcqpmi_ctx_destroy(qcqpmi_ctx *c) {
     (void)hipSetDevice(c->device);
     if (c->stream) (void)spin_sync(c->stream);
     if (c->comm && rccl() && rccl()->CommDestroy) rccl()->CommDestroy(c->comm);
-    free_population(c);
-    admm_free(c, false);
-    for (void *p : c->prob_allocs) (void)hipFree(p);
-    void *ptrs[] = {c->d_Fpack, c->d_Frow, c->d_mu, c->d_best_idx, c->d_best_key, c->d_comm, c->d_comm_big,   // d_gP is in prob_allocs
-                    c->dn_G, c->dn_Dg, c->dn_Ft, c->dn_prof, c->dn_state, c->d_planes, c->d_out, c->d_wS, c->d_wY, c->d_ww, c->d_wz, c->af_work, c->d_qnext, c->d_life, c->d_life_prof, c->d_bestK_idx, c->d_bestK_key, c->d_bestK_x, c->l2_scratch, c->l2_D, c->l2_S, c->l2_abort, c->l2_cuslot, c->l2_preslack, c->l2_y0, c->lr_L, c->lr_G, c->lr_U, c->sb_work, c->ss_work};
-    if (c->h_out) (void)hipHostFree(c->h_out);
-    if (c->h_pin) (void)hipHostFree(c->h_pin);
-    for (void *p : ptrs) if (p) (void)hipFree(p);
+    admm_drop_handle(c);
     for (auto &t : c->timers) { if (t.beg) (void)hipEventDestroy(t.beg); if (t.end) (void)hipEventDestroy(t.end); }
     for (auto &e : c->dn_ev) if (e) (void)hipEventDestroy(e);
     for (auto &e : c->dn_evn) if (e) (void)hipEventDestroy(e);
-    if (c->dn_hn) (void)hipHostFree(c->dn_hn);
     if (c->stream2) (void)hipStreamDestroy(c->stream2);
     if (c->stream) (void)hipStreamDestroy(c->stream);
-    delete c;
+    delete c;      // every buffer frees itself (the stream was idle above: nothing in flight reads one)
 }
 
 int qcqpmi_set_quad(qcqpmi_ctx *c, int64_t k, int format, const double *vals, const int64_t *idx,
@@ -858,9 +795,8 @@ int qcqpmi_set_quad(qcqpmi_ctx *c, int64_t k, int format, const double *vals, co
         if ((double)m1 * (double)n16 * (double)n16 * 8.0 > 200e9)
             return fail(c, QCQPMI_EUNSUPPORTED, "set_quad: %lld matrices of %lld x %lld exceed the 200 GB kept for packed matrices", (long long)m1, (long long)n, (long long)n);
         HIPCHK(c, hipSetDevice(c->device));
-        int rcs;
-        if (!c->dn_gp_pre && (rcs = dev_alloc(c, &c->dn_gp_pre, (size_t)m1 * n16 * n16, false))) return rcs;
-        if (!c->dn_tmp && (rcs = dev_alloc(c, &c->dn_tmp, (size_t)n * n, false))) return rcs;
+        HIPCHK(c, c->dn_gp_pre.reserve(c->stream, (size_t)m1 * n16 * n16, false));
+        HIPCHK(c, c->dn_tmp.reserve(c->stream, (size_t)n * n, false));
         std::vector<double> dense;
         const double *src = vals;
         if (format != QCQPMI_FMT_DENSE) {
@@ -896,14 +832,12 @@ int qcqpmi_set_quad_generated(qcqpmi_ctx *c, int64_t k, uint64_t seed, double sc
     h.r = r; h.relop = relop; h.set = true;
     // the linear term comes back to the host (n values): the generic finalize code reads it there
     HIPCHK(c, hipSetDevice(c->device));
-    double *dq = nullptr;
-    HIPCHK(c, hipMalloc((void **)&dq, (size_t)c->n * sizeof(double)));
-    hipLaunchKernelGGL(dense_gen_q_kernel, dim3((unsigned)((c->n + 255) / 256)), dim3(256), 0, c->stream, dq, c->n, (int)k, seed, qscale);
+    DevBuf<double> dq;
+    HIPCHK(c, dq.reserve(c->stream, (size_t)c->n, false));
+    hipLaunchKernelGGL(dense_gen_q_kernel, dim3((unsigned)((c->n + 255) / 256)), dim3(256), 0, c->stream, dq.p, c->n, (int)k, seed, qscale);
     h.q.resize((size_t)c->n);
-    hipError_t e = hipMemcpyAsync(h.q.data(), dq, (size_t)c->n * sizeof(double), hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = spin_sync(c->stream);
-    (void)hipFree(dq);
-    if (e != hipSuccess) return fail(c, QCQPMI_EHIP, "set_quad_generated: %s", hipGetErrorString(e));
+    HIPCHK(c, hipMemcpyAsync(h.q.data(), dq.p, (size_t)c->n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, spin_sync(c->stream));
     return 0;
 }
 
@@ -924,14 +858,12 @@ int qcqpmi_finalize(qcqpmi_ctx *c) {
         for (int64_t j = 0; j < n; j++) q[j] = h.q[j];
         int rc;
         if (h.gen) {   // generated on the device, mirrored to the host for the diagonal classification below
-            double *tmp = nullptr;
-            if ((rc = dev_alloc(c, &tmp, (size_t)n16 * n16, false))) return rc;
+            DevBuf<double> tmp;
+            HIPCHK(c, tmp.reserve(c->stream, (size_t)n16 * n16, false));
             hipLaunchKernelGGL(dense_gen_rowmajor_kernel, dim3((unsigned)((n16 * n16 + 255) / 256)), dim3(256), 0, c->stream,
-                               tmp, n, n16, 0, h.gseed, h.gscale, h.gdiag);
-            hipError_t e = hipMemcpyAsync(P.data(), tmp, P.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream);
-            if (e == hipSuccess) e = spin_sync(c->stream);
-            (void)hipFree(tmp);
-            if (e != hipSuccess) return fail(c, QCQPMI_EHIP, "finalize: generated objective: %s", hipGetErrorString(e));
+                               tmp.p, n, n16, 0, h.gseed, h.gscale, h.gdiag);
+            HIPCHK(c, hipMemcpyAsync(P.data(), tmp.p, P.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(c, spin_sync(c->stream));
         }
         {
             bool dg = true;
@@ -964,15 +896,13 @@ int qcqpmi_finalize(qcqpmi_ctx *c) {
             c->fbound = fb;
         }
         double *ap = nullptr;
-        if ((rc = dev_alloc(c, &ap, (size_t)n16 * n16, false))) return rc;
-        c->prob_allocs.push_back(ap);
+        if ((rc = prob_alloc(c, &ap, (size_t)n16 * n16))) return rc;
         int64_t total = n16 * n16;
         hipLaunchKernelGGL(pack_A_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, c->stream,
                            dp.P0, ap, n16, dp.KS);
         HIPCHK(c, hipGetLastError());
         double *ap2 = nullptr;
-        if ((rc = dev_alloc(c, &ap2, (size_t)n16 * n16, false))) return rc;
-        c->prob_allocs.push_back(ap2);
+        if ((rc = prob_alloc(c, &ap2, (size_t)n16 * n16))) return rc;
         hipLaunchKernelGGL(pack_A2_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, c->stream,
                            dp.P0, ap2, n16, dp.KS);
         HIPCHK(c, hipGetLastError());
@@ -1117,8 +1047,8 @@ int qcqpmi_finalize(qcqpmi_ctx *c) {
         if ((c->d_gP || all_gen || any_streamed) && (double)(m + 1) * (double)n16 * (double)n16 * 8.0 <= 200e9 && (rc = dense_build(c, gq, gr, grel))) return rc;
         if (c->dn_force && !c->dn_Gpack) return fail(c, QCQPMI_EUNSUPPORTED, "generated functions need the dense path (matrices exceed 200 GB, or generated and uploaded coupled constraints are mixed beyond 16 GB)");
     }
-    if ((rc = dev_alloc(c, &c->d_best_idx, 2))) return rc;
-    if ((rc = dev_alloc(c, &c->d_best_key, 2))) return rc;
+    HIPCHK(c, c->d_best_idx.reserve(c->stream, 2));
+    HIPCHK(c, c->d_best_key.reserve(c->stream, 2));
     HIPCHK(c, spin_sync(c->stream));
     // host copies are no longer needed
     for (auto &h : c->quads) { std::vector<int>().swap(h.ci); std::vector<int>().swap(h.cj); std::vector<double>().swap(h.cv); }
@@ -1133,37 +1063,33 @@ int qcqpmi_sdr_solve_unitdiag(qcqpmi_ctx *c, const double *C, int64_t N, double 
         return fail(c, QCQPMI_EINVAL, "sdr_solve_unitdiag: bad arguments");
     if (N > SDR_NMAX) return fail(c, QCQPMI_EUNSUPPORTED, "sdr_solve_unitdiag: N = %lld exceeds %d", (long long)N, SDR_NMAX);
     HIPCHK(c, hipSetDevice(c->device));
-    double *dC = nullptr, *dV = nullptr, *dh = nullptr;
-    int *ds = nullptr;
-    SdrWork *dw = nullptr;
-    int rc = 0;
-    if ((rc = dev_alloc(c, &dC, (size_t)N * N, false))) return rc;
-    if (!rc) rc = dev_alloc(c, &dV, (size_t)N * SDR_K, false);
-    if (!rc) rc = dev_alloc(c, &dh, (size_t)max_sweeps + 2);
-    if (!rc) rc = dev_alloc(c, &ds, 1);
-    if (!rc) rc = dev_alloc(c, &dw, 1);      // zeroed: arrival counter, abort flag
-    hipError_t e = hipSuccess;
+    DevBuf<double> bC, bV, bh;
+    DevBuf<int> bs;
+    DevBuf<SdrWork> bw;
+    HIPCHK(c, bC.reserve(c->stream, (size_t)N * N, false));
+    HIPCHK(c, bV.reserve(c->stream, (size_t)N * SDR_K, false));
+    HIPCHK(c, bh.reserve(c->stream, (size_t)max_sweeps + 2));
+    HIPCHK(c, bs.reserve(c->stream, 1));
+    HIPCHK(c, bw.reserve(c->stream, 1));      // zeroed: arrival counter, abort flag
     int sw = 0;
-    if (!rc) {
-        e = hipMemcpyAsync(dC, C, (size_t)N * N * sizeof(double), hipMemcpyHostToDevice, c->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(dV, V, (size_t)N * SDR_K * sizeof(double), hipMemcpyHostToDevice, c->stream);
-        if (e == hipSuccess) {
-            // 64 single-wave workgroups that synchronise through memory: cooperative launch = co-residency guaranteed
-            const double *aC = dC;
-            int aN = (int)N;
-            void *args[] = {(void *)&aC, (void *)&dV, (void *)&aN, (void *)&max_sweeps, (void *)&tol, (void *)&dh, (void *)&ds, (void *)&dw};
-            e = hipLaunchCooperativeKernel((const void *)sdr_mixing_kernel, dim3(SDR_K), dim3(64), args,
-                                           (unsigned)(2 * (size_t)N * sizeof(double)), c->stream);
-        }
-        if (e == hipSuccess) e = hipMemcpyAsync(V, dV, (size_t)N * SDR_K * sizeof(double), hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(hist, dh, ((size_t)max_sweeps + 2) * sizeof(double), hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(&sw, ds, sizeof(int), hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess) e = spin_sync(c->stream);
+    HIPCHK(c, hipMemcpyAsync(bC.p, C, (size_t)N * N * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(bV.p, V, (size_t)N * SDR_K * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    {
+        // 64 single-wave workgroups that synchronise through memory: cooperative launch = co-residency guaranteed
+        // (the argument array holds ADDRESSES of the arguments: plain pointers, not the buffers)
+        const double *aC = bC.p;
+        double *dV = bV.p, *dh = bh.p;
+        int *ds = bs.p;
+        SdrWork *dw = bw.p;
+        int aN = (int)N;
+        void *args[] = {(void *)&aC, (void *)&dV, (void *)&aN, (void *)&max_sweeps, (void *)&tol, (void *)&dh, (void *)&ds, (void *)&dw};
+        HIPCHK(c, hipLaunchCooperativeKernel((const void *)sdr_mixing_kernel, dim3(SDR_K), dim3(64), args,
+                                             (unsigned)(2 * (size_t)N * sizeof(double)), c->stream));
     }
-    void *ptrs[] = {dC, dV, dh, ds, dw};
-    for (void *p : ptrs) if (p) (void)hipFree(p);
-    if (rc) return rc;
-    if (e != hipSuccess) return fail(c, QCQPMI_EHIP, "sdr_solve_unitdiag: %s", hipGetErrorString(e));
+    HIPCHK(c, hipMemcpyAsync(V, bV.p, (size_t)N * SDR_K * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(hist, bh.p, ((size_t)max_sweeps + 2) * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(&sw, bs.p, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, spin_sync(c->stream));
     if (sw < 0) return fail(c, QCQPMI_EHIP, "sdr_solve_unitdiag: the workgroups lost step (spin limit reached)");
     *sweeps_done = sw;
     return 0;
@@ -1226,11 +1152,9 @@ int qcqpmi_pop_sdr_sample(qcqpmi_ctx *c, const double *mu, const double *F, int6
     if (reuse && !c->sdr_factor_resident) return fail(c, QCQPMI_ESTATE, "pop_sdr_sample: no resident factor to reuse");
     HIPCHK(c, hipSetDevice(c->device));
     const int64_t n = c->n, n16 = c->n16;
-    if (!c->d_Fpack) {
-        if ((rc = dev_alloc(c, &c->d_Fpack, (size_t)n16 * n16))) return rc;
-        if ((rc = dev_alloc(c, &c->d_Frow, (size_t)n16 * n16))) return rc;
-        if ((rc = dev_alloc(c, &c->d_mu, (size_t)n16))) return rc;
-    }
+    HIPCHK(c, c->d_Fpack.reserve(c->stream, (size_t)n16 * n16));
+    HIPCHK(c, c->d_Frow.reserve(c->stream, (size_t)n16 * n16));
+    HIPCHK(c, c->d_mu.reserve(c->stream, (size_t)n16));
     if (!reuse) {
         HIPCHK(c, hipMemsetAsync(c->d_Frow, 0, (size_t)n16 * n16 * sizeof(double), c->stream));
         HIPCHK(c, hipMemcpy2DAsync(c->d_Frow, (size_t)n16 * sizeof(double), F, (size_t)n * sizeof(double),
@@ -1246,11 +1170,7 @@ int qcqpmi_pop_sdr_sample(qcqpmi_ctx *c, const double *mu, const double *F, int6
     }
     if ((rc = pop_reserve(c, S))) return rc;
     // the standard normals: caller-provided (host layout) or device Philox; the buffer is kept across calls
-    if ((int64_t)c->Rpad * n16 > c->Xi_cap) {
-        if (c->Xi) { HIPCHK(c, spin_sync(c->stream)); (void)hipFree(c->Xi); c->Xi = nullptr; c->Xi_cap = 0; }
-        if ((rc = dev_alloc(c, &c->Xi, (size_t)c->Rpad * n16, false))) return rc;
-        c->Xi_cap = (int64_t)c->Rpad * n16;
-    }
+    HIPCHK(c, c->Xi.reserve(c->stream, (size_t)c->Rpad * n16, false));
     int64_t tot2 = c->Rpad * n16;
     if (Xi) {
         HIPCHK(c, hipMemcpyAsync(c->d_stage, Xi, (size_t)S * n * sizeof(double), hipMemcpyHostToDevice, c->stream));
@@ -1341,48 +1261,31 @@ int qcqpmi_pop_weighted_product(qcqpmi_ctx *c, const double *w, double *Y) {
         D.Gpack = c->dp.Apack; D.m1 = 1; D.m1p = 64; D.q = nullptr; D.qT = nullptr; D.r = nullptr; D.relop = nullptr;
     }
     const int64_t n16 = c->n16, ntiles = c->Rpad / 16;
-    if (!c->d_wS) {
-        if ((rc = dev_alloc(c, &c->d_ww, (size_t)D.m1, false))) return rc;
-        if ((rc = dev_alloc(c, &c->d_wS, (size_t)n16 * n16, false))) return rc;
-        if ((rc = dev_alloc(c, &c->d_wz, (size_t)n16))) return rc;   // zero offset vector of the affine map
-    }
-    if (c->Rpad * n16 > c->wY_cap) {
-        HIPCHK(c, spin_sync(c->stream));
-        if (c->d_wY) (void)hipFree(c->d_wY);
-        c->d_wY = nullptr;
-        if ((rc = dev_alloc(c, &c->d_wY, (size_t)c->Rpad * n16, false))) return rc;
-        c->wY_cap = c->Rpad * n16;
-    }
+    HIPCHK(c, c->d_ww.reserve(c->stream, (size_t)D.m1, false));
+    HIPCHK(c, c->d_wS.reserve(c->stream, (size_t)n16 * n16, false));
+    HIPCHK(c, c->d_wz.reserve(c->stream, (size_t)n16));   // zero offset vector of the affine map
+    HIPCHK(c, c->d_wY.reserve(c->stream, (size_t)c->Rpad * n16, false));
     double *dw = c->d_ww, *dS = c->d_wS, *dY = c->d_wY, *dz = c->d_wz;
-    if ((rc = pin_reserve(c, (size_t)(c->R * c->n) * sizeof(double) + (size_t)D.m1 * sizeof(double)))) return rc;
-    char *hw = c->h_pin + (size_t)(c->R * c->n) * sizeof(double);       // the weights go up through pinned memory too
+    const int64_t total = c->R * c->n;
+    if ((rc = pin_reserve(c, (size_t)total * sizeof(double) + (size_t)D.m1 * sizeof(double)))) return rc;
+    char *hw = c->h_pin + (size_t)total * sizeof(double);       // the weights go up through pinned memory too
     memcpy(hw, w, (size_t)D.m1 * sizeof(double));
-    hipError_t e = hipSuccess;
-    if (!rc) {
-        e = hipMemcpyAsync(dw, hw, (size_t)D.m1 * sizeof(double), hipMemcpyHostToDevice, c->stream);
-        if (e == hipSuccess) {
-            hipLaunchKernelGGL(dense_wsum_pack_kernel, dim3((unsigned)((n16 * n16 + 255) / 256)), dim3(256), 0, c->stream, D, (const double *)dw, dS);
-            DenseProdArgs pa;
-            pa.D = D; pa.D.Gpack = dS; pa.D.q = dz; pa.D.m1 = 1; pa.D.m1p = 64;
-            pa.X = c->X; pa.ntiles = (int)ntiles; pa.b = 0; pa.zs = 1; pa.G = dY; pa.F = nullptr; pa.Rpad = c->Rpad;
-            pa.tile_on = nullptr; pa.hole = -1; pa.ch_only = -1; pa.zplane = 0;
-            auto kg = dense_products_kernel<3>;
-            e = hipFuncSetAttribute((const void *)kg, hipFuncAttributeMaxDynamicSharedMemorySize, DP_LDS_BYTES);
-            if (e == hipSuccess) {
-                hipLaunchKernelGGL(kg, dim3((unsigned)((D.NB + DP_FG - 1) / DP_FG), (unsigned)((ntiles + DP_TG - 1) / DP_TG), 1),
-                                   dim3(256), DP_LDS_BYTES, c->stream, pa);
-                const int64_t total = c->R * c->n;
-                hipLaunchKernelGGL(from_tiles_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, c->stream,
-                                   (const double *)dY, c->d_stage, c->n, c->n16, c->R);
-                e = hipGetLastError();
-                if (e == hipSuccess) e = hipMemcpyAsync(c->h_pin, c->d_stage, (size_t)total * sizeof(double), hipMemcpyDeviceToHost, c->stream);
-            }
-        }
-        if (e == hipSuccess) e = spin_sync(c->stream);
-        if (e == hipSuccess) memcpy(Y, c->h_pin, (size_t)(c->R * c->n) * sizeof(double));
-    }
-    if (rc) return rc;
-    if (e != hipSuccess) return fail(c, QCQPMI_EHIP, "pop_weighted_product: %s", hipGetErrorString(e));
+    HIPCHK(c, hipMemcpyAsync(dw, hw, (size_t)D.m1 * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(dense_wsum_pack_kernel, dim3((unsigned)((n16 * n16 + 255) / 256)), dim3(256), 0, c->stream, D, (const double *)dw, dS);
+    DenseProdArgs pa;
+    pa.D = D; pa.D.Gpack = dS; pa.D.q = dz; pa.D.m1 = 1; pa.D.m1p = 64;
+    pa.X = c->X; pa.ntiles = (int)ntiles; pa.b = 0; pa.zs = 1; pa.G = dY; pa.F = nullptr; pa.Rpad = c->Rpad;
+    pa.tile_on = nullptr; pa.hole = -1; pa.ch_only = -1; pa.zplane = 0;
+    auto kg = dense_products_kernel<3>;
+    HIPCHK(c, hipFuncSetAttribute((const void *)kg, hipFuncAttributeMaxDynamicSharedMemorySize, DP_LDS_BYTES));
+    hipLaunchKernelGGL(kg, dim3((unsigned)((D.NB + DP_FG - 1) / DP_FG), (unsigned)((ntiles + DP_TG - 1) / DP_TG), 1),
+                       dim3(256), DP_LDS_BYTES, c->stream, pa);
+    hipLaunchKernelGGL(from_tiles_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, c->stream,
+                       (const double *)dY, c->d_stage, c->n, c->n16, c->R);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(c->h_pin, c->d_stage, (size_t)total * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, spin_sync(c->stream));
+    memcpy(Y, c->h_pin, (size_t)total * sizeof(double));
     return 0;
 }
 
@@ -1404,25 +1307,16 @@ int qcqpmi_weighted_matrix(qcqpmi_ctx *c, const double *w, double *S) {
     HIPCHK(c, hipSetDevice(c->device));
     const DenseProblem D = dense_problem(c);
     const int64_t n = c->n, n16 = c->n16;
-    double *dw = nullptr, *dS = nullptr, *dU = nullptr;
-    rc = dev_alloc(c, &dw, (size_t)D.m1, false);
-    if (!rc) rc = dev_alloc(c, &dS, (size_t)n16 * n16, false);
-    if (!rc) rc = dev_alloc(c, &dU, (size_t)n * n, false);
-    hipError_t e = hipSuccess;
-    if (!rc) {
-        e = hipMemcpyAsync(dw, w, (size_t)D.m1 * sizeof(double), hipMemcpyHostToDevice, c->stream);
-        if (e == hipSuccess) {
-            hipLaunchKernelGGL(dense_wsum_pack_kernel, dim3((unsigned)((n16 * n16 + 255) / 256)), dim3(256), 0, c->stream, D, (const double *)dw, dS);
-            hipLaunchKernelGGL(dense_unpack_kernel, dim3((unsigned)((n * n + 255) / 256)), dim3(256), 0, c->stream, (const double *)dS, dU, n, (int)(n16 / 4));
-            e = hipGetLastError();
-        }
-        if (e == hipSuccess) e = hipMemcpyAsync(S, dU, (size_t)n * n * sizeof(double), hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess) e = spin_sync(c->stream);
-    }
-    void *ptrs[] = {dw, dS, dU};
-    for (void *p : ptrs) if (p) (void)hipFree(p);
-    if (rc) return rc;
-    if (e != hipSuccess) return fail(c, QCQPMI_EHIP, "weighted_matrix: %s", hipGetErrorString(e));
+    DevBuf<double> dw, dS, dU;
+    HIPCHK(c, dw.reserve(c->stream, (size_t)D.m1, false));
+    HIPCHK(c, dS.reserve(c->stream, (size_t)n16 * n16, false));
+    HIPCHK(c, dU.reserve(c->stream, (size_t)n * n, false));
+    HIPCHK(c, hipMemcpyAsync(dw.p, w, (size_t)D.m1 * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(dense_wsum_pack_kernel, dim3((unsigned)((n16 * n16 + 255) / 256)), dim3(256), 0, c->stream, D, (const double *)dw.p, dS.p);
+    hipLaunchKernelGGL(dense_unpack_kernel, dim3((unsigned)((n * n + 255) / 256)), dim3(256), 0, c->stream, (const double *)dS.p, dU.p, n, (int)(n16 / 4));
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(S, dU.p, (size_t)n * n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, spin_sync(c->stream));
     return 0;
 }
 
@@ -1441,7 +1335,7 @@ int qcqpmi_pop_eval_parts(qcqpmi_ctx *c, double *quad, double *lin) {
     HIPCHK(c, hipMemcpyAsync(c->h_pin, c->d_F, plane, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipMemcpyAsync(c->h_pin + plane, dlin, plane, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, spin_sync(c->stream));
-    const double *hq = (const double *)c->h_pin, *hl = (const double *)(c->h_pin + plane);
+    const double *hq = (const double *)c->h_pin.p, *hl = (const double *)(c->h_pin + plane);
     for (int64_t k = 0; k < m1; k++) {
         memcpy(quad + k * c->R, hq + k * c->Rpad, (size_t)c->R * sizeof(double));
         memcpy(lin + k * c->R, hl + k * c->Rpad, (size_t)c->R * sizeof(double));
@@ -1517,9 +1411,9 @@ int qcqpmi_cd_run_stage(qcqpmi_ctx *c, int stage, int phase1, int64_t num_iters,
     }
     if (stage == 0 || stage == 2) {
         if (c->profile) {
-            if (c->d_prof) { (void)hipFree(c->d_prof); c->d_prof = nullptr; }
-            if ((rc = dev_alloc(c, &c->d_prof, (size_t)(c->Rpad / 16) * 16 + QCQPMI_TRACE_WORDS))) return rc;
-            HIPCHK(c, hipMemsetAsync(c->d_prof + (size_t)(c->Rpad / 16) * 16, 0, QCQPMI_TRACE_WORDS * sizeof(long long), c->stream));
+            const size_t words = (size_t)(c->Rpad / 16) * 16 + QCQPMI_TRACE_WORDS;
+            HIPCHK(c, c->d_prof.reserve(c->stream, words, false));
+            HIPCHK(c, hipMemsetAsync(c->d_prof, 0, words * sizeof(long long), c->stream));
             a.prof = c->d_prof;
         }
         // the pipelined kernel leaves objective and max violation of the restarts it ran in place (tracked objective,
@@ -1557,19 +1451,14 @@ int qcqpmi_cd_dense_block_step(qcqpmi_ctx *c, int phase, int64_t sweep, int64_t 
 
 // buffers of cd_life_kernel: the workgroups' X tiles, the staged diagonal blocks (packed once per problem), the watchdog word
 static int cd_life2_reserve(qcqpmi_ctx *c, int nmw, int cus) {
-    int rc;
     const size_t need = (size_t)cd_life2_max_wgs(nmw, cus, 1) * (size_t)c->n16 * 16;      // (two tiles per workgroup: half the workgroups, the same tiles)
-    if (need > c->l2_scratch_cap) {
-        if (c->l2_scratch) { HIPCHK(c, spin_sync(c->stream)); (void)hipFree(c->l2_scratch); c->l2_scratch = nullptr; c->l2_scratch_cap = 0; }
-        if ((rc = dev_alloc(c, &c->l2_scratch, need))) return rc;
-        c->l2_scratch_cap = need;
-    }
-    if (!c->l2_abort && (rc = dev_alloc(c, &c->l2_abort, 4))) return rc;
-    if (!c->l2_cuslot && (rc = dev_alloc(c, &c->l2_cuslot, 4096))) return rc;
-    if (!c->l2_D) {
+    HIPCHK(c, c->l2_scratch.reserve(c->stream, need));
+    HIPCHK(c, c->l2_abort.reserve(c->stream, 4));
+    HIPCHK(c, c->l2_cuslot.reserve(c->stream, 4096));
+    if (!c->l2_S) {      // (the second of the pair: a call that failed between the two starts over)
         const size_t NB = (size_t)(c->n16 / 16);
-        if ((rc = dev_alloc(c, &c->l2_D, NB * 256))) return rc;
-        if ((rc = dev_alloc(c, &c->l2_S, NB * 48))) return rc;
+        HIPCHK(c, c->l2_D.reserve(c->stream, NB * 256));
+        HIPCHK(c, c->l2_S.reserve(c->stream, NB * 48));
         hipError_t e = (hipError_t)cd_life2_pack(c->dp, c->l2_D, c->l2_S, c->stream);
         if (e != hipSuccess) return fail(c, QCQPMI_EHIP, "cd_life2_pack: %s", hipGetErrorString(e));
     }
@@ -1590,18 +1479,9 @@ static int64_t cd_life2_y0_count(int64_t KR, int RB) {
 
 // buffers of the pre-passes of a prebuilt factored run of KR restarts: the slacks (cd_life_prep_kernel) and Y0 (cd_life_y0_kernel)
 static int cd_life2_pre_reserve(qcqpmi_ctx *c, int64_t KR, int RB) {
-    int rc;
-    if (KR > c->l2_preslack_cap) {
-        if (c->l2_preslack) { HIPCHK(c, spin_sync(c->stream)); (void)hipFree(c->l2_preslack); c->l2_preslack = nullptr; c->l2_preslack_cap = 0; }
-        if ((rc = dev_alloc(c, &c->l2_preslack, (size_t)KR))) return rc;
-        c->l2_preslack_cap = KR;
-    }
+    HIPCHK(c, c->l2_preslack.reserve(c->stream, (size_t)KR));
     const size_t need = (size_t)((cd_life2_y0_count(KR, RB) + 15) / 16) * (size_t)RB * 256;
-    if (need > c->l2_y0_cap) {
-        if (c->l2_y0) { HIPCHK(c, spin_sync(c->stream)); (void)hipFree(c->l2_y0); c->l2_y0 = nullptr; c->l2_y0_cap = 0; }
-        if ((rc = dev_alloc(c, &c->l2_y0, need, false))) return rc;      // (every element a restart reads is written by the pre-pass)
-        c->l2_y0_cap = need;
-    }
+    HIPCHK(c, c->l2_y0.reserve(c->stream, need, false));      // (every element a restart reads is written by the pre-pass)
     return 0;
 }
 
@@ -1656,8 +1536,8 @@ int qcqpmi_cd_stream_run(qcqpmi_ctx *c, int64_t K, int64_t R, int generate, int 
         if (NBq - cs > RQ_NSIMD * RQ_MAXU || NBq < 3) return fail(c, QCQPMI_EUNSUPPORTED, "cd_stream_run: n = %lld outside the range of cd_phase2_qs_kernel (n <= 1024, at least 3 blocks of 16)", (long long)c->n);
     }
     if (generate && (rc = pop_reserve(c, K * R))) return rc;
-    if (!c->d_qnext && (rc = dev_alloc(c, &c->d_qnext, 16))) return rc;
-    if (!c->d_life) HIPCHK(c, hipMalloc((void **)&c->d_life, sizeof(CdLife)));
+    HIPCHK(c, c->d_qnext.reserve(c->stream, 16));
+    HIPCHK(c, c->d_life.reserve(c->stream, 1, false));
     HIPCHK(c, hipMemsetAsync(c->d_qnext, 0, 16 * sizeof(int), c->stream));
     CdLife L;
     L.on = 1; L.generate = generate ? 1 : 0; L.phase1 = phase1 ? 1 : 0; L.Rtotal = K * R; L.Rpop = R;
@@ -1679,7 +1559,7 @@ int qcqpmi_cd_stream_run(qcqpmi_ctx *c, int64_t K, int64_t R, int generate, int 
     }
     const int64_t y0_count = L.y0_count;
     if (c->profile) {      // qcqpmi_debug_profile: tick sums of the launch (qcqpmi_debug_life_profile)
-        if (!c->d_life_prof) HIPCHK(c, hipMalloc((void **)&c->d_life_prof, 24 * sizeof(long long)));
+        HIPCHK(c, c->d_life_prof.reserve(c->stream, 24, false));
         HIPCHK(c, hipMemsetAsync(c->d_life_prof, 0, 24 * sizeof(long long), c->stream));
         L.prof = c->d_life_prof;
     }
@@ -1799,8 +1679,8 @@ int qcqpmi_cd_stream_reserve(qcqpmi_ctx *c, int64_t K, int64_t R) {
     if (K * R > c->Rcap) { if ((rc = pop_reserve(c, K * R))) return rc; }       // (a resident population of that size or more stays)
     if ((rc = cd_outputs_reserve(c, K * R))) return rc;
     if ((rc = cd_bestK_reserve(c, K))) return rc;
-    if (!c->d_qnext && (rc = dev_alloc(c, &c->d_qnext, 16))) return rc;
-    if (!c->d_life) HIPCHK(c, hipMalloc((void **)&c->d_life, sizeof(CdLife)));
+    HIPCHK(c, c->d_qnext.reserve(c->stream, 16));
+    HIPCHK(c, c->d_life.reserve(c->stream, 1, false));
     {
         int nmw = 0, cs2 = 0, kind = 0, cus = 0;
         HIPCHK(c, hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device));
@@ -1870,7 +1750,7 @@ int qcqpmi_cd_set_objective_factor(qcqpmi_ctx *c, const double *L, int64_t r) {
     if (rc) return rc;
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, spin_sync(c->stream));
-    for (double **p : {&c->lr_L, &c->lr_G, &c->lr_U}) if (*p) { (void)hipFree(*p); *p = nullptr; }
+    c->lr_L.release(); c->lr_G.release(); c->lr_U.release();
     c->lr_RB = 0;
     if (!L || r == 0) return 0;                       // cleared
     if (r < 1 || r > c->n) return fail(c, QCQPMI_EINVAL, "cd_set_objective_factor: r = %lld outside 1 .. n", (long long)r);
@@ -1878,9 +1758,9 @@ int qcqpmi_cd_set_objective_factor(qcqpmi_ctx *c, const double *L, int64_t r) {
         return fail(c, QCQPMI_EUNSUPPORTED, "cd_set_objective_factor: the factored lifecycle kernel takes factors of at most 288 columns and n >= 128");
     const int64_t n = c->n, n16 = c->n16, r16 = (r + 15) / 16 * 16;
     const int RB = (int)(r16 / 16), NB = (int)(n16 / 16);
-    if ((rc = dev_alloc(c, &c->lr_L, (size_t)n16 * r16))) return rc;      // (zero-filled)
-    if ((rc = dev_alloc(c, &c->lr_G, (size_t)NB * RB * 256, false))) return rc;
-    if ((rc = dev_alloc(c, &c->lr_U, (size_t)NB * RB * 256, false))) return rc;
+    HIPCHK(c, c->lr_L.reserve(c->stream, (size_t)n16 * r16));      // (zero-filled)
+    HIPCHK(c, c->lr_G.reserve(c->stream, (size_t)NB * RB * 256, false));
+    HIPCHK(c, c->lr_U.reserve(c->stream, (size_t)NB * RB * 256, false));
     HIPCHK(c, hipMemcpy2DAsync(c->lr_L, (size_t)r16 * sizeof(double), L, (size_t)r * sizeof(double), (size_t)r * sizeof(double), (size_t)n,
                                hipMemcpyHostToDevice, c->stream));
     hipError_t e = (hipError_t)cd_life2_pack_factor(c->lr_L, c->lr_G, c->lr_U, NB, RB, c->stream);
@@ -1987,10 +1867,7 @@ int qcqpmi_comm_init(qcqpmi_ctx *c, int rank, int world, const uint8_t id_in[128
     memcpy(id.internal, id_in, 128);
     NCCLCHK(c, rccl()->CommInitRank(&c->comm, world, id, rank));
     c->rank = rank; c->world = world;
-    if (!c->d_comm) {
-        int rc = dev_alloc(c, &c->d_comm, (size_t)4 * world + 4 + (size_t)c->n);
-        if (rc) return rc;
-    }
+    HIPCHK(c, c->d_comm.reserve(c->stream, (size_t)4 * world + 4 + (size_t)c->n));
     return 0;
 }
 
@@ -2005,8 +1882,7 @@ int qcqpmi_comm_allreduce(qcqpmi_ctx *c, double *values, int64_t count, int op) 
     HIPCHK(c, hipSetDevice(c->device));
     double *buf = c->d_comm;
     if (count > 4) {      // the exchange of a streamed run (keys of all populations, then the winners' points): a buffer of its own
-        const int rc = grow_device_buffer(c, &c->d_comm_big, &c->comm_big_cap, (size_t)count * sizeof(double));
-        if (rc) return rc;
+        HIPCHK(c, c->d_comm_big.reserve(c->stream, (size_t)count, false));
         buf = c->d_comm_big;
     }
     HIPCHK(c, hipMemcpyAsync(buf, values, (size_t)count * sizeof(double), hipMemcpyHostToDevice, c->stream));
@@ -2022,9 +1898,8 @@ int qcqpmi_comm_allgather(qcqpmi_ctx *c, const void *send, int64_t nbytes, void 
     if (!c->comm) return fail(c, QCQPMI_ESTATE, "comm_init has not been called");
     HIPCHK(c, hipSetDevice(c->device));
     const int64_t need = ((int64_t)(c->world + 1) * nbytes + 7) / 8;      // doubles: send area + receive area
-    const int rc = grow_device_buffer(c, &c->d_comm_big, &c->comm_big_cap, (size_t)need * sizeof(double));
-    if (rc) return rc;
-    char *d_send = (char *)c->d_comm_big, *d_recv = d_send + nbytes;
+    HIPCHK(c, c->d_comm_big.reserve(c->stream, (size_t)need, false));
+    char *d_send = (char *)c->d_comm_big.p, *d_recv = d_send + nbytes;
     HIPCHK(c, hipMemcpyAsync(d_send, send, (size_t)nbytes, hipMemcpyHostToDevice, c->stream));
     NCCLCHK(c, rccl()->AllGather(d_send, d_recv, (size_t)nbytes, ncclInt8, c->comm, c->stream));
     HIPCHK(c, hipMemcpyAsync(recv, d_recv, (size_t)nbytes * (size_t)c->world, hipMemcpyDeviceToHost, c->stream));

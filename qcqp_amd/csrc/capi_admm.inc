@@ -96,28 +96,19 @@ __global__ void admm_symmetrise_kernel(double *__restrict__ A, int64_t n, int64_
         if (s_ != 0) return fail(c, QCQPMI_EHIP, "%s failed: rocblas status %d", #expr, s_); \
     } while (0)
 
-// keep_zsolver: a new basis does not invalidate (2 (P0 + rho m I))^-1
-void admm_free(qcqpmi_ctx *c, bool keep_zsolver) {
-    void *ptrs[] = {c->ad_WTpk, c->ad_Wpk, c->ad_lam, c->ad_qhat, c->ad_rk, c->ad_relop, c->ad_slo, c->ad_ehi, c->ad_uidx, c->ad_uptr, c->ad_ulist, c->ad_usgn};
-    for (void *p : ptrs) if (p) (void)hipFree(p);
-    c->ad_uidx = c->ad_uptr = c->ad_ulist = nullptr; c->ad_usgn = nullptr; c->ad_unit = false;
-    c->ad_WTpk = c->ad_Wpk = c->ad_lam = c->ad_qhat = c->ad_rk = c->ad_slo = c->ad_ehi = nullptr;
-    if (!keep_zsolver) {
-        if (c->ad_Minvpk) (void)hipFree(c->ad_Minvpk);
-        c->ad_Minvpk = nullptr;
-        c->ad_Minv_device = false;
-    }
-    c->ad_relop = nullptr;
-    c->ad_rows = 0; c->ad_Mh16 = 0; c->ad_lowrank = 0;
+void admm_drop_handle(qcqpmi_ctx *c) {
     if (c->rb_handle && rocblas() && rocblas()->destroy) rocblas()->destroy(c->rb_handle);
     c->rb_handle = nullptr;
 }
 
-template <typename T>
-struct DevBuf {   // scoped device allocation for the work arrays of one admm_run
-    T *p = nullptr;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-};
+// drops the installed basis; ad_Minvpk stays: a new basis does not invalidate (2 (P0 + rho m I))^-1
+void admm_free(qcqpmi_ctx *c) {
+    c->ad_WTpk.release(); c->ad_Wpk.release(); c->ad_lam.release(); c->ad_qhat.release(); c->ad_rk.release(); c->ad_relop.release();
+    c->ad_slo.release(); c->ad_ehi.release(); c->ad_uidx.release(); c->ad_uptr.release(); c->ad_ulist.release(); c->ad_usgn.release();
+    c->ad_unit = false;
+    c->ad_rows = 0; c->ad_Mh16 = 0; c->ad_lowrank = 0;
+    admm_drop_handle(c);
+}
 
 int gemm_pk(qcqpmi_ctx *c, const double *A, const double *B, double *C, const double *bias, int MB, int KB, int ntiles, int zs,
             double alpha = 1.0) {
@@ -149,9 +140,8 @@ int admm_install_basis(qcqpmi_ctx *c, const double *Wd, int64_t rows) {
     const int64_t n = c->n, n16 = c->n16, m = c->m;
     const int64_t Mh = m * rows, Mh16 = (Mh + 15) / 16 * 16;
     if (Mh16 / 16 > 2147483647LL / 64 || Mh16 * n16 > (int64_t)1 << 40) return fail(c, QCQPMI_EUNSUPPORTED, "admm: basis too large");
-    int rc;
-    if ((rc = dev_alloc(c, &c->ad_WTpk, (size_t)Mh16 * n16, false))) return rc;
-    if ((rc = dev_alloc(c, &c->ad_Wpk, (size_t)Mh16 * n16, false))) return rc;
+    HIPCHK(c, c->ad_WTpk.reserve(c->stream, (size_t)Mh16 * n16, false));
+    HIPCHK(c, c->ad_Wpk.reserve(c->stream, (size_t)Mh16 * n16, false));
     const int MBh = (int)(Mh16 / 16), KBn = (int)(n16 / 16);
     const int64_t tot = Mh16 * n16;
     hipLaunchKernelGGL(gemm_pk_pack_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, c->stream, Wd, c->ad_WTpk, Mh, n, n, (int64_t)1, MBh, KBn);
@@ -181,18 +171,17 @@ int admm_upload_small(qcqpmi_ctx *c, const double *lam, const double *qhat, int6
     c->ad_qzero = true;
     for (int64_t t = 0; t < m * rows; t++) if (qhat[t] != 0.0) { c->ad_qzero = false; break; }
     int rc;
-    auto up = [&](double **dst, const double *src, size_t cnt) -> int {
-        int r_ = dev_alloc(c, dst, cnt, false);
-        if (r_) return r_;
-        HIPCHK(c, hipMemcpyAsync(*dst, src, cnt * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    auto up = [&](DevBuf<double> &dst, const double *src, size_t cnt) -> int {
+        HIPCHK(c, dst.reserve(c->stream, cnt, false));
+        HIPCHK(c, hipMemcpyAsync(dst.p, src, cnt * sizeof(double), hipMemcpyHostToDevice, c->stream));
         return 0;
     };
-    if ((rc = up(&c->ad_lam, lam, (size_t)m * rows))) return rc;
-    if ((rc = up(&c->ad_qhat, qhat, (size_t)m * rows))) return rc;
-    if ((rc = up(&c->ad_rk, rk.data(), rk.size()))) return rc;
-    if ((rc = up(&c->ad_slo, slo.data(), slo.size()))) return rc;
-    if ((rc = up(&c->ad_ehi, ehi.data(), ehi.size()))) return rc;
-    if ((rc = dev_alloc(c, &c->ad_relop, (size_t)m, false))) return rc;
+    if ((rc = up(c->ad_lam, lam, (size_t)m * rows))) return rc;
+    if ((rc = up(c->ad_qhat, qhat, (size_t)m * rows))) return rc;
+    if ((rc = up(c->ad_rk, rk.data(), rk.size()))) return rc;
+    if ((rc = up(c->ad_slo, slo.data(), slo.size()))) return rc;
+    if ((rc = up(c->ad_ehi, ehi.data(), ehi.size()))) return rc;
+    HIPCHK(c, c->ad_relop.reserve(c->stream, (size_t)m, false));
     HIPCHK(c, hipMemcpyAsync(c->ad_relop, relop.data(), (size_t)m * sizeof(int), hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, spin_sync(c->stream));
     return 0;
@@ -251,7 +240,7 @@ int qcqpmi_admm_set_eig(qcqpmi_ctx *c, const double *lmb, const double *Q) {
     if (c->m < 1) return fail(c, QCQPMI_EINVAL, "admm needs at least one constraint");
     HIPCHK(c, hipSetDevice(c->device));
     const int64_t n = c->n, m = c->m;
-    admm_free(c, true);
+    admm_free(c);
     // Wd[k][j][i] = Q_k[i][j]: eigenvector j of constraint k contiguous (NumPy's eigh layout transposed)
     std::vector<double> W((size_t)m * n * n), qhat((size_t)m * n);
     for (int64_t k = 0; k < m; k++) {
@@ -267,7 +256,7 @@ int qcqpmi_admm_set_eig(qcqpmi_ctx *c, const double *lmb, const double *Q) {
         }
     }
     DevBuf<double> Wd;
-    if ((rc = dev_alloc(c, &Wd.p, W.size(), false))) return rc;
+    HIPCHK(c, Wd.reserve(c->stream, W.size(), false));
     HIPCHK(c, hipMemcpyAsync(Wd.p, W.data(), W.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
     if ((rc = admm_install_basis(c, Wd.p, n))) return rc;
     if ((rc = admm_upload_small(c, lmb, qhat.data(), n))) return rc;
@@ -319,11 +308,10 @@ int admm_install_unit(qcqpmi_ctx *c, const double *Bv, int64_t rows) {
     for (int64_t i = 0; i < n16; i++) ptr[(size_t)i + 1] += ptr[(size_t)i];
     std::vector<int> fill(ptr.begin(), ptr.end() - 1);
     for (int64_t h = 0; h < Mh; h++) list[(size_t)fill[(size_t)idx[(size_t)h]]++] = (int)h;     // ascending h per coordinate
-    int rc;
-    if ((rc = dev_alloc(c, &c->ad_uidx, idx.size(), false))) return rc;
-    if ((rc = dev_alloc(c, &c->ad_usgn, sgn.size(), false))) return rc;
-    if ((rc = dev_alloc(c, &c->ad_uptr, ptr.size(), false))) return rc;
-    if ((rc = dev_alloc(c, &c->ad_ulist, list.size(), false))) return rc;
+    HIPCHK(c, c->ad_uidx.reserve(c->stream, idx.size(), false));
+    HIPCHK(c, c->ad_usgn.reserve(c->stream, sgn.size(), false));
+    HIPCHK(c, c->ad_uptr.reserve(c->stream, ptr.size(), false));
+    HIPCHK(c, c->ad_ulist.reserve(c->stream, list.size(), false));
     HIPCHK(c, hipMemcpyAsync(c->ad_uidx, idx.data(), idx.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(c->ad_usgn, sgn.data(), sgn.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(c->ad_uptr, ptr.data(), ptr.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
@@ -344,9 +332,9 @@ int qcqpmi_admm_set_basis(qcqpmi_ctx *c, int64_t rp, const double *lam, const do
         return fail(c, QCQPMI_EUNSUPPORTED, "admm_set_basis: reduced bases come with 1, 2, 4 or 8 rows per constraint (pad with zero rows), or more than 8");
     HIPCHK(c, hipSetDevice(c->device));
     const int64_t n = c->n, m = c->m;
-    admm_free(c, true);
+    admm_free(c);
     DevBuf<double> Wd;
-    if ((rc = dev_alloc(c, &Wd.p, (size_t)m * rp * n, false))) return rc;
+    HIPCHK(c, Wd.reserve(c->stream, (size_t)m * rp * n, false));
     HIPCHK(c, hipMemcpyAsync(Wd.p, Bv, (size_t)m * rp * n * sizeof(double), hipMemcpyHostToDevice, c->stream));
     if ((rc = admm_install_basis(c, Wd.p, rp))) return rc;
     if ((rc = admm_upload_small(c, lam, qhat, rp))) return rc;
@@ -380,8 +368,8 @@ int qcqpmi_admm_apply_constraints(qcqpmi_ctx *c, int p, const double *Vin, int s
     const int64_t n = c->n, m = c->m;
     DevBuf<double> dV, dO;
     const size_t vin = (size_t)(shared ? 1 : m) * n * p, vout = (size_t)m * n * p;
-    if ((rc = dev_alloc(c, &dV.p, vin, false))) return rc;
-    if ((rc = dev_alloc(c, &dO.p, vout, false))) return rc;
+    HIPCHK(c, dV.reserve(c->stream, vin, false));
+    HIPCHK(c, dO.reserve(c->stream, vout, false));
     HIPCHK(c, hipMemcpyAsync(dV.p, Vin, vin * sizeof(double), hipMemcpyHostToDevice, c->stream));
     hipLaunchKernelGGL(admm_apply_constraints_kernel, dim3((unsigned)((n + 15) / 16), (unsigned)m), dim3(256), 0, c->stream,
                        (const double *)c->d_gP, (const double *)dV.p, dO.p, n, p, shared ? 1 : 0);
@@ -403,19 +391,19 @@ int qcqpmi_admm_setup(qcqpmi_ctx *c) {
     HIPCHK(c, hipSetDevice(c->device));
     const int64_t n = c->n, m = c->m;
     if (n > 32768 || m > 1000000) return fail(c, QCQPMI_EUNSUPPORTED, "admm_setup: sizes exceed rocSOLVER int range");
-    admm_free(c, true);
+    admm_free(c);
     RBCHK(c, rb->create(&c->rb_handle));      // rocSOLVER takes a rocBLAS handle (setup only; no product of the iteration uses it)
     RBCHK(c, rb->set_stream(c->rb_handle, c->stream));
     DevBuf<double> W, E, lam, qh;
     DevBuf<int> info;
-    if ((rc = dev_alloc(c, &W.p, (size_t)m * n * n, false))) return rc;
-    if ((rc = dev_alloc(c, &lam.p, (size_t)m * n, false))) return rc;
-    if ((rc = dev_alloc(c, &qh.p, (size_t)m * n, false))) return rc;
-    if ((rc = dev_alloc(c, &E.p, (size_t)m * n, false))) return rc;
-    if ((rc = dev_alloc(c, &info.p, (size_t)m))) return rc;
+    HIPCHK(c, W.reserve(c->stream, (size_t)m * n * n, false));
+    HIPCHK(c, lam.reserve(c->stream, (size_t)m * n, false));
+    HIPCHK(c, qh.reserve(c->stream, (size_t)m * n, false));
+    HIPCHK(c, E.reserve(c->stream, (size_t)m * n, false));
+    HIPCHK(c, info.reserve(c->stream, (size_t)m));
     DevBuf<double> slo, ehi;
-    if ((rc = dev_alloc(c, &slo.p, (size_t)m, false))) return rc;
-    if ((rc = dev_alloc(c, &ehi.p, (size_t)m, false))) return rc;
+    HIPCHK(c, slo.reserve(c->stream, (size_t)m, false));
+    HIPCHK(c, ehi.reserve(c->stream, (size_t)m, false));
     // symmetric row-major == column-major: the matrices go into W in place and come back as eigenvectors
     HIPCHK(c, hipMemcpyAsync(W.p, c->d_gP, (size_t)m * n * n * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
     const int64_t tot = m * n * n;
@@ -453,15 +441,15 @@ int qcqpmi_admm_onecons(qcqpmi_ctx *c, int64_t k, double *out) {
     const int ntiles = (int)(Rpad / 16), KBn = (int)(n16 / 16), MBh = (int)(c->ad_Mh16 / 16);
     DevBuf<double> ZQ, Xo;
     DevBuf<uint8_t> act;
-    if ((rc = dev_alloc(c, &ZQ.p, (size_t)c->ad_Mh16 * Rpad))) return rc;
-    if ((rc = dev_alloc(c, &Xo.p, (size_t)n16 * Rpad))) return rc;
-    if ((rc = dev_alloc(c, &act.p, (size_t)Rpad))) return rc;
+    HIPCHK(c, ZQ.reserve(c->stream, (size_t)c->ad_Mh16 * Rpad));
+    HIPCHK(c, Xo.reserve(c->stream, (size_t)n16 * Rpad));
+    HIPCHK(c, act.reserve(c->stream, (size_t)Rpad));
     HIPCHK(c, hipMemsetAsync(act.p, 1, (size_t)Rpad, c->stream));
     if ((rc = gemm_pk(c, c->ad_WTpk, c->X, ZQ.p, nullptr, MBh, KBn, ntiles, 1))) return rc;
     if (c->ad_lowrank) {
         // keep B^T z: x = z + B (xhat - B^T z)
         DevBuf<double> ZB;
-        if ((rc = dev_alloc(c, &ZB.p, (size_t)c->ad_Mh16 * Rpad, false))) return rc;
+        HIPCHK(c, ZB.reserve(c->stream, (size_t)c->ad_Mh16 * Rpad, false));
         HIPCHK(c, hipMemcpyAsync(ZB.p, ZQ.p, (size_t)c->ad_Mh16 * Rpad * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
         AdmmArgs sa;
         admm_fill_args(c, sa, R);
@@ -596,11 +584,9 @@ int qcqpmi_admm_zsolver_device(qcqpmi_ctx *c, double rho, int64_t max_iter, doub
     int rc;
     DevBuf<double> Mtm, Mpk, Xtm, Xpk, Ttm, Utm, rs;
     DevBuf<unsigned long long> rb;
-    if ((rc = dev_alloc(c, &Mtm.p, (size_t)tot, false)) || (rc = dev_alloc(c, &Mpk.p, (size_t)tot, false)) ||
-        (rc = dev_alloc(c, &Xtm.p, (size_t)tot, false)) || (rc = dev_alloc(c, &Xpk.p, (size_t)tot, false)) ||
-        (rc = dev_alloc(c, &Ttm.p, (size_t)tot, false)) || (rc = dev_alloc(c, &Utm.p, (size_t)tot, false)) ||
-        (rc = dev_alloc(c, &rs.p, (size_t)n16, false)) || (rc = dev_alloc(c, &rb.p, 1, false)))
-        return rc;
+    for (DevBuf<double> *b : {&Mtm, &Mpk, &Xtm, &Xpk, &Ttm, &Utm}) HIPCHK(c, b->reserve(st, (size_t)tot, false));
+    HIPCHK(c, rs.reserve(st, (size_t)n16, false));
+    HIPCHK(c, rb.reserve(st, 1, false));
     const dim3 gb((unsigned)((tot + 255) / 256)), tb(256);
     hipLaunchKernelGGL(zs_build_kernel, gb, tb, 0, st, c->dp.P0, n, n16, rho * (double)m, Mtm.p);
     hipLaunchKernelGGL(zs_pack_sym_kernel, gb, tb, 0, st, (const double *)Mtm.p, Mpk.p, n16);
@@ -643,8 +629,7 @@ int qcqpmi_admm_zsolver_device(qcqpmi_ctx *c, double rho, int64_t max_iter, doub
     if ((rc = gemm_pk(c, Xpk.p, Ttm.p, Utm.p, nullptr, KBn, KBn, nt, 1))) return rc;             // U = X R
     hipLaunchKernelGGL(zs_add_kernel, gb, tb, 0, st, Xtm.p, (const double *)Utm.p, tot);
     HIPCHK(c, hipGetLastError());
-    if (c->ad_Minvpk) { (void)hipFree(c->ad_Minvpk); c->ad_Minvpk = nullptr; }
-    if ((rc = dev_alloc(c, &c->ad_Minvpk, (size_t)tot, false))) return rc;
+    HIPCHK(c, c->ad_Minvpk.reserve(c->stream, (size_t)tot, false));      // (n16 x n16 whatever rho: reused)
     hipLaunchKernelGGL(zs_pack_sym_kernel, gb, tb, 0, st, (const double *)Xtm.p, c->ad_Minvpk, n16);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, spin_sync(st));
@@ -708,9 +693,9 @@ int qcqpmi_p0_lambda_min(qcqpmi_ctx *c, int64_t max_steps, double tol, double *l
     if (max_steps <= 0 || max_steps > n) max_steps = n;
     if (!(tol > 0.0)) tol = 1e-12;
     hipStream_t st = c->stream;
-    int rc;
     DevBuf<double> dv, dy;
-    if ((rc = dev_alloc(c, &dv.p, (size_t)n16, false)) || (rc = dev_alloc(c, &dy.p, (size_t)n16, false))) return rc;
+    HIPCHK(c, dv.reserve(st, (size_t)n16, false));
+    HIPCHK(c, dy.reserve(st, (size_t)n16, false));
     std::vector<std::vector<double>> V;
     std::vector<double> al, be, w((size_t)n), v((size_t)n);
     uint64_t sd = 0x9E3779B97F4A7C15ull;
@@ -796,13 +781,8 @@ static int admm_run_fused(qcqpmi_ctx *c, int phase1, int64_t num_iters, double t
     const size_t n_flags = (size_t)a.ntiles * 2 * a.C + 2;
     const size_t bytes = (nR + n_xb1 + n_xb2 + 4 * (size_t)Rpad + 2 * (size_t)n16) * sizeof(double) + (n_flags + 2) * sizeof(unsigned) + 16 * sizeof(long long);
     hipStream_t st = c->stream;
-    if (bytes > c->af_work_cap) {
-        HIPCHK(c, spin_sync(st));
-        if (c->af_work) { (void)hipFree(c->af_work); c->af_work = nullptr; c->af_work_cap = 0; }
-        HIPCHK(c, hipMalloc((void **)&c->af_work, bytes));
-        c->af_work_cap = bytes;
-    }
-    double *wp = reinterpret_cast<double *>(c->af_work);
+    HIPCHK(c, c->af_work.reserve(st, bytes, false));
+    double *wp = reinterpret_cast<double *>(c->af_work.p);
     a.BEST = wp; wp += nR;
     a.xb1 = wp; wp += n_xb1;
     a.xb2 = wp; wp += n_xb2;
@@ -912,28 +892,28 @@ int qcqpmi_admm_run(qcqpmi_ctx *c, int phase1, int64_t num_iters, double tol, do
     const size_t nR = (size_t)n16 * Rpad;
     const bool unit = c->ad_unit && !c->ad_unit_off;      // unit bases: gather / scatter instead of the two consensus GEMMs
     const int zs2 = unit ? 1 : gemm_zsplit(KBn, ntiles, MBh);       // planes of S = W D
-    if ((rc = dev_alloc(c, &X0.p, nR))) return rc;
-    if ((rc = dev_alloc(c, &Z.p, nR))) return rc;
-    if ((rc = dev_alloc(c, &Zlast.p, nR))) return rc;
-    if ((rc = dev_alloc(c, &Znew.p, nR))) return rc;
-    if ((rc = dev_alloc(c, &Sp.p, nR * (size_t)zs2))) return rc;
-    if ((rc = dev_alloc(c, &Y.p, nR))) return rc;
-    if ((rc = dev_alloc(c, &BEST.p, nR))) return rc;
+    HIPCHK(c, X0.reserve(c->stream, nR));
+    HIPCHK(c, Z.reserve(c->stream, nR));
+    HIPCHK(c, Zlast.reserve(c->stream, nR));
+    HIPCHK(c, Znew.reserve(c->stream, nR));
+    HIPCHK(c, Sp.reserve(c->stream, nR * (size_t)zs2));
+    HIPCHK(c, Y.reserve(c->stream, nR));
+    HIPCHK(c, BEST.reserve(c->stream, nR));
     // ZQ = W^T Z has few rows in a reduced basis (m rp): split the contraction over n into planes the small secular kernel sums
     const int zs1 = unit ? 1 : (c->ad_lowrank && c->ad_rows <= 8) ? gemm_zsplit(MBh, ntiles, KBn) : 1;
-    if ((rc = dev_alloc(c, &ZQ.p, (size_t)Mh16 * Rpad * (size_t)zs1))) return rc;
-    if ((rc = dev_alloc(c, &UH.p, (size_t)Mh16 * Rpad))) return rc;
-    if ((rc = dev_alloc(c, &dist2.p, Rpad))) return rc;
-    if ((rc = dev_alloc(c, &f0z.p, Rpad))) return rc;
-    if ((rc = dev_alloc(c, &bf0.p, Rpad))) return rc;
-    if ((rc = dev_alloc(c, &bmv.p, Rpad))) return rc;
-    if ((rc = dev_alloc(c, &fa.p, Rpad))) return rc;
-    if ((rc = dev_alloc(c, &mvb.p, Rpad))) return rc;
-    if ((rc = dev_alloc(c, &act.p, Rpad))) return rc;
-    if ((rc = dev_alloc(c, &pick.p, Rpad))) return rc;
-    if ((rc = dev_alloc(c, &it1.p, Rpad))) return rc;
-    if ((rc = dev_alloc(c, &it2.p, Rpad))) return rc;
-    if ((rc = dev_alloc(c, &nact.p, 8))) return rc;         // one counter of active restarts per iteration, eight iterations between two host reads
+    HIPCHK(c, ZQ.reserve(c->stream, (size_t)Mh16 * Rpad * (size_t)zs1));
+    HIPCHK(c, UH.reserve(c->stream, (size_t)Mh16 * Rpad));
+    HIPCHK(c, dist2.reserve(c->stream, Rpad));
+    HIPCHK(c, f0z.reserve(c->stream, Rpad));
+    HIPCHK(c, bf0.reserve(c->stream, Rpad));
+    HIPCHK(c, bmv.reserve(c->stream, Rpad));
+    HIPCHK(c, fa.reserve(c->stream, Rpad));
+    HIPCHK(c, mvb.reserve(c->stream, Rpad));
+    HIPCHK(c, act.reserve(c->stream, Rpad));
+    HIPCHK(c, pick.reserve(c->stream, Rpad));
+    HIPCHK(c, it1.reserve(c->stream, Rpad));
+    HIPCHK(c, it2.reserve(c->stream, Rpad));
+    HIPCHK(c, nact.reserve(c->stream, 8));         // one counter of active restarts per iteration, eight iterations between two host reads
     // ---- the z-solve (qcqp.py:224-227, 231-232): (2 (P0 + rho m I))^-1 given by the host, packed for the GEMM -- or, for a
     // diagonal P0, formed right here
     const bool diag = !Minv && !dev_minv;
@@ -943,18 +923,17 @@ int qcqpmi_admm_run(qcqpmi_ctx *c, int phase1, int64_t num_iters, double tol, do
     } else if (diag) {
         std::vector<double> dv((size_t)n16, 0.0), pd((size_t)n16, 0.0);
         for (int64_t j = 0; j < n; j++) { pd[(size_t)j] = c->p0_diag_host[(size_t)j]; dv[(size_t)j] = 1.0 / (2.0 * (pd[(size_t)j] + rho * (double)m)); }
-        if ((rc = dev_alloc(c, &dinv.p, (size_t)n16, false))) return rc;
-        if ((rc = dev_alloc(c, &pdiag.p, (size_t)n16, false))) return rc;
+        HIPCHK(c, dinv.reserve(c->stream, (size_t)n16, false));
+        HIPCHK(c, pdiag.reserve(c->stream, (size_t)n16, false));
         HIPCHK(c, hipMemcpyAsync(dinv.p, dv.data(), (size_t)n16 * sizeof(double), hipMemcpyHostToDevice, st));
         HIPCHK(c, hipMemcpyAsync(pdiag.p, pd.data(), (size_t)n16 * sizeof(double), hipMemcpyHostToDevice, st));
         HIPCHK(c, spin_sync(st));
     } else {
         DevBuf<double> tmp;
-        if ((rc = dev_alloc(c, &tmp.p, (size_t)n * n, false))) return rc;
+        HIPCHK(c, tmp.reserve(c->stream, (size_t)n * n, false));
         HIPCHK(c, hipMemcpyAsync(tmp.p, Minv, (size_t)n * n * sizeof(double), hipMemcpyHostToDevice, st));
-        if (c->ad_Minvpk) { (void)hipFree(c->ad_Minvpk); c->ad_Minvpk = nullptr; }
         c->ad_Minv_device = false;
-        if ((rc = dev_alloc(c, &c->ad_Minvpk, (size_t)n16 * n16, false))) return rc;
+        HIPCHK(c, c->ad_Minvpk.reserve(c->stream, (size_t)n16 * n16, false));
         const int64_t tot = n16 * n16;
         hipLaunchKernelGGL(gemm_pk_pack_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, (const double *)tmp.p, c->ad_Minvpk, n, n, n, (int64_t)1, KBn, KBn);
         HIPCHK(c, hipGetLastError());

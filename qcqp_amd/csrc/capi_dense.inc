@@ -18,10 +18,12 @@ DenseProblem dense_problem(const qcqpmi_ctx *c) {
 int dense_build(qcqpmi_ctx *c, const std::vector<double> &gq, const std::vector<double> &gr, const std::vector<int> &grel) {
     const int64_t n = c->n, n16 = c->n16, m1 = c->m + 1;
     int rc;
-    double *gp = c->dn_gp_pre;      // streaming upload: the constraint matrices are packed already (qcqpmi_set_quad)
-    c->dn_gp_pre = nullptr;
-    if (!gp && (rc = dev_alloc(c, &gp, (size_t)m1 * n16 * n16, false))) return rc;
-    c->prob_allocs.push_back(gp);
+    double *gp = nullptr;
+    if (c->dn_gp_pre) {             // streaming upload: the constraint matrices are packed already (qcqpmi_set_quad)
+        const size_t bytes = c->dn_gp_pre.cap * sizeof(double);
+        gp = c->dn_gp_pre.take();
+        c->prob_allocs.emplace_back((char *)gp, bytes);
+    } else if ((rc = prob_alloc(c, &gp, (size_t)m1 * n16 * n16))) return rc;
     const int64_t total = n16 * n16;
     const unsigned pb = (unsigned)((total + 255) / 256);
     // function 0 from the row-major P0 (uploaded or generated), the others from gP or from the generator
@@ -37,7 +39,7 @@ int dense_build(qcqpmi_ctx *c, const std::vector<double> &gq, const std::vector<
             // streaming mode (no row-major copy of the constraint matrices exists) and this function was not streamed by
             // qcqpmi_set_quad because it touches a single coordinate (a box constraint x_i^2 <= 1 among coupled ones) or
             // none: pack it now from the host triplets through the staging buffer
-            if (!c->dn_tmp && (rc = dev_alloc(c, &c->dn_tmp, (size_t)n * n, false))) return rc;
+            HIPCHK(c, c->dn_tmp.reserve(c->stream, (size_t)n * n, false));
             std::vector<double> dense((size_t)n * n, 0.0);
             for (size_t e = 0; e < h.cv.size(); e++) dense[(size_t)h.ci[e] * n + h.cj[e]] += h.cv[e];
             HIPCHK(c, hipMemcpyAsync(c->dn_tmp, dense.data(), (size_t)n * n * sizeof(double), hipMemcpyHostToDevice, c->stream));
@@ -68,18 +70,13 @@ int dense_build(qcqpmi_ctx *c, const std::vector<double> &gq, const std::vector<
     if ((rc = prob_upload(c, &tr, r))) return rc;
     if ((rc = prob_upload(c, &trel, rel))) return rc;
     HIPCHK(c, spin_sync(c->stream));
+    c->dn_tmp.release();      // no function arrives after finalize
     c->dn_Gpack = gp; c->dn_q = tq; c->dn_qT = tqT; c->dn_r = tr; c->dn_relop = trel;
     return 0;
 }
 
 int ensure_F(qcqpmi_ctx *c) {
-    const int64_t need = (c->m + 1) * c->Rpad;
-    if (need > c->F_cap) {
-        if (c->d_F) { HIPCHK(c, spin_sync(c->stream)); (void)hipFree(c->d_F); c->d_F = nullptr; }
-        int rc = dev_alloc(c, &c->d_F, need);
-        if (rc) return rc;
-        c->F_cap = need;
-    }
+    HIPCHK(c, c->d_F.reserve(c->stream, (size_t)((c->m + 1) * c->Rpad)));
     return 0;
 }
 
@@ -108,13 +105,7 @@ int launch_eval_dense(qcqpmi_ctx *c, bool with_Ft) {
     a.D = dense_problem(c);
     a.ntiles = (int)(c->Rpad / 16);
     a.zs = dense_zsplit(a.D.m1, a.ntiles, a.D.NB);
-    const int64_t need = (int64_t)(a.zs + 1) * (c->m + 1) * c->Rpad;   // partial planes + the linear terms
-    if (need > c->F_cap) {
-        if (c->d_F) { HIPCHK(c, spin_sync(c->stream)); (void)hipFree(c->d_F); c->d_F = nullptr; }
-        int rc = dev_alloc(c, &c->d_F, need);
-        if (rc) return rc;
-        c->F_cap = need;
-    }
+    HIPCHK(c, c->d_F.reserve(c->stream, (size_t)((int64_t)(a.zs + 1) * (c->m + 1) * c->Rpad)));   // partial planes + the linear terms
     a.X = c->X; a.b = 0; a.G = nullptr; a.F = c->d_F; a.Rpad = c->Rpad; a.tile_on = nullptr;
     a.hole = -1; a.ch_only = -1; a.zplane = 0;
     auto k = dense_products_kernel<1>;
@@ -141,13 +132,7 @@ int eval_parts_dense(qcqpmi_ctx *c) {
     a.ntiles = (int)(c->Rpad / 16);
     a.zs = dense_zsplit(a.D.m1, a.ntiles, a.D.NB);
     c->eval_zs = a.zs;
-    const int64_t need = (int64_t)(a.zs + 1) * (c->m + 1) * c->Rpad;
-    if (need > c->F_cap) {
-        if (c->d_F) { HIPCHK(c, spin_sync(c->stream)); (void)hipFree(c->d_F); c->d_F = nullptr; }
-        int rc = dev_alloc(c, &c->d_F, need);
-        if (rc) return rc;
-        c->F_cap = need;
-    }
+    HIPCHK(c, c->d_F.reserve(c->stream, (size_t)((int64_t)(a.zs + 1) * (c->m + 1) * c->Rpad)));
     a.X = c->X; a.b = 0; a.G = nullptr; a.F = c->d_F; a.Rpad = c->Rpad; a.tile_on = nullptr;
     a.hole = -1; a.ch_only = -1; a.zplane = 0;
     auto k = dense_products_kernel<1>;
@@ -165,45 +150,27 @@ int eval_parts_dense(qcqpmi_ctx *c) {
 
 int dense_reserve(qcqpmi_ctx *c) {
     const int64_t ntiles = c->Rpad / 16, m1 = c->m + 1, m1p = (m1 + 63) / 64 * 64;
-    int rc;
     // two buffers (block b is read while b+1 is produced), each: K-split planes + the fix-up plane
     const int64_t gneed = 2 * (int64_t)(dense_zsplit((int)m1, (int)ntiles, (int)(c->n16 / 16)) + 1) * ntiles * 256 * m1p;
-    if (gneed > c->dn_G_cap) {
-        HIPCHK(c, spin_sync(c->stream));
-        if (c->dn_G) (void)hipFree(c->dn_G);
-        if (c->dn_Ft) (void)hipFree(c->dn_Ft);
-        c->dn_G = c->dn_Ft = nullptr;
-        if ((rc = dev_alloc(c, &c->dn_G, (size_t)gneed, false))) return rc;
-        if ((rc = dev_alloc(c, &c->dn_Ft, (size_t)(c->Rpad * m1p)))) return rc;
-        c->dn_G_cap = gneed;
-    }
-    if (!c->dn_Dg && (rc = dev_alloc(c, &c->dn_Dg, (size_t)m1p * 512))) return rc;
-    if (c->profile && !c->dn_prof) {
-        HIPCHK(c, hipMalloc((void **)&c->dn_prof, 64 * sizeof(long long)));
-        HIPCHK(c, hipMemset(c->dn_prof, 0, 64 * sizeof(long long)));
-    }
+    HIPCHK(c, c->dn_G.reserve(c->stream, (size_t)gneed, false));
+    HIPCHK(c, c->dn_Ft.reserve(c->stream, (size_t)(c->Rpad * m1p)));
+    HIPCHK(c, c->dn_Dg.reserve(c->stream, (size_t)m1p * 512));
+    if (c->profile) HIPCHK(c, c->dn_prof.reserve(c->stream, 64));      // (zeroed once; qcqpmi_debug_dense_profile reads and clears)
     if (!c->stream2) {
         HIPCHK(c, hipStreamCreateWithFlags(&c->stream2, hipStreamNonBlocking));
         for (auto &e : c->dn_ev) HIPCHK(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
         for (auto &e : c->dn_evn) HIPCHK(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        HIPCHK(c, hipHostMalloc((void **)&c->dn_hn, 2 * sizeof(int), hipHostMallocDefault));
     }
-    if (c->Rpad > c->dn_state_cap) {
-        HIPCHK(c, spin_sync(c->stream));
-        if (c->dn_state) (void)hipFree(c->dn_state);
-        c->dn_state = nullptr;
-        // upd, viol_last (8 B each) + live, on, tile_on (1 B each) + nlive
-        const size_t bytes = (size_t)c->Rpad * (8 + 8 + 1 + 1 + 1) + 64;
-        HIPCHK(c, hipMalloc(&c->dn_state, bytes));
-        c->dn_state_cap = c->Rpad;
-    }
+    HIPCHK(c, c->dn_hn.reserve(c->stream, 2, false));
+    // upd, viol_last (8 B each) + live, on, tile_on (1 B each) + nlive
+    HIPCHK(c, c->dn_state.reserve(c->stream, (size_t)c->Rpad * (8 + 8 + 1 + 1 + 1) + 64, false));
     return 0;
 }
 
 DenseState dense_state(qcqpmi_ctx *c, bool phase1) {
     DenseState S;
-    char *p = (char *)c->dn_state;
-    const size_t Rp = (size_t)c->dn_state_cap;
+    char *p = c->dn_state;
+    const size_t Rp = (size_t)c->Rpad;      // (every phase lays the buffer out afresh: dense_state_init_kernel)
     S.upd = (int64_t *)p; p += Rp * 8;
     S.viol_last = (double *)p; p += Rp * 8;
     S.nlive = (int *)p; p += 64;

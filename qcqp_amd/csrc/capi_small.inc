@@ -11,18 +11,6 @@ struct Carve {
     size_t take(size_t bytes) { const size_t o = off; off += (bytes + 255) / 256 * 256; return o; }
 };
 
-// a device buffer that only grows: at least `bytes` behind *ptr afterwards (what it held is dropped when it has to move)
-template <typename T>
-int grow_device_buffer(qcqpmi_ctx *c, T **ptr, size_t *cap, size_t bytes) {
-    if (bytes <= *cap) return 0;
-    HIPCHK(c, spin_sync(c->stream));
-    if (*ptr) (void)hipFree(*ptr);
-    *ptr = nullptr; *cap = 0;
-    HIPCHK(c, hipMalloc((void **)ptr, bytes));
-    *cap = bytes;
-    return 0;
-}
-
 // host -> work buffer; a missing array or an empty piece is skipped
 int stage_in(qcqpmi_ctx *c, void *dst, const void *src, size_t bytes) {
     if (src && bytes) HIPCHK(c, hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, c->stream));
@@ -148,7 +136,7 @@ int cd_small_batch(qcqpmi_ctx *c, int64_t maxn, bool per_problem, const double *
     const BatchBest best = {cv.take((size_t)B * 2 * sizeof(int64_t)), cv.take((size_t)B * 2 * sizeof(double)), cv.take((size_t)B * n * 8),
                             best_index, best_f0, best_maxviol, best_x};
     const size_t ocons = cv.take(cons ? (size_t)B * m * 24 : 0);
-    if ((rc = grow_device_buffer(c, &c->sb_work, &c->sb_work_cap, cv.off))) return rc;
+    HIPCHK(c, c->sb_work.reserve(c->stream, cv.off, false));
     char *w = c->sb_work;
     if ((rc = stage_in(c, w + oP, P0s, (size_t)B * n * n * 8)) || (rc = stage_in(c, w + oq, q0s, (size_t)B * n * 8)) ||
         (rc = stage_in(c, w + or0, r0s, (size_t)B * 8)) || (rc = stage_in(c, w + oX0, generate ? nullptr : X0, (size_t)T * n * 8)) ||
@@ -223,7 +211,7 @@ int sdr_small_batch(qcqpmi_ctx *c, bool per_problem, const double *ds, int64_t B
     const size_t oV0 = cv.take(V0s ? vbytes : 0), oV = cv.take(vbytes);
     const size_t opr = cv.take((size_t)B * 8), oy = cv.take((size_t)B * N * 8), osw = cv.take((size_t)B * 8), oX = cv.take((size_t)B * S * n * 8);
     const size_t oticket = cv.take(2 * sizeof(int));
-    if ((rc = grow_device_buffer(c, &c->ss_work, &c->ss_work_cap, cv.off))) return rc;
+    HIPCHK(c, c->ss_work.reserve(c->stream, cv.off, false));
     char *w = c->ss_work;
     std::vector<double> sv((size_t)ns);
     for (int64_t i = 0; i < ns; i++) sv[(size_t)i] = sqrt(ds ? ds[i] : c->unit_d[(size_t)i]);
@@ -321,7 +309,7 @@ int qcqpmi_admm_small_batch_run(qcqpmi_ctx *c, int64_t B, const double *P0s, con
     const BatchBest best = {cv.take((size_t)B * 2 * sizeof(int64_t)), cv.take((size_t)B * 2 * sizeof(double)), cv.take((size_t)B * n * 8),
                             best_index, best_f0, best_maxviol, best_x};
     const size_t ocons = cv.take(cons ? (size_t)B * m * 24 : 0);
-    if ((rc = grow_device_buffer(c, &c->sb_work, &c->sb_work_cap, cv.off))) return rc;
+    HIPCHK(c, c->sb_work.reserve(c->stream, cv.off, false));
     char *w = c->sb_work;
     if ((rc = stage_in(c, w + oP, P0s, (size_t)B * n * n * 8)) || (rc = stage_in(c, w + oM, Minvs, (size_t)B * n * n * 8)) ||
         (rc = stage_in(c, w + oq, q0s, (size_t)B * n * 8)) || (rc = stage_in(c, w + or0, r0s, (size_t)B * 8)) ||

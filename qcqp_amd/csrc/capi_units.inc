@@ -75,20 +75,13 @@ __global__ void unit_onevar_coeffs_kernel(DevProblem P, const double *__restrict
     out[3 * t] = t2; out[3 * t + 1] = t1; out[3 * t + 2] = t0;
 }
 
-struct UnitBufs {   // scoped device buffers of one unit call
-    std::vector<void *> p;
-    ~UnitBufs() { for (void *q : p) if (q) (void)hipFree(q); }
-    template <typename T>
-    hipError_t up(T **dst, const T *src, size_t cnt) {
-        void *v = nullptr;
-        hipError_t e = hipMalloc(&v, std::max<size_t>(cnt, 1) * sizeof(T));
-        if (e != hipSuccess) return e;
-        p.push_back(v);
-        *dst = (T *)v;
-        if (src) e = hipMemcpy(v, src, cnt * sizeof(T), hipMemcpyHostToDevice);
-        return e;
-    }
-};
+// a scoped device buffer of one unit call: cnt elements, filled from src when there is one (the null stream: these calls have no context)
+template <typename T>
+hipError_t unit_up(DevBuf<T> &b, const T *src, size_t cnt) {
+    hipError_t e = b.reserve(nullptr, cnt, false);
+    if (e == hipSuccess && src) e = hipMemcpy(b.p, src, cnt * sizeof(T), hipMemcpyHostToDevice);
+    return e;
+}
 
 #define UNITCHK(expr)                                                                                   \
     do {                                                                                                \
@@ -109,19 +102,18 @@ int qcqpmi_onevar_coeffs(qcqpmi_ctx *c, const int64_t *coord, double *out) {
     for (int64_t r = 0; r < c->R; r++)
         if (coord[r] < 0 || coord[r] >= c->n) return fail(c, QCQPMI_EINVAL, "onevar_coeffs: coordinate %lld of restart %lld", (long long)coord[r], (long long)r);
     HIPCHK(c, hipSetDevice(c->device));
-    UnitBufs B;
-    int64_t *dcoord = nullptr;
-    double *dout = nullptr;
+    DevBuf<int64_t> dcoord;
+    DevBuf<double> dout;
     const size_t cnt = (size_t)c->R * (size_t)(c->m + 1) * 3;
-    UNITCHK(B.up(&dcoord, coord, (size_t)c->R));
-    UNITCHK(B.up(&dout, (const double *)nullptr, cnt));
+    UNITCHK(unit_up(dcoord, coord, (size_t)c->R));
+    UNITCHK(unit_up(dout, (const double *)nullptr, cnt));
     HIPCHK(c, spin_sync(c->stream));
     const int64_t tot = c->R * (c->m + 1);
     hipLaunchKernelGGL(unit_onevar_coeffs_kernel, dim3((unsigned)((tot + 127) / 128)), dim3(128), 0, c->stream, c->dp,
-                       (const double *)c->d_gP, (const double *)c->X, c->R, (const int64_t *)dcoord, dout);
+                       (const double *)c->d_gP, (const double *)c->X, c->R, (const int64_t *)dcoord.p, dout.p);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, spin_sync(c->stream));
-    HIPCHK(c, hipMemcpy(out, dout, cnt * sizeof(double), hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(out, dout.p, cnt * sizeof(double), hipMemcpyDeviceToHost));
     return 0;
 }
 
@@ -129,15 +121,14 @@ int qcqpmi_feasible_intervals_batch(int device, int64_t count, const double *pqr
     if (count <= 0 || !pqrs || !relop || !out) return fail(nullptr, QCQPMI_EINVAL, "feasible_intervals_batch: bad arguments");
     if (qcqpmi_device_count() <= 0) return fail(nullptr, QCQPMI_EHIP, "no HIP device visible (there is no CPU fallback)");
     UNITCHK(hipSetDevice(device));
-    UnitBufs B;
-    double *dp = nullptr, *dout = nullptr;
-    int *dr = nullptr;
-    UNITCHK(B.up(&dp, pqrs, (size_t)count * 4));
-    UNITCHK(B.up(&dr, relop, (size_t)count));
-    UNITCHK(B.up(&dout, (const double *)nullptr, (size_t)count * 5));
-    hipLaunchKernelGGL(unit_intervals_kernel, dim3((unsigned)((count + 127) / 128)), dim3(128), 0, 0, count, dp, dr, dout);
+    DevBuf<double> dp, dout;
+    DevBuf<int> dr;
+    UNITCHK(unit_up(dp, pqrs, (size_t)count * 4));
+    UNITCHK(unit_up(dr, relop, (size_t)count));
+    UNITCHK(unit_up(dout, (const double *)nullptr, (size_t)count * 5));
+    hipLaunchKernelGGL(unit_intervals_kernel, dim3((unsigned)((count + 127) / 128)), dim3(128), 0, 0, count, dp.p, dr.p, dout.p);
     UNITCHK(hipGetLastError());
-    UNITCHK(hipMemcpy(out, dout, (size_t)count * 5 * sizeof(double), hipMemcpyDeviceToHost));
+    UNITCHK(hipMemcpy(out, dout.p, (size_t)count * 5 * sizeof(double), hipMemcpyDeviceToHost));
     return 0;
 }
 
@@ -148,24 +139,23 @@ int qcqpmi_onevar_qcqp_batch(int device, int64_t count, const double *f0, const 
         if (nf[i] < 0 || nf[i] > UNIT_MAXC) return fail(nullptr, QCQPMI_EUNSUPPORTED, "onevar_qcqp_batch: at most %d constraints per case", UNIT_MAXC);
     if (qcqpmi_device_count() <= 0) return fail(nullptr, QCQPMI_EHIP, "no HIP device visible (there is no CPU fallback)");
     UNITCHK(hipSetDevice(device));
-    UnitBufs B;
-    double *df0 = nullptr, *dfs = nullptr, *ds = nullptr, *dx = nullptr, *dC = nullptr;
-    int *dnf = nullptr, *dst = nullptr, *dnC = nullptr;
-    UNITCHK(B.up(&df0, f0, (size_t)count * 3));
-    UNITCHK(B.up(&dfs, fs, (size_t)count * UNIT_MAXC * 4));
-    UNITCHK(B.up(&dnf, nf, (size_t)count));
-    UNITCHK(B.up(&ds, s, (size_t)count));
-    UNITCHK(B.up(&dx, (const double *)nullptr, (size_t)count));
-    UNITCHK(B.up(&dst, (const int *)nullptr, (size_t)count));
-    UNITCHK(B.up(&dC, (const double *)nullptr, (size_t)count * (UNIT_MAXC + 1) * 2));
-    UNITCHK(B.up(&dnC, (const int *)nullptr, (size_t)count));
-    hipLaunchKernelGGL(unit_onevar_kernel, dim3((unsigned)((count + 63) / 64)), dim3(64), 0, 0, count, df0, dfs, dnf, ds, seed, dx,
-                       dst, dC, dnC);
+    DevBuf<double> df0, dfs, ds, dx, dC;
+    DevBuf<int> dnf, dst, dnC;
+    UNITCHK(unit_up(df0, f0, (size_t)count * 3));
+    UNITCHK(unit_up(dfs, fs, (size_t)count * UNIT_MAXC * 4));
+    UNITCHK(unit_up(dnf, nf, (size_t)count));
+    UNITCHK(unit_up(ds, s, (size_t)count));
+    UNITCHK(unit_up(dx, (const double *)nullptr, (size_t)count));
+    UNITCHK(unit_up(dst, (const int *)nullptr, (size_t)count));
+    UNITCHK(unit_up(dC, (const double *)nullptr, (size_t)count * (UNIT_MAXC + 1) * 2));
+    UNITCHK(unit_up(dnC, (const int *)nullptr, (size_t)count));
+    hipLaunchKernelGGL(unit_onevar_kernel, dim3((unsigned)((count + 63) / 64)), dim3(64), 0, 0, count, df0.p, dfs.p, dnf.p, ds.p, seed, dx.p,
+                       dst.p, dC.p, dnC.p);
     UNITCHK(hipGetLastError());
-    UNITCHK(hipMemcpy(x, dx, (size_t)count * sizeof(double), hipMemcpyDeviceToHost));
-    UNITCHK(hipMemcpy(status, dst, (size_t)count * sizeof(int), hipMemcpyDeviceToHost));
-    if (C_out) UNITCHK(hipMemcpy(C_out, dC, (size_t)count * (UNIT_MAXC + 1) * 2 * sizeof(double), hipMemcpyDeviceToHost));
-    if (nC_out) UNITCHK(hipMemcpy(nC_out, dnC, (size_t)count * sizeof(int), hipMemcpyDeviceToHost));
+    UNITCHK(hipMemcpy(x, dx.p, (size_t)count * sizeof(double), hipMemcpyDeviceToHost));
+    UNITCHK(hipMemcpy(status, dst.p, (size_t)count * sizeof(int), hipMemcpyDeviceToHost));
+    if (C_out) UNITCHK(hipMemcpy(C_out, dC.p, (size_t)count * (UNIT_MAXC + 1) * 2 * sizeof(double), hipMemcpyDeviceToHost));
+    if (nC_out) UNITCHK(hipMemcpy(nC_out, dnC.p, (size_t)count * sizeof(int), hipMemcpyDeviceToHost));
     return 0;
 }
 

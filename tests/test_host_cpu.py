@@ -943,3 +943,38 @@ def test_multi_class_families_are_what_the_kinds_take_and_the_oracle_solves_them
         x0 = orc.keyed_normal_matrix(7, n, 1, first_index=3)[:, 0]
         x, s1, s2 = prob.improve_cd(x0, num_iters=200, rng=rng)
         assert prob.max_violation(x) < 1e-2, (fam, prob.max_violation(x))
+
+
+def test_device_memory_is_allocated_and_freed_in_one_place():
+    """Every buffer of the C ABI's host side is a DevBuf / PinBuf (csrc/dev_buf.h): the runtime's allocation and free calls occur
+    in that header only, and the helpers it replaced are gone.  (Hand-kept free lists had missed three buffers, and every
+    open-coded growth site kept its own copy of the wait / free / null / allocate / set-capacity rule.)"""
+    from qcqp_amd import _build
+    text = {f: open(os.path.join(_build.SRC, f)).read() for f in os.listdir(_build.SRC) if f.endswith(('.hip', '.h', '.inc'))}
+    assert 'dev_buf.h' in text
+    call = re.compile(r'\b(hipMalloc\w*|hipFree\w*|hipHostMalloc|hipHostFree|hipHostAlloc|hipMallocAsync|hipFreeAsync)\s*\(')
+    where = sorted(f for f, t in text.items() if call.search(t))
+    assert where == ['dev_buf.h'], where
+    gone = re.compile(r'\b(dev_alloc|grow_device_buffer)\b')
+    assert not sorted(f for f, t in text.items() if gone.search(t))
+    # one definition of the owning type and of the wait it needs before a free
+    assert [f for f, t in text.items() if re.search(r'^struct DevBuf\b', t, re.M)] == ['dev_buf.h']
+    assert [f for f, t in text.items() if re.search(r'^(?:inline )?hipError_t spin_sync\(', t, re.M)] == ['dev_buf.h']
+
+
+def test_dev_buf_selftest_under_sanitizers(tmp_path):
+    """tests/host/dev_buf_selftest.cpp: dev_buf.h against a stand-in runtime that counts live blocks, aborts on a double free and can
+    refuse an allocation -- no-op when the capacity suffices, growth frees the old block, a failed growth leaves {nullptr, 0} and a
+    later smaller request allocates again, take() hands the block over without freeing, nothing is live after destruction.  Host
+    compiler, AddressSanitizer + UBSan; not linked against the HIP runtime."""
+    import shutil
+    cxx = os.environ.get('CXX') or shutil.which('g++') or shutil.which('clang++')
+    inc = '/opt/rocm/include'
+    if not cxx or not os.path.exists(os.path.join(inc, 'hip', 'hip_runtime_api.h')):
+        pytest.skip('no host compiler / HIP headers')
+    exe = str(tmp_path / 'dev_buf_selftest')
+    p = subprocess.run([cxx, '-std=c++17', '-D__HIP_PLATFORM_AMD__', '-I' + inc, '-fsanitize=address,undefined', '-o', exe,
+                        os.path.join(REPO, 'tests', 'host', 'dev_buf_selftest.cpp')], stdout=subprocess.PIPE, stderr=subprocess.STDOUT)
+    assert p.returncode == 0, p.stdout.decode()
+    r = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT)
+    assert r.returncode == 0 and r.stdout.decode().strip() == 'ok', r.stdout.decode()
