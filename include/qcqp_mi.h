@@ -478,6 +478,28 @@ int qcqpmi_admm_small_batch_run(qcqpmi_ctx *ctx, int64_t B, const double *P0s, c
                                 int64_t num_iters, double tol, double viol_lim, uint64_t seed, uint64_t seed_stride,
                                 uint64_t first_index, double select_tol, int64_t *iters1, int64_t *iters2, double *f0, double *maxviol,
                                 double *X, int64_t *best_index, double *best_f0, double *best_maxviol, double *best_x);
+/* IMPROVE(ADMM) FOR PROBLEMS OF UP TO 128 VARIABLES (added within ABI 6: a new symbol, nothing else changes).  The arguments of
+ * qcqpmi_admm_small_batch_run, 1 <= n <= 128.
+ * n <= 64: exactly the launch of qcqpmi_admm_small_batch_run -- the same kernel, the same bits, the same name in qcqpmi_last_admm_kernel.
+ * 65 <= n <= 128: the WIDE kernels admm_small_kernel<MAXC, pc, 2> -- one wavefront per (problem, restart) as before, lane l holds the
+ * coordinates l and l + 64 (the second one where l + 64 < n), each with its z, its duals, its operand sum and its constraint list; the
+ * keyed starts go by the coordinate index.  z = Minv_b rhs is summed over k = 0 .. n-1 ascending with rhs_k read from slot k >> 6 at
+ * lane k & 63; the sums over the coordinates (f0 of an iterate, |last_z - z|^2) add the lane's two slots first and then run the tree over
+ * the lanes; the objective through P0_b keeps its ascending sums across both slots.  The LDS image is the same -- Minv_b row-major
+ * n x n, q0_b, the [3][m] coefficients with cons, two control words: (n^2 + n + 3 m) 8 + 8 bytes, 132 104 at n = 128 without cons, at most
+ * 144 392 of the 160 KB of a CU; P0_b stays in global memory.  Workgroups of 256 or 512 threads, whichever holds more waves on a CU.
+ * A 64 x 64 QPSK MIMO frame (128 real variables) is the example.
+ * PARITY: that of qcqpmi_admm_small_batch_run, unchanged -- 1e-9 against the reference for a few iterations per phase; a result depends
+ * on (problem b, rho_b, Minv_b, seed of b, global index) alone: bit for bit; with cons, restart (b, r) is bit for bit the restart of the
+ * call with B = 1, cons == NULL on a context created from problem b's own functions.
+ * qcqpmi_last_admm_kernel for n > 64: "admm_small_kernel<1,w2>" / "<4,w2>" / "<1,pc,w2>" / "<4,pc,w2>".
+ * Refusals, the resident population and qcqpmi_last_cd_kernel left alone.  QCQPMI_EUNSUPPORTED: n > 128, constraints that are not
+ * separable.  QCQPMI_EINVAL: everything qcqpmi_admm_small_batch_run refuses with it. */
+int qcqpmi_admm_batch_run(qcqpmi_ctx *ctx, int64_t B, const double *P0s, const double *q0s, const double *r0s, const double *cons,
+                          const double *rhos, const double *Minvs, int64_t R, int generate, const double *X0, int phase1,
+                          int64_t num_iters, double tol, double viol_lim, uint64_t seed, uint64_t seed_stride, uint64_t first_index,
+                          double select_tol, int64_t *iters1, int64_t *iters2, double *f0, double *maxviol, double *X,
+                          int64_t *best_index, double *best_f0, double *best_maxviol, double *best_x);
 /* Device and pinned-host buffers for a qcqpmi_cd_stream_run(K, R) to come (population, per-restart outputs, per-population
  * winners; with an objective factor set, the buffers of the factored kernel's pre-passes: slacks and Y0 = L^T x0): allocation only, so that a timed or latency-sensitive run does not start with hipMalloc / hipHostMalloc.  A
  * resident population smaller than K R points is dropped (like any reallocation of the population). */

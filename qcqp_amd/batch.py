@@ -4,8 +4,9 @@ A frame of MIMO detection problems is thousands of independent Boolean least squ
 instance has its own objective and all of them the constraints x_i^2 == 1.  ``QCQP`` holds one problem per context; this class
 holds B of them on ONE context and runs suggest(RANDOM) + improve(COORD_DESCENT) for all B x R restarts through one persistent
 kernel (``Engine.cd_small_batch_run``, qcqpmi_cd_small_batch_run; for 64 < n <= 128 ``Engine.cd_batch_run``, qcqpmi_cd_batch_run: the
-wide kernels, two coordinates per lane).  improve(ADMM) -- n <= 64 -- runs the reference's consensus ADMM for all B x R restarts in
-one launch too (``Engine.admm_small_batch_run``, qcqpmi_admm_small_batch_run), with rho per problem by the reference's rule and
+wide kernels, two coordinates per lane).  improve(ADMM) runs the reference's consensus ADMM for all B x R restarts in one launch too
+(n <= 64: ``Engine.admm_small_batch_run``, qcqpmi_admm_small_batch_run; 64 < n <= 128, asked for with wide=True:
+``Engine.admm_batch_run``, qcqpmi_admm_batch_run, wide kernels again), with rho per problem by the reference's rule and
 (2 (P0_b + rho_b m I))^-1 from one batched host inverse.  suggest(SDR) -- for constraints x_i^2 == d_i -- solves the
 semidefinite relaxation of all B problems and draws their samples in one launch as well (``Engine.sdr_small_batch``,
 qcqpmi_sdr_small_batch) and publishes the certified bounds in ``sdr_bound``; improve() then starts from the samples.  Problem b's results are those of
@@ -76,7 +77,7 @@ def _structure(funcs):
     return None if any(e is None for e in out) else out
 
 
-MAX_N = 128          # qcqpmi_cd_batch_run: two coordinates per lane
+MAX_N = 128          # qcqpmi_cd_batch_run, qcqpmi_admm_batch_run: two coordinates per lane
 MAX_N_SMALL = 64     # qcqpmi_cd_small_batch_run, qcqpmi_sdr_small_batch, qcqpmi_admm_small_batch_run: one coordinate per lane
 
 
@@ -197,19 +198,22 @@ class QCQPBatch(object):
             self._starts = None
         self._suggested = (int(num_samples), int(seed), int(first_index), int(seed_stride))
 
-    def improve(self, method=s.COORD_DESCENT, num_iters=1000, viol_tol=1e-2, tol=None, phase1=True, seed=None, viol_lim=1e4, rho=None):
+    def improve(self, method=s.COORD_DESCENT, num_iters=1000, viol_tol=1e-2, tol=None, phase1=True, seed=None, viol_lim=1e4, rho=None,
+                wide=False):
         """improve(COORD_DESCENT) or improve(ADMM) of every suggested start of every problem; returns (f (B,), v (B,)) of the best
         restart per problem (QCQPForm.better, ties -> lowest index) and sets .x (B, n), .population_f / .population_v (B, R),
         .best_index, .last_stats.  seed: the seed of suggest() (a problem's normals and its draws come from ONE keyed stream).
         COORD_DESCENT: num_iters, viol_tol, tol (1e-4), phase1.
-        ADMM (n <= 64): num_iters, tol (1e-2), viol_lim, rho, phase1 -- the arguments of the reference's improve_admm.  rho == None:
-        the reference's rule (qcqp.py:270-277) problem by problem; a given rho that is too small for some problem raises the
-        reference's message.  .last_stats holds rho (B,), iters1, iters2 (B, R) and the kernel's name."""
+        ADMM (n <= 64; n <= 128 with wide=True): num_iters, tol (1e-2), viol_lim, rho, phase1 -- the arguments of the reference's
+        improve_admm.  rho == None: the reference's rule (qcqp.py:270-277) problem by problem; a given rho that is too small for some
+        problem raises the reference's message.  .last_stats holds rho (B,), iters1, iters2 (B, R) and the kernel's name.
+        wide=True admits 65 <= n <= 128 to ADMM (``Engine.admm_batch_run``: the wide kernels, two coordinates per lane); n <= 64 runs
+        as without it.  The default refuses n > 64 as before.  COORD_DESCENT ignores it."""
         if method not in (s.COORD_DESCENT, s.ADMM):
             raise Exception("QCQPBatch.improve is defined for the COORD_DESCENT and ADMM methods")
-        if method == s.ADMM and self.n > MAX_N_SMALL:      # before any launch
-            raise Exception("QCQPBatch.improve(ADMM) is defined for n <= %d (n = %d): the batched kernel holds a point in one wavefront; "
-                            "use improve(COORD_DESCENT), or QCQP per problem" % (MAX_N_SMALL, self.n))
+        if method == s.ADMM and self.n > MAX_N_SMALL and not wide:      # before any launch
+            raise Exception("QCQPBatch.improve(ADMM) is defined for n <= %d (n = %d) unless wide=True is given (n <= %d: the wide kernels, "
+                            "two coordinates per lane); or use improve(COORD_DESCENT), or QCQP per problem" % (MAX_N_SMALL, self.n, MAX_N))
         if self._suggested is None:
             raise Exception("QCQPBatch.improve: call suggest(RANDOM or SDR, num_samples=R, seed=...) first")
         R, sd, first_index, stride = self._suggested
@@ -236,9 +240,9 @@ class QCQPBatch(object):
     def _improve_admm(self, R, sd, first_index, stride, num_iters, tol, viol_lim, rho, phase1):
         m = self.form.m
         rhos = admm_rhos(self.P0s, m, rho)
-        out = self.engine.admm_small_batch_run(self.P0s, self.q0s, self.r0s, R, rhos, admm_minvs(self.P0s, rhos, m), X0=self._starts,
-                                               phase1=phase1, num_iters=num_iters, tol=tol, viol_lim=viol_lim, seed=sd,
-                                               seed_stride=stride, first_index=first_index, want_x=False, cons=self.cons)
+        run = self.engine.admm_small_batch_run if self.n <= MAX_N_SMALL else self.engine.admm_batch_run
+        out = run(self.P0s, self.q0s, self.r0s, R, rhos, admm_minvs(self.P0s, rhos, m), X0=self._starts, phase1=phase1, num_iters=num_iters,
+                  tol=tol, viol_lim=viol_lim, seed=sd, seed_stride=stride, first_index=first_index, want_x=False, cons=self.cons)
         return self._publish(out, s.ADMM, R, rho=rhos, kernel=self.engine.last_admm_kernel()[0])
 
     def close(self):

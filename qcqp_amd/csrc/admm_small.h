@@ -8,6 +8,9 @@
 // admm_unit_step_kernel.  Restart (b, r) starts from the keyed normals (seed + b seed_stride, first_index + r) or from X0 and depends
 // on nothing but (problem b, rho_b, Minv_b, its start): not on B, the neighbours, the workgroups or the order in which the work is
 // dealt out.
+//
+// 64 < n <= 128 (qcqpmi_admm_batch_run): the wide kernels admm_small_kernel<MAXC, pc, 2> -- one wavefront per (problem,
+// restart) as before, two coordinates per lane, the same LDS image (up to 144 392 bytes), the same parity statement.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -17,6 +20,9 @@
 namespace qcqpmi {
 
 constexpr int ADMM_SMALL_MAXN = 64;      // lane = coordinate: one wavefront holds a point
+constexpr int ADMM_WIDE_MAXN = 128;      // the wide kernels (admm_small_kernel<MAXC, pc, 2>): lane l holds coordinates l and l + 64
+// their largest workgroup; the launch takes 256 or 512 threads, whichever puts more waves on a CU (admm_small_workgroups)
+constexpr int ADMM_WIDE_THREADS = 512;
 
 struct AdmmSmallArgs {
     DevProblem P;                // n, m and the per-coordinate constraint lists (cptr / cp / cq / cr / crel / cidx); its objective is not read
@@ -40,9 +46,11 @@ struct AdmmSmallArgs {
     double *X;                   // [B][R][n] final points
 };
 
-// workgroups of the launch (small_workgroup_cap; pc_entries: as small_image_bytes takes it), or < 0: -hipError_t
-int admm_small_workgroups(int64_t n, int maxc, int64_t pc_entries, int64_t tickets, int device);
-int admm_small_launch(const AdmmSmallArgs &a, int maxc, int wgs, hipStream_t st);      // a.cons != nullptr: the <MAXC, pc> kernels
-const char *admm_small_name(int maxc, bool pc);
+// workgroups of the launch (small_workgroup_cap; pc_entries: as small_image_bytes takes it), or < 0: -hipError_t; *threads: the size of a workgroup
+// -- 256 for n <= ADMM_SMALL_MAXN; for the wide kernels 256 or ADMM_WIDE_THREADS, whichever the occupancy query gives more resident
+// waves (a tie goes to the larger one)
+int admm_small_workgroups(int64_t n, int maxc, int64_t pc_entries, int64_t tickets, int device, int *threads);
+int admm_small_launch(const AdmmSmallArgs &a, int maxc, int wgs, int threads, hipStream_t st);      // a.cons != nullptr: the <MAXC, pc> kernels
+const char *admm_small_name(int maxc, bool pc, bool wide);
 
 }  // namespace qcqpmi

@@ -242,53 +242,18 @@ int sdr_small_batch(qcqpmi_ctx *c, bool per_problem, const double *ds, int64_t B
     return 0;
 }
 
-}  // namespace
-
-extern "C" {
-
-int qcqpmi_cd_small_batch_run(qcqpmi_ctx *c, int64_t B, const double *P0s, const double *q0s, const double *r0s, int64_t R, int generate,
-                              const double *X0, int phase1, int64_t num_iters, double viol_tol, double tol, uint64_t seed,
-                              uint64_t seed_stride, uint64_t first_index, double select_tol, int64_t *sweeps1, int64_t *sweeps2,
-                              int64_t *visits2, int64_t *accepted2, uint8_t *ran_phase2, int *status1, int *status2, double *f0,
-                              double *maxviol, double *X, int64_t *best_index, double *best_f0, double *best_maxviol, double *best_x) {
-    return cd_small_batch(c, CD_SMALL_MAXN, false, nullptr, B, P0s, q0s, r0s, R, generate, X0, phase1, num_iters, viol_tol, tol, seed, seed_stride, first_index,
-                          select_tol, sweeps1, sweeps2, visits2, accepted2, ran_phase2, status1, status2, f0, maxviol, X, best_index, best_f0,
-                          best_maxviol, best_x);
-}
-
-// ---- the same launch with PER-PROBLEM constraint coefficients cons [B][m][3]: the context fixes the structure (cd_small.h)
-int qcqpmi_cd_small_batch_run_pc(qcqpmi_ctx *c, int64_t B, const double *P0s, const double *q0s, const double *r0s, const double *cons,
-                                 int64_t R, int generate, const double *X0, int phase1, int64_t num_iters, double viol_tol, double tol,
-                                 uint64_t seed, uint64_t seed_stride, uint64_t first_index, double select_tol, int64_t *sweeps1,
-                                 int64_t *sweeps2, int64_t *visits2, int64_t *accepted2, uint8_t *ran_phase2, int *status1, int *status2,
-                                 double *f0, double *maxviol, double *X, int64_t *best_index, double *best_f0, double *best_maxviol,
-                                 double *best_x) {
-    return cd_small_batch(c, CD_SMALL_MAXN, true, cons, B, P0s, q0s, r0s, R, generate, X0, phase1, num_iters, viol_tol, tol, seed, seed_stride, first_index,
-                          select_tol, sweeps1, sweeps2, visits2, accepted2, ran_phase2, status1, status2, f0, maxviol, X, best_index, best_f0,
-                          best_maxviol, best_x);
-}
-
-// ---- the batch for 1 <= n <= 128: the two symbols above for n <= 64 (cons == NULL: shared constraints), the wide kernels past it
-int qcqpmi_cd_batch_run(qcqpmi_ctx *c, int64_t B, const double *P0s, const double *q0s, const double *r0s, const double *cons, int64_t R,
-                        int generate, const double *X0, int phase1, int64_t num_iters, double viol_tol, double tol, uint64_t seed,
-                        uint64_t seed_stride, uint64_t first_index, double select_tol, int64_t *sweeps1, int64_t *sweeps2, int64_t *visits2,
-                        int64_t *accepted2, uint8_t *ran_phase2, int *status1, int *status2, double *f0, double *maxviol, double *X,
-                        int64_t *best_index, double *best_f0, double *best_maxviol, double *best_x) {
-    return cd_small_batch(c, CD_WIDE_MAXN, cons != nullptr, cons, B, P0s, q0s, r0s, R, generate, X0, phase1, num_iters, viol_tol, tol, seed, seed_stride,
-                          first_index, select_tol, sweeps1, sweeps2, visits2, accepted2, ran_phase2, status1, status2, f0, maxviol, X, best_index,
-                          best_f0, best_maxviol, best_x);
-}
-
-// ---- improve(ADMM) for B small problems (n <= 64), R restarts each (admm_small.h); qcqpmi_last_cd_kernel is not touched either
-int qcqpmi_admm_small_batch_run(qcqpmi_ctx *c, int64_t B, const double *P0s, const double *q0s, const double *r0s, const double *cons,
-                                const double *rhos, const double *Minvs, int64_t R, int generate, const double *X0, int phase1,
-                                int64_t num_iters, double tol, double viol_lim, uint64_t seed, uint64_t seed_stride, uint64_t first_index,
-                                double select_tol, int64_t *iters1, int64_t *iters2, double *f0, double *maxviol, double *X,
-                                int64_t *best_index, double *best_f0, double *best_maxviol, double *best_x) {
+// ---- improve(ADMM), R restarts each (admm_small.h); qcqpmi_last_cd_kernel is not touched either.  maxn: ADMM_SMALL_MAXN, or ADMM_WIDE_MAXN
+// for qcqpmi_admm_batch_run, whose problems of more than ADMM_SMALL_MAXN variables run the wide kernels
+int admm_small_batch(qcqpmi_ctx *c, int64_t maxn, int64_t B, const double *P0s, const double *q0s, const double *r0s, const double *cons,
+                     const double *rhos, const double *Minvs, int64_t R, int generate, const double *X0, int phase1,
+                     int64_t num_iters, double tol, double viol_lim, uint64_t seed, uint64_t seed_stride, uint64_t first_index,
+                     double select_tol, int64_t *iters1, int64_t *iters2, double *f0, double *maxviol, double *X,
+                     int64_t *best_index, double *best_f0, double *best_maxviol, double *best_x) {
     const char *name = "admm_small_batch_run";
     int rc = check_batch_context(c, name);
     if (rc) return rc;
-    if (c->n > ADMM_SMALL_MAXN) return fail(c, QCQPMI_EUNSUPPORTED, "admm_small_batch_run: n = %lld, the small-problem kernel takes n <= %d (one lane per coordinate)", (long long)c->n, ADMM_SMALL_MAXN);
+    if (c->n > maxn) return fail(c, QCQPMI_EUNSUPPORTED, "admm_small_batch_run: n = %lld, the small-problem kernel takes n <= %lld (%s)", (long long)c->n, (long long)maxn,
+                                 maxn > ADMM_SMALL_MAXN ? "two coordinates per lane" : "one lane per coordinate");
     if (B < 1 || R < 1 || num_iters < 0 || !P0s || !q0s || !r0s || !rhos || !Minvs || (!generate && !X0))
         return fail(c, QCQPMI_EINVAL, "admm_small_batch_run: bad B / R / num_iters, or a missing input array");
     if ((rc = check_batch_count(c, name, B, R))) return rc;
@@ -330,13 +295,14 @@ int qcqpmi_admm_small_batch_run(qcqpmi_ctx *c, int64_t B, const double *P0s, con
     a.iters1 = (int64_t *)o; a.iters2 = (int64_t *)(o + 8 * T); a.f0 = (double *)(o + 16 * T); a.maxviol = (double *)(o + 24 * T);
     a.X = (double *)(w + oX);
     const int maxc = c->maxc <= 1 ? 1 : 4;
-    const int cap = admm_small_workgroups(n, maxc, cons ? m : 0, B * R, c->device);
+    int threads = 0;
+    const int cap = admm_small_workgroups(n, maxc, cons ? m : 0, B * R, c->device, &threads);
     if (cap < 1) return fail(c, QCQPMI_EHIP, "admm_small_batch_run: occupancy query failed: %s", hipGetErrorString((hipError_t)(-cap)));
-    const TicketPlan plan = ticket_partition(B, R, cap, 4);      // workgroups of four waves
+    const TicketPlan plan = ticket_partition(B, R, cap, threads / 64);      // workgroups of four waves; four or eight in the wide kernels
     a.RC = plan.RC; a.chunks = plan.chunks;
-    const hipError_t qe = (hipError_t)admm_small_launch(a, maxc, plan.wgs, c->stream);
+    const hipError_t qe = (hipError_t)admm_small_launch(a, maxc, plan.wgs, threads, c->stream);
     if (qe != hipSuccess) return fail(c, QCQPMI_EHIP, "admm_small_batch_run: %s", hipGetErrorString(qe));
-    c->last_admm_kernel = admm_small_name(maxc, cons != nullptr);
+    c->last_admm_kernel = admm_small_name(maxc, cons != nullptr, n > ADMM_SMALL_MAXN);
     c->last_admm_C = 0;
     if ((rc = select_batch_best(c, name, w, best, a.f0, a.maxviol, a.X, B, R, n, select_tol))) return rc;
     std::vector<char> hout((size_t)T * 32);      // (megabytes of fresh pages: touched while the kernel runs)
@@ -348,6 +314,63 @@ int qcqpmi_admm_small_batch_run(qcqpmi_ctx *c, int64_t B, const double *P0s, con
     void *const outs[4] = {iters1, iters2, f0, maxviol};
     for (size_t k = 0; k < 4; k++) if (outs[k]) memcpy(outs[k], hout.data() + k * n8, n8);
     return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int qcqpmi_cd_small_batch_run(qcqpmi_ctx *c, int64_t B, const double *P0s, const double *q0s, const double *r0s, int64_t R, int generate,
+                              const double *X0, int phase1, int64_t num_iters, double viol_tol, double tol, uint64_t seed,
+                              uint64_t seed_stride, uint64_t first_index, double select_tol, int64_t *sweeps1, int64_t *sweeps2,
+                              int64_t *visits2, int64_t *accepted2, uint8_t *ran_phase2, int *status1, int *status2, double *f0,
+                              double *maxviol, double *X, int64_t *best_index, double *best_f0, double *best_maxviol, double *best_x) {
+    return cd_small_batch(c, CD_SMALL_MAXN, false, nullptr, B, P0s, q0s, r0s, R, generate, X0, phase1, num_iters, viol_tol, tol, seed, seed_stride, first_index,
+                          select_tol, sweeps1, sweeps2, visits2, accepted2, ran_phase2, status1, status2, f0, maxviol, X, best_index, best_f0,
+                          best_maxviol, best_x);
+}
+
+// ---- the same launch with PER-PROBLEM constraint coefficients cons [B][m][3]: the context fixes the structure (cd_small.h)
+int qcqpmi_cd_small_batch_run_pc(qcqpmi_ctx *c, int64_t B, const double *P0s, const double *q0s, const double *r0s, const double *cons,
+                                 int64_t R, int generate, const double *X0, int phase1, int64_t num_iters, double viol_tol, double tol,
+                                 uint64_t seed, uint64_t seed_stride, uint64_t first_index, double select_tol, int64_t *sweeps1,
+                                 int64_t *sweeps2, int64_t *visits2, int64_t *accepted2, uint8_t *ran_phase2, int *status1, int *status2,
+                                 double *f0, double *maxviol, double *X, int64_t *best_index, double *best_f0, double *best_maxviol,
+                                 double *best_x) {
+    return cd_small_batch(c, CD_SMALL_MAXN, true, cons, B, P0s, q0s, r0s, R, generate, X0, phase1, num_iters, viol_tol, tol, seed, seed_stride, first_index,
+                          select_tol, sweeps1, sweeps2, visits2, accepted2, ran_phase2, status1, status2, f0, maxviol, X, best_index, best_f0,
+                          best_maxviol, best_x);
+}
+
+// ---- the batch for 1 <= n <= 128: the two symbols above for n <= 64 (cons == NULL: shared constraints), the wide kernels past it
+int qcqpmi_cd_batch_run(qcqpmi_ctx *c, int64_t B, const double *P0s, const double *q0s, const double *r0s, const double *cons, int64_t R,
+                        int generate, const double *X0, int phase1, int64_t num_iters, double viol_tol, double tol, uint64_t seed,
+                        uint64_t seed_stride, uint64_t first_index, double select_tol, int64_t *sweeps1, int64_t *sweeps2, int64_t *visits2,
+                        int64_t *accepted2, uint8_t *ran_phase2, int *status1, int *status2, double *f0, double *maxviol, double *X,
+                        int64_t *best_index, double *best_f0, double *best_maxviol, double *best_x) {
+    return cd_small_batch(c, CD_WIDE_MAXN, cons != nullptr, cons, B, P0s, q0s, r0s, R, generate, X0, phase1, num_iters, viol_tol, tol, seed, seed_stride,
+                          first_index, select_tol, sweeps1, sweeps2, visits2, accepted2, ran_phase2, status1, status2, f0, maxviol, X, best_index,
+                          best_f0, best_maxviol, best_x);
+}
+
+// ---- improve(ADMM) for B small problems (n <= 64), R restarts each (admm_small.h)
+int qcqpmi_admm_small_batch_run(qcqpmi_ctx *c, int64_t B, const double *P0s, const double *q0s, const double *r0s, const double *cons,
+                                const double *rhos, const double *Minvs, int64_t R, int generate, const double *X0, int phase1,
+                                int64_t num_iters, double tol, double viol_lim, uint64_t seed, uint64_t seed_stride, uint64_t first_index,
+                                double select_tol, int64_t *iters1, int64_t *iters2, double *f0, double *maxviol, double *X,
+                                int64_t *best_index, double *best_f0, double *best_maxviol, double *best_x) {
+    return admm_small_batch(c, ADMM_SMALL_MAXN, B, P0s, q0s, r0s, cons, rhos, Minvs, R, generate, X0, phase1, num_iters, tol, viol_lim, seed, seed_stride,
+                            first_index, select_tol, iters1, iters2, f0, maxviol, X, best_index, best_f0, best_maxviol, best_x);
+}
+
+// ---- the same for 1 <= n <= 128: the launch above for n <= 64, the wide kernels past it
+int qcqpmi_admm_batch_run(qcqpmi_ctx *c, int64_t B, const double *P0s, const double *q0s, const double *r0s, const double *cons,
+                          const double *rhos, const double *Minvs, int64_t R, int generate, const double *X0, int phase1, int64_t num_iters,
+                          double tol, double viol_lim, uint64_t seed, uint64_t seed_stride, uint64_t first_index, double select_tol,
+                          int64_t *iters1, int64_t *iters2, double *f0, double *maxviol, double *X, int64_t *best_index, double *best_f0,
+                          double *best_maxviol, double *best_x) {
+    return admm_small_batch(c, ADMM_WIDE_MAXN, B, P0s, q0s, r0s, cons, rhos, Minvs, R, generate, X0, phase1, num_iters, tol, viol_lim, seed, seed_stride,
+                            first_index, select_tol, iters1, iters2, f0, maxviol, X, best_index, best_f0, best_maxviol, best_x);
 }
 
 int qcqpmi_sdr_small_batch(qcqpmi_ctx *c, int64_t B, const double *P0s, const double *q0s, const double *r0s, int64_t S, int max_sweeps,

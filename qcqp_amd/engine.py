@@ -403,12 +403,25 @@ class Engine(object):
         X0 (B, R, n).  Returns the dictionary of admm_run with arrays of shape (B, R) -- iters1, iters2 (the reference's counts), f0,
         maxviol --, X (B, R, n) if want_x, and per problem best_index / best_f0 / best_maxviol (B,) and best_x (B, n).  cons (B, m, 3):
         per-problem constraint coefficients as cd_small_batch_run takes them.  The resident population is not touched."""
-        B, R, P0s, q0s, r0s, X0, cons, (rhos, Minvs) = self._batch_inputs('admm_small_batch_run', P0s, q0s, r0s, R, X0, cons, extra=(rhos, Minvs))
+        return self._admm_batch('admm_small_batch_run', P0s, q0s, r0s, R, rhos, Minvs, X0, phase1, num_iters, tol, viol_lim, seed, seed_stride,
+                                first_index, select_tol, want_x, cons)
+
+    def admm_batch_run(self, P0s, q0s, r0s, R, rhos, Minvs, X0=None, phase1=True, num_iters=1000, tol=1e-2, viol_lim=1e4, seed=0,
+                       seed_stride=1, first_index=0, select_tol=1e-4, want_x=True, cons=None):
+        """admm_small_batch_run for problems of up to 128 variables (qcqpmi_admm_batch_run): the same arguments, the same dictionary.
+        n <= 64 runs exactly the launch of admm_small_batch_run (same kernel, same bits); 65 <= n <= 128 runs the wide kernels
+        admm_small_kernel<MAXC[,pc],w2>: one wavefront per (problem, restart), two coordinates per lane."""
+        return self._admm_batch('admm_batch_run', P0s, q0s, r0s, R, rhos, Minvs, X0, phase1, num_iters, tol, viol_lim, seed, seed_stride,
+                                first_index, select_tol, want_x, cons)
+
+    def _admm_batch(self, name, P0s, q0s, r0s, R, rhos, Minvs, X0, phase1, num_iters, tol, viol_lim, seed, seed_stride, first_index,
+                    select_tol, want_x, cons):
+        B, R, P0s, q0s, r0s, X0, cons, (rhos, Minvs) = self._batch_inputs(name, P0s, q0s, r0s, R, X0, cons, extra=(rhos, Minvs))
         n, T = self.n, max(B * R, 0)
         out = dict(iters1=np.zeros(T, dtype=np.int64), iters2=np.zeros(T, dtype=np.int64), f0=np.empty(T), maxviol=np.empty(T),
                    X=np.empty((B, max(R, 0), n)) if want_x else None, best_index=np.zeros(B, dtype=np.int64), best_f0=np.empty(B),
                    best_maxviol=np.empty(B), best_x=np.zeros((B, n)))
-        self._chk(self.L.qcqpmi_admm_small_batch_run(
+        self._chk(getattr(self.L, 'qcqpmi_' + name)(
             self.h, B, _dp(P0s), _dp(q0s), _dp(r0s), _dp(cons), _dp(rhos), _dp(Minvs), R, 0 if X0 is not None else 1, _dp(X0),
             int(bool(phase1)), int(num_iters), float(tol), float(viol_lim), int(seed), int(seed_stride), int(first_index), float(select_tol),
             _ip(out['iters1']), _ip(out['iters2']), _dp(out['f0']), _dp(out['maxviol']), _dp(out['X']), _ip(out['best_index']),

@@ -1,4 +1,5 @@
-"""Wall time of the batched ADMM (qcqpmi_admm_small_batch_run) against the per-problem loop it replaces.
+"""Wall time of the batched ADMM (qcqpmi_admm_small_batch_run; --wide: qcqpmi_admm_batch_run, n <= 128) against the per-problem loop it
+replaces.
 
 Workload: problems.boolean_least_squares_batch(B, n, m), R restarts per problem, num_iters iterations per phase at most.
   batched    QCQPBatch.suggest(RANDOM) + improve(ADMM): one batched eigvalsh (the rho rule), one batched inverse, ONE launch of
@@ -6,7 +7,9 @@ Workload: problems.boolean_least_squares_batch(B, n, m), R restarts per problem,
              synchronised; --repeat calls after one warm-up, median.  The host part (eigvalsh + inverse) is timed on its own as well.
   loop       what the library offered before: per problem QCQP(Problem).suggest(RANDOM, R) + improve(ADMM) -- a context, finalize,
              a Lanczos run for lambda_min, the inverse, several launches per iteration.  Timed on the first --loop-problems problems and
-             SCALED LINEARLY to B (every problem costs the same launches).
+             SCALED LINEARLY to B (every problem costs the same launches).  --loop-problems 0 skips it (an A/B of the batched call alone).
+--wide passes wide=True to improve(ADMM), so that --n 128 --m 192 runs (the wide kernels); --wide-threads T sets
+QCQPMI_ADMM_WIDE_THREADS: a workgroup of T threads for the wide kernels instead of the occupancy rule (results do not depend on it).
 Prints one JSON line.  The two paths agree in the median only (the iteration amplifies rounding: DESIGN.md 4.13); the line reports on how
 many of the timed problems the winners' objectives agree to 1e-6."""
 import argparse
@@ -28,7 +31,11 @@ def main():
     ap.add_argument('--repeat', type=int, default=5)
     ap.add_argument('--loop-problems', type=int, default=64)
     ap.add_argument('--seed', type=int, default=1)
+    ap.add_argument('--wide', action='store_true')
+    ap.add_argument('--wide-threads', type=int, default=0)
     args = ap.parse_args()
+    if args.wide_threads:
+        os.environ['QCQPMI_ADMM_WIDE_THREADS'] = str(args.wide_threads)      # read once, at the first wide launch
 
     from qcqp_amd import QCQP, Problem, batch, problems, settings as s
     from qcqp_amd.batch import QCQPBatch
@@ -42,7 +49,7 @@ def main():
 
     def batched():
         t0 = time.perf_counter()
-        f, v = qb.improve(s.ADMM, num_iters=args.num_iters)
+        f, v = qb.improve(s.ADMM, num_iters=args.num_iters, **(dict(wide=True) if args.wide else {}))
         return time.perf_counter() - t0, f
 
     batched()                                       # warm-up: code object, buffers
@@ -69,16 +76,17 @@ def main():
             best.append(float(fb))
         return time.perf_counter() - t0, best
 
-    loop()                                          # warm-up
-    lt = sorted((loop() for _ in range(3)), key=lambda t: t[0])
-    t_loop, best = lt[1]
-    agree = sum(1 for b in range(nl) if abs(f_batched[b] - best[b]) <= 1e-6 * (1 + abs(best[b])))
-    print(json.dumps(dict(
-        workload=dict(family='bls', B=args.B, n=args.n, m=args.m, R=args.R, num_iters=args.num_iters), kernel=st['kernel'],
-        batched_s=t_batched, batched_all_s=times, host_eigvalsh_and_inverse_s=t_host, restart_iterations=iters,
-        restart_iterations_per_s=iters / t_batched, loop_problems=nl, loop_s_measured=t_loop,
-        loop_s_scaled_to_B=t_loop * args.B / nl, speedup_scaled=(t_loop * args.B / nl) / t_batched,
-        winners_objective_agree_1e6='%d/%d' % (agree, nl))))
+    out = dict(workload=dict(family='bls', B=args.B, n=args.n, m=args.m, R=args.R, num_iters=args.num_iters), kernel=st['kernel'],
+               wide_threads=args.wide_threads or 'rule', batched_s=t_batched, batched_all_s=times, host_eigvalsh_and_inverse_s=t_host,
+               restart_iterations=iters, restart_iterations_per_s=iters / t_batched, loop_problems=nl)
+    if nl > 0:
+        loop()                                      # warm-up
+        lt = sorted((loop() for _ in range(3)), key=lambda t: t[0])
+        t_loop, best = lt[1]
+        agree = sum(1 for b in range(nl) if abs(f_batched[b] - best[b]) <= 1e-6 * (1 + abs(best[b])))
+        out.update(loop_s_measured=t_loop, loop_s_scaled_to_B=t_loop * args.B / nl, speedup_scaled=(t_loop * args.B / nl) / t_batched,
+                   winners_objective_agree_1e6='%d/%d' % (agree, nl))
+    print(json.dumps(out))
 
 
 if __name__ == '__main__':
