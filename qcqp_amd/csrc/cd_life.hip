@@ -1513,12 +1513,15 @@ __global__ __launch_bounds__((NMW == 3 && TILES == 1) ? 256 : 512, 2) void cd_li
 // (where it took 19 % of a workgroup's time and left the neighbour's roles unpaired meanwhile).  A workgroup takes one tile of
 // 16 restarts: thread (g, s) = (tid >> 4, tid & 15) owns the coordinate pairs 2 g + 32 k, 2 g + 32 k + 1 of slot s, so that a
 // row of the tile (16 restarts, 128 B) is one access.  Same visits, same termination rule, same exact max reductions as the
-// build: the same bits.  Out: the point after phase 1 in b.X (the refill copies it, write-out overwrites it), sweeps1 / status1 /
-// ran2 at the restart's index (write-out writes the same values again) and the slack in CdLife::preslack.
+// build: the same bits.  That layout holds for generation, sweep 0 of phase 1 and the slack pass; a later sweep with fewer than 16
+// unfinished columns gives each of them to all 256 threads in turn (see the loop).  Three waves per SIMD (168 registers): the visits
+// are chains of dependent double-precision instructions, a third wave fills their gaps.  Out: the point after phase 1 in b.X (the
+// refill copies it, write-out overwrites it), sweeps1 / status1 / ran2 at the restart's index (write-out writes the same values
+// again) and the slack in CdLife::preslack.
 constexpr int L2P_NT = 256;
-__global__ __launch_bounds__(L2P_NT) void cd_life_prep_kernel(DevProblem P, const CdLife *life, double *X, int64_t num_iters, double tol) {
-    __shared__ unsigned long long key[16];
-    __shared__ int upd[16], st1[16], fin[16], sw[16], nact;
+__global__ __launch_bounds__(L2P_NT, 3) void cd_life_prep_kernel(DevProblem P, const CdLife *life, double *X, int64_t num_iters, double tol) {
+    __shared__ unsigned long long key[16], csd[16], cgi[16];
+    __shared__ int upd[16], st1[16], fin[16], sw[16], cols[16], nact;
     const int tid = threadIdx.x, s = tid & 15, g = tid >> 4;
     GLB const CdLife *lf = glb(life);
     const int64_t id = (int64_t)blockIdx.x * 16 + s;
@@ -1543,53 +1546,77 @@ __global__ __launch_bounds__(L2P_NT) void cd_life_prep_kernel(DevProblem P, cons
     const int e0 = P.cptr[P.krep[0]];
     const double cp = P.cp[e0], cq = P.cq[e0], cr = P.cr[e0];
     const int rel = P.crel[e0];
-    if (tid < 16) { fin[tid] = valid ? 0 : 1; sw[tid] = 0; st1[tid] = 0; }
+    if (tid < 16) { fin[tid] = valid ? 0 : 1; sw[tid] = 0; st1[tid] = 0; csd[tid] = sd; cgi[tid] = gidx; }
     if (lf->phase1) {
         const bool band2 = cq == 0.0 && rel == RELOP_EQ && cp > 1e-4 && cr < -1e-3;      // the build's choice of visit
+        GLB double *Xtile = glb(X) + (int64_t)blockIdx.x * n16 * 16;
         for (int64_t t = 0; t < num_iters; t++) {
             if (tid < 16) { key[tid] = ordered_key(-QM_INF); upd[tid] = 0; }
             __syncthreads();
-            if (tid == 0) { int c = 0; for (int k = 0; k < 16; k++) c += fin[k] ? 0 : 1; nact = c; }
+            if (tid == 0) { int c = 0; for (int k = 0; k < 16; k++) if (!fin[k]) cols[c++] = k; nact = c; }
             __syncthreads();
             if (nact == 0) break;
-            double va = -QM_INF;
-            int moved = 0, stv = 0;
-            if (!fin[s]) {
-                for (int64_t j = 2 * g; j < n; j += 32) {
-                    if (band2) {
-                        const int64_t i2[2] = {j, j + 1};
-                        const bool on2[2] = {true, j + 1 < n};
-                        double x2[2] = {Xt[16 * j], on2[1] ? Xt[16 * (j + 1)] : 1.0};
-                        P1Visit V2[2];
-                        p1_band_visit_n<2>(cp, cq, cr, i2, x2, on2, tol, viol_tol, sd, gidx, t, V2);
+            // Sweep 0, and later sweeps of a full tile, run in lockstep: thread (g, s) visits its pairs of slot s.  Once fewer than 16
+            // columns are unfinished (a restart ends after sweep 0 unless a coordinate sits within tol of the band: one in twenty at the
+            // headline, so most tiles hold one or two) the sweep is COMPACT: the unfinished columns one after the other, each with all
+            // 256 threads, thread tid on the pairs 2 tid + 512 k -- at n = 1024 two pair visits per thread and unfinished column, where
+            // lockstep issues 32 per thread with the lanes of the finished columns idle.  A visit depends on (restart, coordinate,
+            // sweep) only: the same bits.
+            const bool compact = t > 0 && nact < 16;
+            const int npass = compact ? nact : 1;
+            const int64_t j0 = compact ? 2 * tid : 2 * g, jstep = compact ? 2 * L2P_NT : 32;
+            for (int qq = 0; qq < npass; qq++) {
+                const int c = compact ? cols[qq] : s;
+                const bool live = compact || !fin[s];
+                GLB double *Xc = Xtile + c;
+                const uint64_t sdc = csd[c], gic = cgi[c];
+                double va = -QM_INF;
+                int moved = 0, stv = 0;
+                if (live) {
+                    for (int64_t j = j0; j < n; j += jstep) {
+                        if (band2) {
+                            const int64_t i2[2] = {j, j + 1};
+                            const bool on2[2] = {true, j + 1 < n};
+                            double x2[2] = {Xc[16 * j], on2[1] ? Xc[16 * (j + 1)] : 1.0};
+                            P1Visit V2[2];
+                            p1_band_visit_n<2, true>(cp, cq, cr, i2, x2, on2, tol, viol_tol, sdc, gic, t, V2);
 #pragma unroll
-                        for (int k = 0; k < 2; k++)
-                            if (on2[k]) {
-                                if (V2[k].moved) { Xt[16 * i2[k]] = x2[k]; moved = 1; }
-                                if (V2[k].status) stv = V2[k].status;
-                                va = V2[k].vafter > va ? V2[k].vafter : va;
+                            for (int k = 0; k < 2; k++)
+                                if (on2[k]) {
+                                    if (V2[k].moved) { Xc[16 * i2[k]] = x2[k]; moved = 1; }
+                                    if (V2[k].status) stv = V2[k].status;
+                                    va = V2[k].vafter > va ? V2[k].vafter : va;
+                                }
+                        } else {
+                            for (int64_t i = j; i < j + 2 && i < n; i++) {
+                                int fl = 0;
+                                double v = 0.0;
+                                const double xi = p1_class_visit(cp, cq, cr, rel, i, Xc[16 * i], tol, viol_tol, sdc, gic, t, &fl, &v);
+                                if (fl & 1) { Xc[16 * i] = xi; moved = 1; }
+                                if (fl >> 8) stv = -(fl >> 8);
+                                va = v > va ? v : va;
                             }
-                    } else {
-                        for (int64_t i = j; i < j + 2 && i < n; i++) {
-                            int fl = 0;
-                            double v = 0.0;
-                            const double xi = p1_class_visit(cp, cq, cr, rel, i, Xt[16 * i], tol, viol_tol, sd, gidx, t, &fl, &v);
-                            if (fl & 1) { Xt[16 * i] = xi; moved = 1; }
-                            if (fl >> 8) stv = -(fl >> 8);
-                            va = v > va ? v : va;
                         }
                     }
                 }
-            }
-            // the lanes of a slot within the wave: s, s + 16, s + 32, s + 48
+                // lockstep: the lanes of a slot within the wave are s, s + 16, s + 32, s + 48; compact: the whole wave is one column
 #pragma unroll
-            for (int o = 16; o <= 32; o <<= 1) {
-                const double w = __shfl_xor(va, o, 64);
-                va = w > va ? w : va;
-                moved |= __shfl_xor(moved, o, 64);
+                for (int o = 16; o <= 32; o <<= 1) {
+                    const double w = __shfl_xor(va, o, 64);
+                    va = w > va ? w : va;
+                    moved |= __shfl_xor(moved, o, 64);
+                }
+                if (compact) {
+#pragma unroll
+                    for (int o = 1; o <= 8; o <<= 1) {
+                        const double w = __shfl_xor(va, o, 64);
+                        va = w > va ? w : va;
+                        moved |= __shfl_xor(moved, o, 64);
+                    }
+                }
+                if ((tid & 63) < (compact ? 1 : 16) && live) { atomicMax(&key[c], ordered_key(va)); if (moved) upd[c] = 1; }
+                if (stv) st1[c] = stv;
             }
-            if ((tid & 63) < 16 && !fin[s]) { atomicMax(&key[s], ordered_key(va)); if (moved) upd[s] = 1; }
-            if (stv) st1[s] = stv;
             __syncthreads();
             if (tid < 16 && !fin[tid]) {
                 sw[tid]++;

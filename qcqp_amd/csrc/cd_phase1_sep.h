@@ -12,6 +12,7 @@
 #pragma once
 #include "kernels.h"
 #include "onevar.h"
+#include "p1_bisect.h"
 
 namespace qcqpmi {
 
@@ -221,7 +222,7 @@ __device__ inline void p1_band_visit(double p, double q, double r, int64_t i, do
 // bit: the bisection loops are fused (an element that is done idles in the body: selects), the tail that builds the set of the
 // last successful slack and draws the point is computed for every element and applied where a step succeeded.  r < -1e-3 only
 // (the Boolean family; see p1_band_visit for the test on the slack); `on[k]` = false: element k is padding.
-template <int NV>
+template <int NV, bool FASTA = false>
 __device__ inline void p1_band_visit_n(double p, double q, double r, const int64_t (&i)[NV], double (&xi)[NV], const bool (&on)[NV], double tol,
                                        double viol_tol, uint64_t seed, uint64_t grestart, int64_t t, P1Visit (&V)[NV]) {
     double viol[NV], ss[NV], es[NV], sp[NV];
@@ -235,29 +236,35 @@ __device__ inline void p1_band_visit_n(double p, double q, double r, const int64
         ss[k] = -tol; es[k] = on[k] ? viol[k] - viol_tol : -tol; sp[k] = 0.0;
         it[k] = 0; itp[k] = 0; pending[k] = false;
     }
-    for (;;) {
-        bool any = false;
+    if constexpr (FASTA) {
+        // cd_life_prep_kernel: the same loop behind a first phase that carries `es` alone (p1_bisect.h, where a host program can drive
+        // both).  The lifecycle kernels and cd_queue.hip keep the loop below as it stands: their code, registers and timing are unchanged.
+        p1_band_bisect<NV>(p, r, tol, ss, es, sp, it, itp, pending);
+    } else {
+        for (;;) {
+            bool any = false;
 #pragma unroll
-        for (int k = 0; k < NV; k++) any = any || (es[k] - ss[k] > tol);
-        if (!any) break;
+            for (int k = 0; k < NV; k++) any = any || (es[k] - ss[k] > tol);
+            if (!any) break;
 #pragma unroll
-        for (int k = 0; k < NV; k++) {
-            const bool act = es[k] - ss[k] > tol;
-            const double s = (ss[k] + es[k]) / 2.0;
-            const uint32_t itb = it[k];
-            it[k] += act ? 1u : 0u;
-            bool nonempty = s > 0.0;
-            if (__builtin_expect(act && !(fabs(s) > guard), 0)) {       // within rounding of the threshold: the reference's discriminants
-                const double D1 = 0.0 - 4.0 * p * (r - s);
-                const double D2 = 0.0 - 4.0 * (-p) * (-r - s);
-                nonempty = D1 > 0.0 && (D2 < 0.0 || D2 < D1);
+            for (int k = 0; k < NV; k++) {
+                const bool act = es[k] - ss[k] > tol;
+                const double s = (ss[k] + es[k]) / 2.0;
+                const uint32_t itb = it[k];
+                it[k] += act ? 1u : 0u;
+                bool nonempty = s > 0.0;
+                if (__builtin_expect(act && !(fabs(s) > guard), 0)) {       // within rounding of the threshold: the reference's discriminants
+                    const double D1 = 0.0 - 4.0 * p * (r - s);
+                    const double D2 = 0.0 - 4.0 * (-p) * (-r - s);
+                    nonempty = D1 > 0.0 && (D2 < 0.0 || D2 < D1);
+                }
+                const bool up = act && nonempty, dn = act && !nonempty;
+                ss[k] = dn ? s : ss[k];
+                es[k] = up ? s : es[k];
+                sp[k] = up ? s : sp[k];
+                itp[k] = up ? itb : itp[k];
+                pending[k] = pending[k] || up;
             }
-            const bool up = act && nonempty, dn = act && !nonempty;
-            ss[k] = dn ? s : ss[k];
-            es[k] = up ? s : es[k];
-            sp[k] = up ? s : sp[k];
-            itp[k] = up ? itb : itp[k];
-            pending[k] = pending[k] || up;
         }
     }
 #pragma unroll
