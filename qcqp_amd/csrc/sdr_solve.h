@@ -8,6 +8,10 @@
 // which decreases <C, V V^T> monotonically and converges to the SDP optimum for K > sqrt(2N).
 // Third-party solver in the reference => parity is unpinned by construction; validated by optimality
 // conditions (dual certificate lambda_min(C + diag(y)) >= -eps, tests/test_gpu_api.py) and brute force.
+// The kernel itself is followed SWEEP BY SWEEP: from a given V0 after T sweeps, V and hist equal a plain restatement of the passes
+// below (tests/sdr_mixing_cases.py: mixing_reference) to 1e-12 for N = 2 .. 4096, with the stop rule, max_sweeps = 0, rows whose
+// g_i is zero and bit-for-bit repeatability (tests/test_gpu_sdr_mixing.py; the restatement against long double in
+// tests/test_sdr_mixing_cpu.py).  The history formulas assume UNIT rows of the V handed in; the kernel does not normalise them.
 //
 // The method is a strictly sequential chain of N small matrix-vector products per sweep.  Layout on the
 // chip: COMPONENT-SLICED -- workgroup kk (one wavefront, 64 workgroups on 64 CUs) owns component kk of

@@ -482,7 +482,11 @@ class Engine(object):
     # ------------------------------------------------------------ SDP relaxation
     def sdr_solve_unitdiag(self, Cm, V0=None, max_sweeps=2000, tol=1e-10, seed=0):
         """min <C, X> s.t. diag(X) = 1, X PSD (mixing method on the device).  Returns V (N x 64, unit
-        rows, X = V V^T), the objective history and the number of sweeps."""
+        rows, X = V V^T), the objective history (hist[0]: the start, hist[t]: after sweep t, tracked by the exact decrease
+        of every update, hist[sweeps + 1]: recomputed at the end) and the number of sweeps.
+        A V0 handed in is taken AS IT IS and must have unit rows: it is not normalised here or on the device, and the
+        history formulas (v_i . g_i + C_ii per row, -2 (|g_i| + g_i . v_i) per update) hold for unit rows only -- with other
+        rows hist[0] and the tracked values are not <C, V V^T> (the rows the sweeps visit come back unit all the same)."""
         Cm = np.ascontiguousarray(Cm, dtype=np.float64)
         N = Cm.shape[0]
         assert Cm.shape == (N, N)
