@@ -16,7 +16,8 @@ HEADER = os.path.join(REPO, 'include', 'qcqp_mi.h')
 
 # translation units; what each one includes is found by scanning its `#include "..."` lines recursively (round 4 shipped a
 # hand-kept list that missed a header: an edit to it rebuilt nothing)
-TRANSLATION_UNITS = ['capi.hip', 'admm_fused.hip', 'cd_queue.hip', 'cd_life.hip', 'cd_small.hip', 'sdr_small.hip', 'admm_small.hip']
+TRANSLATION_UNITS = ['capi.hip', 'capi_admm.hip', 'capi_small.hip', 'capi_units.hip', 'capi_comm.hip',
+                     'admm_fused.hip', 'cd_queue.hip', 'cd_life.hip', 'cd_small.hip', 'sdr_small.hip', 'admm_small.hip']
 _INC = re.compile(r'^\s*#\s*include\s+"([^"]+)"', re.M)
 
 
@@ -57,8 +58,13 @@ def _unit_deps(unit):
     return unit_sources(unit) + [HEADER]
 
 
+def stale_units():
+    """The units whose object is missing or older than one of their sources."""
+    return [u for u in UNITS if _stale(_obj(u), _unit_deps(u))]
+
+
 def needs_build():
-    return any(_stale(_obj(u), _unit_deps(u)) for u in UNITS) or _stale(LIB, [_obj(u) for u in UNITS if os.path.exists(_obj(u))])
+    return bool(stale_units()) or _stale(LIB, [_obj(u) for u in UNITS])
 
 
 def build(force=False, verbose=False):
@@ -78,8 +84,8 @@ def build(force=False, verbose=False):
             print(' '.join(cmd))
         subprocess.check_call(cmd)
 
-    todo = [u for u in UNITS if force or _stale(_obj(u), _unit_deps(u))]
-    with ThreadPoolExecutor(max_workers=max(1, len(todo))) as ex:
+    todo = list(UNITS) if force else stale_units()
+    with ThreadPoolExecutor(max_workers=min(16, max(1, len(todo)))) as ex:
         list(ex.map(compile_unit, todo))
     cmd = [hipcc, '--offload-arch=gfx950', '-shared', '-fPIC', '-o', LIB] + [_obj(u) for u in UNITS] + ['-ldl']
     if verbose:

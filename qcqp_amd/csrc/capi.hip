@@ -1,218 +1,29 @@
 // C ABI of libqcqp_mi.so (declared in include/qcqp_mi.h): context, problem upload, population
-// management, launches of the kernels in kernels_impl.h, HIP-event timing, lazy RCCL.
-#include <dlfcn.h>
-#include <unistd.h>
-#include <hip/hip_runtime.h>
-#include <rccl/rccl.h>
-
+// management, launches of the kernels in kernels_impl.h, HIP-event timing.  The core of the host side: the ADMM calls are in
+// capi_admm.hip, the small-problem batch calls in capi_small.hip, the unit operators in capi_units.hip, RCCL in capi_comm.hip;
+// capi_ctx.h holds what these units share.
 #include <algorithm>
+#include <chrono>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
-#include <string>
-#include <chrono>
-#include <vector>
 
-#include "../../include/qcqp_mi.h"
+#include "capi_ctx.h"
 #include "kernels_impl.h"
-#include "admm.h"
-#include "admm_fused.h"
 #include "cd_queue.h"
-#include "cd_life.h"
-#include "cd_small.h"
-#include "admm_small.h"
-#include "sdr_small.h"
-#include "gemm_pk.h"
-#include "cd_general.h"
 #include "cd_dense.h"
 #include "sdr_solve.h"
-#include "dev_buf.h"
 
 using namespace qcqpmi;
 
 namespace {
 
-thread_local std::string g_create_error;
-
-struct HostQuad {
-    bool set = false;
-    std::vector<int> ci, cj;  // COO
-    std::vector<double> cv;
-    std::vector<double> q;
-    double r = 0.0;
-    int relop = 0;
-    // generated on the device (qcqpmi_set_quad_generated)
-    bool gen = false;
-    uint64_t gseed = 0;
-    double gscale = 0.0, gqscale = 0.0, gdiag = 0.0;
-    // packed on the device at qcqpmi_set_quad time (problems whose constraint matrices exceed the row-major budget)
-    bool streamed = false;
-};
-
-struct Timer {
-    hipEvent_t beg = nullptr, end = nullptr;
-    bool valid = false;
-};
-
-struct RcclApi {
-    void *h = nullptr;
-    ncclResult_t (*GetUniqueId)(ncclUniqueId *) = nullptr;
-    ncclResult_t (*CommInitRank)(ncclComm_t *, int, ncclUniqueId, int) = nullptr;
-    ncclResult_t (*CommDestroy)(ncclComm_t) = nullptr;
-    ncclResult_t (*AllGather)(const void *, void *, size_t, ncclDataType_t, ncclComm_t, hipStream_t) = nullptr;
-    ncclResult_t (*Broadcast)(const void *, void *, size_t, ncclDataType_t, int, ncclComm_t, hipStream_t) = nullptr;
-    ncclResult_t (*AllReduce)(const void *, void *, size_t, ncclDataType_t, ncclRedOp_t, ncclComm_t, hipStream_t) = nullptr;
-    const char *(*GetErrorString)(ncclResult_t) = nullptr;
-};
-
-RcclApi *rccl() {
-    static RcclApi api;
-    static bool tried = false;
-    if (!tried) {
-        tried = true;
-        const char *names[] = {"librccl.so", "librccl.so.1", "/opt/rocm/lib/librccl.so"};
-        for (const char *nm : names) {
-            api.h = dlopen(nm, RTLD_NOW | RTLD_GLOBAL);
-            if (api.h) break;
-        }
-        if (api.h) {
-            api.GetUniqueId = (decltype(api.GetUniqueId))dlsym(api.h, "ncclGetUniqueId");
-            api.CommInitRank = (decltype(api.CommInitRank))dlsym(api.h, "ncclCommInitRank");
-            api.CommDestroy = (decltype(api.CommDestroy))dlsym(api.h, "ncclCommDestroy");
-            api.AllGather = (decltype(api.AllGather))dlsym(api.h, "ncclAllGather");
-            api.Broadcast = (decltype(api.Broadcast))dlsym(api.h, "ncclBroadcast");
-            api.AllReduce = (decltype(api.AllReduce))dlsym(api.h, "ncclAllReduce");
-            api.GetErrorString = (decltype(api.GetErrorString))dlsym(api.h, "ncclGetErrorString");
-        }
-    }
-    return (api.h && api.GetUniqueId && api.CommInitRank && api.AllGather && api.Broadcast &&
-            api.AllReduce) ? &api : nullptr;
-}
+thread_local std::string g_create_error;      // the ONE slot of errors without a context: fail() writes it, qcqpmi_last_error(NULL) reads it
 
 }  // namespace
 
-// Every device or pinned pointer the context OWNS is a DevBuf / PinBuf (dev_buf.h): freed when the context is deleted, grown with
-// reserve().  Raw pointers below only view another allocation (dn_Gpack, dn_q, ..., dp.*: all of them in prob_allocs).
-struct qcqpmi_ctx {
-    int device = 0;
-    int64_t n = 0, n16 = 0, m = 0;
-    hipStream_t stream = nullptr;
-    std::string err;
-    std::vector<HostQuad> quads;  // m+1
-    bool finalized = false;
-    bool sep = false;
-    int maxc = 0;
-    int K = 0;
-    int objclass = 0;  // 1: every P0[i,i] > 0, 2: every P0[i,i] == 0, 0: mixed (negative entries, or zero in places: cd_life_kernel's SGN kind)
-    bool symcls = false;  // one constraint class of the form p x_i^2 + r == 0 (feasible sets mirrored about 0)
-    DevProblem dp{};
-    std::vector<DevBuf<char>> prob_allocs;   // the problem's arrays (dp.*, dn_*, d_gP): allocated at finalize, never grown
-    // population: the group below grows together (pop_reserve, Rcap restarts); Xi and d_F are sized on demand and dropped with it
-    int64_t R = 0, Rpad = 0, Rcap = 0;
-    DevBuf<double> X, Xi;        // Xi: the standard normals of pop_sdr_sample
-    DevBuf<double> d_f0, d_mv, d_F;
-    DevBuf<int64_t> d_visits, d_acc, d_sweeps, d_sweeps1;
-    DevBuf<int> d_status, d_status1;
-    DevBuf<uint8_t> d_flag;
-    DevBuf<int64_t> d_best_idx;
-    DevBuf<double> d_best_key;
-    DevBuf<double> d_stage;  // host-layout staging (n x Rcap)
-    bool evaluated = false;
-    // SDR factor
-    DevBuf<double> d_Fpack, d_Frow, d_mu;
-    Timer timers[5];
-    // ADMM: the stacked bases B = [B_1 ... B_m] packed for the two products (gemm_pk.h), eigenvalues, B^T q, brackets
-    // unit bases (every basis vector is +-e_i: separable constraints): ZQ = W^T Z is a gather, S = W D a scatter (no GEMM)
-    DevBuf<int> ad_uidx, ad_uptr, ad_ulist;                                // [Mh16] coordinate of basis row h (-1: padding); CSR coordinate -> rows
-    DevBuf<double> ad_usgn;                                                // [Mh16] its sign
-    bool ad_unit = false, ad_unit_off = false;
-    DevBuf<double> ad_WTpk, ad_Wpk, ad_lam, ad_qhat, ad_rk, ad_slo, ad_ehi;
-    DevBuf<double> ad_Minvpk;
-    DevBuf<int> ad_relop;
-    int64_t ad_rows = 0, ad_Mh16 = 0;   // hat rows per constraint (n, or rp of a reduced basis); m * rows padded to 16
-    int ad_lowrank = 0;
-    bool ad_qzero = false;              // every B_k^T q_k is zero
-    void *rb_handle = nullptr;          // rocBLAS handle: only the rocSOLVER setup path needs one
-    bool p0_diag = false;               // P0 has no off-diagonal entries (z-update and f0 need no product then)
-    std::vector<double> p0_diag_host;
-    // outputs of a run packed into one device buffer, copied with ONE transfer into pinned host memory
-    DevBuf<char> d_out;
-    PinBuf<char> h_out;
-    PinBuf<char> h_pin;                   // pinned bounce buffer of the relaxation solver's downloads
-    int eval_zs = 1;   // planes of the last dense evaluation
-    DevBuf<double> d_wS, d_wY, d_ww, d_wz;   // qcqpmi_pop_weighted_product work buffers
-    DevBuf<double> d_planes;   // partial planes of x'P0x from the GEMM evaluation
-    double *d_gP = nullptr;   // dense constraint matrices [m][n][n] (problems whose constraints couple coordinates): in prob_allocs
-    // dense-constraint path (cd_dense.h): all matrices in block-major fragment order + work buffers
-    const double *dn_Gpack = nullptr, *dn_q = nullptr, *dn_qT = nullptr, *dn_r = nullptr;
-    const int *dn_relop = nullptr;
-    DevBuf<double> dn_G, dn_Dg, dn_Ft;    // dn_Ft grows with dn_G
-    int dense_chain_mode = 0;             // 0: four waves per restart where it applies, 1: one wave per restart (cross-check)
-    DevBuf<long long> dn_prof;            // 32 tick sums of the dense chain kernel (debug profile)
-    DevBuf<char> dn_state;                // per-restart state of a dense phase (dense_state lays it out for Rpad restarts)
-    hipStream_t stream2 = nullptr;   // second stream of the dense path: products of block b+1 while the chain walks b
-    hipEvent_t dn_ev[3] = {nullptr, nullptr, nullptr};
-    hipEvent_t dn_evn[2] = {nullptr, nullptr};   // "live count of sweep t copied" (dense path: the host runs one sweep ahead)
-    PinBuf<int> dn_hn;                           // pinned: the two live counts in flight
-    bool dn_force = false;    // generated functions: the dense path is the only one that holds them
-    // streaming upload (coupled constraints beyond `stream_limit` bytes of row-major storage): every function is packed for the
-    // matrix cores as it arrives; neither the host nor the device ever holds a second copy
-    double stream_limit = 16e9;
-    DevBuf<double> dn_gp_pre, dn_tmp;     // the packed matrices until finalize takes them over; the row-major staging of one function
-    // comm
-    ncclComm_t comm = nullptr;
-    int rank = 0, world = 1;
-    DevBuf<double> d_comm, d_comm_big;
-    DevBuf<long long> d_prof;
-    int cd_stage = 0;                   // qcqpmi_cd_run_stage: last stage completed of a split run
-    bool sdr_factor_resident = false;   // d_Fpack / d_mu hold the pair of the last pop_sdr_sample
-    double ad_Minv_rho = 0.0;           // rho of the z-solver matrix formed by qcqpmi_admm_zsolver_device
-    bool ad_Minv_device = false;
-    const char *last_cd2_kernel = "";     // name of the phase-2 kernel of the most recent cd run (bench / profiles)
-    bool profile = false;
-    int dbg = 0;
-    // fused persistent ADMM kernel (admm_fused.h): one work buffer kept across runs, grown on demand
-    DevBuf<char> af_work;
-    bool ad_fused = true;                 // qcqpmi_admm_fused: use the fused kernel where it applies
-    int ad_fused_nt = 512;                // threads per workgroup of the fused kernel (256: qcqpmi_admm_fused(ctx, 2))
-    const char *last_admm_kernel = "";    // "admm_fused_kernel" / "admm_multi_launch"
-    int last_admm_C = 0;                  // workgroups per tile of the last fused run
-    long long af_prof[16] = {0};          // stage cycle counters of the last fused run (when qcqpmi_debug_profile enabled them)
-    int cd_queue = 2;                     // qcqpmi_cd_queue: 0 off, 1 restart-level scheduling (cd_phase2_qs_kernel) wherever it applies,
-                                          // 2 auto: when there are more tiles than CUs
-    DevBuf<int> d_qnext;                  // [0] queue head of the slot-queue kernel
-    bool q_prepared = false;              // the queue of the resident population has been reset
-    DevBuf<CdLife> d_life;       // qcqpmi_cd_stream_run: parameters of the lifecycle launch
-    // second-generation lifecycle kernel (cd_life.h): the workgroups' X tiles, the staged diagonal blocks, the watchdog word
-    int Kreal = 0;               // constraint classes among the REAL coordinates (the padded ones of n16 carry no constraint)
-    double fbound = 0.0;         // sum |P0| + sum |q0| + |r0|
-    DevBuf<double> l2_scratch;
-    DevBuf<double> l2_D, l2_S;
-    DevBuf<int> l2_abort;
-    DevBuf<int> l2_cuslot;       // [4096] arrival counters per compute unit of cd_life_kernel (zeroed before every launch)
-    DevBuf<double> l2_preslack;  // [K R] slack of the prebuilt columns (cd_life2_prep_launch)
-    DevBuf<double> l2_y0;        // [tile][16 lr_RB][16] Y0 = L^T x0 of the preloaded restarts (cd_life2_y0_launch)
-    // factored objective P0 = L L^T (qcqpmi_cd_set_objective_factor): L (n16 x 16 lr_RB, zero-padded) and its fragment packs
-    DevBuf<double> lr_L, lr_G, lr_U; int lr_RB = 0;
-    int life_version = 0;        // qcqpmi_cd_life_version: 0 = the faster one for the shape, 2 = cd_life_kernel wherever it applies, 1 = cd_phase2_qs_kernel<lifecycle> only
-    DevBuf<long long> d_life_prof;
-    DevBuf<int64_t> d_bestK_idx; DevBuf<double> d_bestK_key, d_bestK_x;
-    bool cd_ref_order = false;   // qcqpmi_cd_reference_order: coupled constraints in the reference's summation order
-    bool force_generic = false;  // debug/tests: run the general phase-2 kernel even when the pipelined one applies
-    std::vector<int> last_st1, last_st2;   // per-restart status codes of the last coordinate-descent run (qcqpmi_cd_status)
-    // capi_small.inc, the CD and ADMM batch calls: ONE device buffer for the objectives, starts, per-restart outputs, points and winners
-    // of a call (grown on demand; the resident population and its buffers are never used by that call)
-    DevBuf<char> sb_work;
-    // qcqpmi_sdr_small_batch: d (n) when every coordinate carries exactly one constraint p x_i^2 + r == 0 with d_i = -r / p > 0 (the
-    // unit-diagonal family of the relaxation), else empty; and the call's own device buffer, like sb_work
-    std::vector<double> unit_d;
-    DevBuf<char> ss_work;
-};
-
-namespace {
-
-void admm_drop_handle(qcqpmi_ctx *c);      // capi_admm.inc: the rocBLAS handle of qcqpmi_admm_setup
+namespace qcqpmi {
 
 int fail(qcqpmi_ctx *c, int code, const char *fmt, ...) {
     char buf[1024];
@@ -224,13 +35,26 @@ int fail(qcqpmi_ctx *c, int code, const char *fmt, ...) {
     return code;
 }
 
-#define HIPCHK(c, expr)                                                                       \
-    do {                                                                                      \
-        hipError_t e_ = (expr);                                                               \
-        if (e_ != hipSuccess)                                                                 \
-            return fail(c, QCQPMI_EHIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), \
-                        __FILE__, __LINE__);                                                  \
-    } while (0)
+int check_ready(qcqpmi_ctx *c, bool need_pop) {
+    if (!c) return QCQPMI_EINVAL;
+    if (!c->finalized) return fail(c, QCQPMI_ESTATE, "qcqpmi_finalize has not been called");
+    if (need_pop && c->R <= 0) return fail(c, QCQPMI_ESTATE, "no resident population (upload / randn / sdr_sample first)");
+    return 0;
+}
+
+void launch_select_best(qcqpmi_ctx *c, int64_t pops, const double *f0, const double *maxviol, int64_t R, double tol, int64_t *out_idx,
+                        double *out_key) {
+    hipLaunchKernelGGL(select_best_kernel, dim3((unsigned)pops), dim3(1024), 0, c->stream, f0, maxviol, R, tol, out_idx, out_key);
+}
+
+void launch_from_tiles(qcqpmi_ctx *c, const double *Xt, int64_t R) {
+    const int64_t total = R * c->n;
+    hipLaunchKernelGGL(from_tiles_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, c->stream, Xt, c->d_stage, c->n, c->n16, R);
+}
+
+}  // namespace qcqpmi
+
+namespace {
 
 // `count` elements of the problem's own storage: owned by prob_allocs until the context goes
 template <typename T>
@@ -284,12 +108,6 @@ int pop_reserve(qcqpmi_ctx *c, int64_t R) {
     c->Rpad = Rpad;
     c->evaluated = false;
     return 0;
-}
-
-void tic(qcqpmi_ctx *c, int which) { (void)hipEventRecord(c->timers[which].beg, c->stream); }
-void toc(qcqpmi_ctx *c, int which) {
-    (void)hipEventRecord(c->timers[which].end, c->stream);
-    c->timers[which].valid = true;
 }
 
 bool dense_on(const qcqpmi_ctx *c);
@@ -594,13 +412,6 @@ int launch_cd(qcqpmi_ctx *c, const CdArgs &a1, bool phase1, bool &used_lds, bool
     return 0;
 }
 
-int check_ready(qcqpmi_ctx *c, bool need_pop) {
-    if (!c) return QCQPMI_EINVAL;
-    if (!c->finalized) return fail(c, QCQPMI_ESTATE, "qcqpmi_finalize has not been called");
-    if (need_pop && c->R <= 0) return fail(c, QCQPMI_ESTATE, "no resident population (upload / randn / sdr_sample first)");
-    return 0;
-}
-
 }  // namespace
 
 #include "cd_dense_mw.h"
@@ -663,8 +474,6 @@ int cd_run_general(qcqpmi_ctx *c, int phase1, int64_t num_iters, double viol_tol
     return 0;
 }
 
-#include "capi_small.inc"
-
 // ============================================================================================
 
 extern "C" {
@@ -710,7 +519,7 @@ void qcqpmi_ctx_destroy(qcqpmi_ctx *c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
     if (c->stream) (void)spin_sync(c->stream);
-    if (c->comm && rccl() && rccl()->CommDestroy) rccl()->CommDestroy(c->comm);
+    comm_drop(c);
     admm_drop_handle(c);
     for (auto &t : c->timers) { if (t.beg) (void)hipEventDestroy(t.beg); if (t.end) (void)hipEventDestroy(t.end); }
     for (auto &e : c->dn_ev) if (e) (void)hipEventDestroy(e);
@@ -1120,8 +929,7 @@ int qcqpmi_pop_download(qcqpmi_ctx *c, double *X, int64_t R) {
     if (!X || R <= 0 || R > c->R) return fail(c, QCQPMI_EINVAL, "pop_download: bad arguments");
     HIPCHK(c, hipSetDevice(c->device));
     int64_t total = R * c->n;
-    hipLaunchKernelGGL(from_tiles_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, c->stream,
-                       c->X, c->d_stage, c->n, c->n16, R);
+    launch_from_tiles(c, c->X, R);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipMemcpyAsync(X, c->d_stage, (size_t)total * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, spin_sync(c->stream));
@@ -1280,8 +1088,7 @@ int qcqpmi_pop_weighted_product(qcqpmi_ctx *c, const double *w, double *Y) {
     HIPCHK(c, hipFuncSetAttribute((const void *)kg, hipFuncAttributeMaxDynamicSharedMemorySize, DP_LDS_BYTES));
     hipLaunchKernelGGL(kg, dim3((unsigned)((D.NB + DP_FG - 1) / DP_FG), (unsigned)((ntiles + DP_TG - 1) / DP_TG), 1),
                        dim3(256), DP_LDS_BYTES, c->stream, pa);
-    hipLaunchKernelGGL(from_tiles_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, c->stream,
-                       (const double *)dY, c->d_stage, c->n, c->n16, c->R);
+    launch_from_tiles(c, dY, c->R);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipMemcpyAsync(c->h_pin, c->d_stage, (size_t)total * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, spin_sync(c->stream));
@@ -1643,8 +1450,7 @@ int qcqpmi_cd_stream_run(qcqpmi_ctx *c, int64_t K, int64_t R, int generate, int 
         // the best restart of every population (QCQPForm.better folded over it, ties -> lowest index)
         if ((rc = cd_bestK_reserve(c, K))) return rc;
         // one workgroup per population, then one gather of the winners' columns: three launches and three copies whatever K
-        hipLaunchKernelGGL(select_best_kernel, dim3((unsigned)K), dim3(1024), 0, c->stream, (const double *)c->d_f0, (const double *)c->d_mv,
-                           R, select_tol, c->d_bestK_idx, c->d_bestK_key);
+        launch_select_best(c, K, c->d_f0, c->d_mv, R, select_tol, c->d_bestK_idx, c->d_bestK_key);
         if (best_x) {
             HIPCHK(c, hipMemsetAsync(c->d_bestK_x, 0, (size_t)K * c->n * sizeof(double), c->stream));
             hipLaunchKernelGGL(gather_best_x_kernel, dim3((unsigned)K), dim3(256), 0, c->stream, (const double *)c->X, c->n, c->n16, R,
@@ -1722,8 +1528,7 @@ int qcqpmi_select_best(qcqpmi_ctx *c, double tol, int64_t *best_index, double *b
     if (rc) return rc;
     HIPCHK(c, hipSetDevice(c->device));
     if (!c->evaluated && (rc = launch_eval(c, false))) return rc;
-    hipLaunchKernelGGL(select_best_kernel, dim3(1), dim3(1024), 0, c->stream, c->d_f0, c->d_mv, c->R, tol,
-                       c->d_best_idx, c->d_best_key);
+    launch_select_best(c, 1, c->d_f0, c->d_mv, c->R, tol, c->d_best_idx, c->d_best_key);
     HIPCHK(c, hipGetLastError());
     int64_t idx[2];
     double key[2];
@@ -1834,6 +1639,12 @@ int qcqpmi_debug_trace(qcqpmi_ctx *c, int64_t *out, int count) {
     return 0;
 }
 
+int qcqpmi_debug_dense_profile(qcqpmi_ctx *c, int64_t *out64) {
+    if (!c || !out64) return QCQPMI_EINVAL;
+    HIPCHK(c, hipSetDevice(c->device));
+    return dense_profile_read(c, out64);
+}
+
 int qcqpmi_sync(qcqpmi_ctx *c) {
     if (!c) return QCQPMI_EINVAL;
     HIPCHK(c, hipSetDevice(c->device));
@@ -1841,110 +1652,5 @@ int qcqpmi_sync(qcqpmi_ctx *c) {
     return 0;
 }
 
-// ------------------------------------------------------------------------------------- RCCL
-
-#define NCCLCHK(c, expr)                                                                        \
-    do {                                                                                        \
-        ncclResult_t r_ = (expr);                                                               \
-        if (r_ != ncclSuccess)                                                                  \
-            return fail(c, QCQPMI_ECOMM, "%s failed: %s", #expr,                                \
-                        rccl()->GetErrorString ? rccl()->GetErrorString(r_) : "rccl error");    \
-    } while (0)
-
-int qcqpmi_comm_unique_id(uint8_t id_out[128]) {
-    if (!rccl()) return fail(nullptr, QCQPMI_ECOMM, "librccl.so could not be loaded");
-    ncclUniqueId id;
-    if (rccl()->GetUniqueId(&id) != ncclSuccess) return fail(nullptr, QCQPMI_ECOMM, "ncclGetUniqueId failed");
-    memcpy(id_out, id.internal, 128);
-    return 0;
-}
-
-int qcqpmi_comm_init(qcqpmi_ctx *c, int rank, int world, const uint8_t id_in[128]) {
-    if (!c || world < 1 || rank < 0 || rank >= world) return QCQPMI_EINVAL;
-    if (!rccl()) return fail(c, QCQPMI_ECOMM, "librccl.so could not be loaded");
-    HIPCHK(c, hipSetDevice(c->device));
-    ncclUniqueId id;
-    memcpy(id.internal, id_in, 128);
-    NCCLCHK(c, rccl()->CommInitRank(&c->comm, world, id, rank));
-    c->rank = rank; c->world = world;
-    HIPCHK(c, c->d_comm.reserve(c->stream, (size_t)4 * world + 4 + (size_t)c->n));
-    return 0;
-}
-
-int qcqpmi_comm_barrier(qcqpmi_ctx *c) {
-    double v = 0.0;
-    return qcqpmi_comm_allreduce(c, &v, 1, 0);
-}
-
-int qcqpmi_comm_allreduce(qcqpmi_ctx *c, double *values, int64_t count, int op) {
-    if (!c || !values || count < 1 || count > ((int64_t)1 << 28) || op < 0 || op > 1) return QCQPMI_EINVAL;
-    if (!c->comm) return fail(c, QCQPMI_ESTATE, "comm_init has not been called");
-    HIPCHK(c, hipSetDevice(c->device));
-    double *buf = c->d_comm;
-    if (count > 4) {      // the exchange of a streamed run (keys of all populations, then the winners' points): a buffer of its own
-        HIPCHK(c, c->d_comm_big.reserve(c->stream, (size_t)count, false));
-        buf = c->d_comm_big;
-    }
-    HIPCHK(c, hipMemcpyAsync(buf, values, (size_t)count * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    NCCLCHK(c, rccl()->AllReduce(buf, buf, (size_t)count, ncclDouble, op == 0 ? ncclMax : ncclSum, c->comm, c->stream));
-    HIPCHK(c, hipMemcpyAsync(values, buf, (size_t)count * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, spin_sync(c->stream));
-    return 0;
-}
-
-// every rank contributes `nbytes` bytes; everyone receives the world x nbytes bytes in rank order (one ncclAllGather)
-int qcqpmi_comm_allgather(qcqpmi_ctx *c, const void *send, int64_t nbytes, void *recv) {
-    if (!c || !send || !recv || nbytes < 1 || nbytes > ((int64_t)1 << 28)) return QCQPMI_EINVAL;
-    if (!c->comm) return fail(c, QCQPMI_ESTATE, "comm_init has not been called");
-    HIPCHK(c, hipSetDevice(c->device));
-    const int64_t need = ((int64_t)(c->world + 1) * nbytes + 7) / 8;      // doubles: send area + receive area
-    HIPCHK(c, c->d_comm_big.reserve(c->stream, (size_t)need, false));
-    char *d_send = (char *)c->d_comm_big.p, *d_recv = d_send + nbytes;
-    HIPCHK(c, hipMemcpyAsync(d_send, send, (size_t)nbytes, hipMemcpyHostToDevice, c->stream));
-    NCCLCHK(c, rccl()->AllGather(d_send, d_recv, (size_t)nbytes, ncclInt8, c->comm, c->stream));
-    HIPCHK(c, hipMemcpyAsync(recv, d_recv, (size_t)nbytes * (size_t)c->world, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, spin_sync(c->stream));
-    return 0;
-}
-
-int qcqpmi_comm_select_best(qcqpmi_ctx *c, double tol, int64_t index_offset, int64_t *best_global_index,
-                            double *best_f0, double *best_maxviol, double *best_x) {
-    if (!c) return QCQPMI_EINVAL;
-    if (!c->comm) return fail(c, QCQPMI_ESTATE, "comm_init has not been called");
-    int64_t li = -1;
-    double lf = 0.0, lv = 0.0;
-    int rc = qcqpmi_select_best(c, tol, &li, &lf, &lv, nullptr);
-    if (rc) return rc;
-    // key record: (bucket, f0, maxviol, global index) as 4 doubles (indices < 2^53 are exact)
-    double rec[4] = {std::floor(lv / tol), lf, lv, (double)(index_offset + li)};
-    if (!(lv == lv) || !(lf == lf) || li < 0) rec[0] = 9.0e18;
-    const int W = c->world;
-    double *d_send = c->d_comm, *d_recv = c->d_comm + 4, *d_x = c->d_comm + 4 + 4 * (size_t)W;
-    HIPCHK(c, hipMemcpyAsync(d_send, rec, sizeof(rec), hipMemcpyHostToDevice, c->stream));
-    NCCLCHK(c, rccl()->AllGather(d_send, d_recv, 4, ncclDouble, c->comm, c->stream));
-    std::vector<double> all((size_t)4 * W);
-    HIPCHK(c, hipMemcpyAsync(all.data(), d_recv, all.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, spin_sync(c->stream));
-    int win = 0;
-    for (int w = 1; w < W; w++) {
-        const double *a = &all[(size_t)4 * w], *b = &all[(size_t)4 * win];
-        if (a[0] < b[0] || (a[0] == b[0] && (a[1] < b[1] || (a[1] == b[1] && a[3] < b[3])))) win = w;
-    }
-    if (c->rank == win && li >= 0) {
-        const double *src = c->X + (li >> 4) * c->n16 * 16 + (li & 15);
-        HIPCHK(c, hipMemcpy2DAsync(d_x, sizeof(double), src, 16 * sizeof(double), sizeof(double), (size_t)c->n,
-                                   hipMemcpyDeviceToDevice, c->stream));
-    }
-    NCCLCHK(c, rccl()->Broadcast(d_x, d_x, (size_t)c->n, ncclDouble, win, c->comm, c->stream));
-    if (best_x) HIPCHK(c, hipMemcpyAsync(best_x, d_x, (size_t)c->n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, spin_sync(c->stream));
-    if (best_global_index) *best_global_index = (int64_t)all[(size_t)4 * win + 3];
-    if (best_f0) *best_f0 = all[(size_t)4 * win + 1];
-    if (best_maxviol) *best_maxviol = all[(size_t)4 * win + 2];
-    return 0;
-}
-
 }  // extern "C"
 
-#include "capi_admm.inc"
-#include "capi_units.inc"

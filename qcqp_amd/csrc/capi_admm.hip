@@ -1,7 +1,20 @@
-// ADMM part of the C ABI (included by capi.hip): setup (qcqpmi_admm_set_eig / set_basis / setup / zsolver_device),
+// ADMM part of the C ABI: setup (qcqpmi_admm_set_eig / set_basis / setup / zsolver_device),
 // the unit operator qcqpmi_admm_onecons and the iteration qcqpmi_admm_run.  Every product of the iteration goes through
 // the engine's own fp64 GEMM (gemm_pk.h); the algorithm itself is in admm.h.  rocSOLVER -- and the rocBLAS handle it
 // wants -- is loaded lazily for the optional device-side eigendecompositions of qcqpmi_admm_setup only.
+// The one unit that compiles the kernels of admm.h and gemm_pk.h.
+#include <dlfcn.h>
+
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+
+#include "capi_ctx.h"
+#include "admm.h"
+#include "admm_fused.h"
+#include "gemm_pk.h"
+
+using namespace qcqpmi;
 
 namespace {
 
@@ -96,10 +109,14 @@ __global__ void admm_symmetrise_kernel(double *__restrict__ A, int64_t n, int64_
         if (s_ != 0) return fail(c, QCQPMI_EHIP, "%s failed: rocblas status %d", #expr, s_); \
     } while (0)
 
-void admm_drop_handle(qcqpmi_ctx *c) {
+}  // namespace
+
+void qcqpmi::admm_drop_handle(qcqpmi_ctx *c) {
     if (c->rb_handle && rocblas() && rocblas()->destroy) rocblas()->destroy(c->rb_handle);
     c->rb_handle = nullptr;
 }
+
+namespace {
 
 // drops the installed basis; ad_Minvpk stays: a new basis does not invalidate (2 (P0 + rho m I))^-1
 void admm_free(qcqpmi_ctx *c) {
@@ -474,7 +491,7 @@ int qcqpmi_admm_onecons(qcqpmi_ctx *c, int64_t k, double *out) {
     }
     HIPCHK(c, hipGetLastError());
     const int64_t total = R * c->n;
-    hipLaunchKernelGGL(from_tiles_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, c->stream, (const double *)Xo.p, c->d_stage, c->n, c->n16, R);
+    launch_from_tiles(c, Xo.p, R);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipMemcpyAsync(out, c->d_stage, (size_t)total * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, spin_sync(c->stream));
@@ -850,12 +867,6 @@ int qcqpmi_debug_admm_profile(qcqpmi_ctx *c, int64_t *out16) {
     if (!c || !out16) return QCQPMI_EINVAL;
     for (int k = 0; k < 16; k++) out16[k] = (int64_t)c->af_prof[k];
     return 0;
-}
-
-int qcqpmi_debug_dense_profile(qcqpmi_ctx *c, int64_t *out64) {
-    if (!c || !out64) return QCQPMI_EINVAL;
-    HIPCHK(c, hipSetDevice(c->device));
-    return dense_profile_read(c, out64);
 }
 
 const char *qcqpmi_last_admm_kernel(qcqpmi_ctx *c, int *workgroups_per_tile) {

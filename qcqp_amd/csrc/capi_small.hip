@@ -1,7 +1,17 @@
-// Small-problem batch part of the C ABI (included by capi.hip): B small problems over the context's constraint structure in ONE
+// Small-problem batch part of the C ABI: B small problems over the context's constraint structure in ONE
 // persistent launch of cd_small.hip, admm_small.hip or sdr_small.hip.  A call works in a device buffer of its own (sb_work for CD and
 // ADMM, ss_work for SDR): the resident population, its evaluation, its status codes and an installed ADMM basis are not touched,
 // whether the call succeeds or is refused.  The shared steps come first; a driver is its argument struct, its launch and its outputs.
+// Host code only: the three launcher headers, and the launch of the core's selection kernel through capi_ctx.h.
+#include <cmath>
+#include <cstring>
+
+#include "capi_ctx.h"
+#include "cd_small.h"
+#include "admm_small.h"
+#include "sdr_small.h"
+
+using namespace qcqpmi;
 
 namespace {
 
@@ -76,8 +86,7 @@ struct BatchBest {
 int select_batch_best(qcqpmi_ctx *c, const char *name, char *w, const BatchBest &b, const double *f0, const double *maxviol, const double *X,
                       int64_t B, int64_t R, int64_t n, double select_tol) {
     if (!b.wanted()) return 0;
-    hipLaunchKernelGGL(select_best_kernel, dim3((unsigned)B), dim3(1024), 0, c->stream, f0, maxviol, R, select_tol, (int64_t *)(w + b.oidx),
-                       (double *)(w + b.okey));
+    launch_select_best(c, B, f0, maxviol, R, select_tol, (int64_t *)(w + b.oidx), (double *)(w + b.okey));
     HIPCHK(c, hipGetLastError());
     if (b.x) {
         HIPCHK(c, hipMemsetAsync(w + b.ox, 0, (size_t)B * n * 8, c->stream));

@@ -1,9 +1,14 @@
-// Unit operators of the C ABI (included by capi.hip): the reference's module-level helpers
+// Unit operators of the C ABI: the reference's module-level helpers
 // get_feasible_intervals (utilities.py:198-232) and onevar_qcqp (utilities.py:241-288) evaluated ON THE
 // DEVICE for a batch of independent cases, by exactly the device functions the coordinate-descent
 // kernels inline (onevar.h).  They exist so that the golden vectors captured from the reference for
 // these two functions (tests/golden/g3_intervals, g4_onevar_qcqp) are checked against the GPU code
 // itself and not only through whole trajectories.
+#include "capi_ctx.h"
+#include "onevar.h"
+#include "cd_general.h"      // gen_onevar_t2t1, gen_onevar_t0: the two device functions only, no kernel of it is instantiated here
+
+using namespace qcqpmi;
 
 namespace {
 

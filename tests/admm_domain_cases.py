@@ -1,6 +1,6 @@
 """What tests/test_admm_domain_cpu.py and tests/test_gpu_admm_domain.py share: a plain reference of onecons_qcqp IN A BASIS
 (utilities.py:149-196 as csrc/admm.h evaluates it), the DERIVED rounding bound the device is held to, a restatement of the launch
-conditions of csrc/capi_admm.inc (admm_launch_secular, gemm_pk, gemm_zsplit), the seeded generators and the case tables.  A plain
+conditions of csrc/capi_admm.hip (admm_launch_secular, gemm_pk, gemm_zsplit), the seeded generators and the case tables.  A plain
 module, not a conftest, and it imports no GPU code.
 
 REFERENCE (onecons_basis).  Given the eigenvalues lam, qhat = B q, r, the relop, the bracket (slo, ehi) and vhat = B z of ONE
@@ -76,7 +76,7 @@ ALL_SECULAR = ['small<%d>' % r for r in SMALL_ROWS] + ['wave<%d,%d>' % (e, w) fo
 
 
 def secular_instantiation(rows, lowrank):
-    """admm_launch_secular (csrc/capi_admm.inc): which kernel solves the secular equations; None = refused."""
+    """admm_launch_secular (csrc/capi_admm.hip): which kernel solves the secular equations; None = refused."""
     if lowrank and rows <= 8:
         return 'small<%d>' % rows if rows in SMALL_ROWS else None
     for lim, epl, nw in WAVE_LIMITS:

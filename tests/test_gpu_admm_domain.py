@@ -1,4 +1,4 @@
-"""The multi-launch ADMM path (csrc/admm.h, csrc/gemm_pk.h, csrc/capi_admm.inc) over its dispatch domain, the fused kernel switched
+"""The multi-launch ADMM path (csrc/admm.h, csrc/gemm_pk.h, csrc/capi_admm.hip) over its dispatch domain, the fused kernel switched
 off: every instantiation admm_launch_secular can choose, both tilings of the GEMM, the split planes of both products, both
 reductions of the violation -- against a longdouble reference and a derived bound, and against the oracle.
 

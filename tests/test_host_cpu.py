@@ -837,12 +837,89 @@ def test_build_units_cover_every_source_file():
             assert _build._stale(obj, _build._unit_deps('cd_life.hip'))
         finally:
             os.utime(hdr, (st.st_atime, st.st_mtime))
+    # the ADMM host code is a unit of its own: an edit to it, or to the kernel header only it includes, makes that unit stale
+    # and leaves the object of capi.hip current
+    objs = [_build._obj(u) for u in _build.TRANSLATION_UNITS]
+    if all(os.path.exists(o) for o in objs):
+        newest = max(os.path.getmtime(o) for o in objs)
+        before = set(_build.stale_units())
+        for name in ('capi_admm.hip', 'admm.h'):
+            path = os.path.join(_build.SRC, name)
+            st = os.stat(path)
+            try:
+                os.utime(path, (st.st_atime, newest + 10))
+                assert set(_build.stale_units()) == before | {'capi_admm.hip'}, name
+                assert _build.needs_build()
+            finally:
+                os.utime(path, (st.st_atime, st.st_mtime))
+
+
+def test_every_kernel_is_compiled_into_one_unit():
+    """A kernel is launched only from the unit that compiles it: the host stub of a kernel (its __device_stub__ symbol) is defined
+    in exactly one object of the in-tree build.  A template kernel instantiated in two units would be compiled twice and register
+    one stub from two code objects; a plain one would not link."""
+    import shutil
+    from qcqp_amd import _build
+    objs = [_build._obj(u) for u in _build.TRANSLATION_UNITS]
+    if not shutil.which('nm') or not all(os.path.exists(o) for o in objs):
+        pytest.skip('no nm / no objects of an in-tree build')
+    owner, shared = {}, []
+    for o in objs:
+        out = subprocess.run(['nm', '--defined-only', o], stdout=subprocess.PIPE, check=True).stdout.decode()
+        stubs = {line.split()[-1] for line in out.splitlines() if '__device_stub__' in line}
+        if os.path.basename(o) == 'capi.o':
+            assert stubs, 'capi.o defines no kernel stub: is nm reading the objects?'
+        for s in stubs:
+            if s in owner:
+                shared.append((s, owner[s], os.path.basename(o)))
+            owner[s] = os.path.basename(o)
+    assert not shared, shared
+
+
+def test_only_the_owning_unit_reaches_a_kernel_header():
+    """The seams of the C ABI's host side: capi_small.hip and capi_comm.hip are host code (nothing they are built from defines a
+    kernel), rccl/rccl.h is included by capi_comm.hip alone, and the kernels of admm.h and gemm_pk.h are compiled into
+    capi_admm.hip alone."""
+    from qcqp_amd import _build
+    for unit in ('capi_small.hip', 'capi_comm.hip'):
+        with_kernel = [os.path.basename(p) for p in _build.unit_sources(unit) if '__global__' in open(p).read()]
+        assert not with_kernel, (unit, with_kernel)
+    text = {f: open(os.path.join(_build.SRC, f)).read() for f in os.listdir(_build.SRC) if f.endswith(('.hip', '.h', '.inc'))}
+    assert sorted(f for f, t in text.items() if re.search(r'^\s*#\s*include\s*<rccl/', t, re.M)) == ['capi_comm.hip']
+    for hdr in ('admm.h', 'gemm_pk.h'):
+        reach = sorted(u for u in _build.TRANSLATION_UNITS if os.path.join(_build.SRC, hdr) in _build.unit_sources(u))
+        assert reach == ['capi_admm.hip'], (hdr, reach)
+
+
+def test_errors_without_a_context_share_one_slot():
+    """qcqpmi_last_error(NULL) returns the message of the last call that failed without a context, whichever unit of the library
+    that call lives in: the context constructor (capi.hip) and a unit operator (capi_units.hip) refuse bad arguments before they
+    touch a device, each with its own message, in both orders.  (A copy of the slot per unit would keep returning the core's.)"""
+    from qcqp_amd import _ffi
+    L = _ffi.lib()
+    h = ctypes.c_void_p()
+
+    z = np.zeros(5)
+    zi = np.zeros(1, dtype=np.int32)
+
+    def core():
+        assert L.qcqpmi_ctx_create(ctypes.byref(h), 0, 1, 0) == -1
+        assert L.qcqpmi_last_error(None) == b'ctx_create: bad arguments'
+
+    def unit():
+        assert L.qcqpmi_feasible_intervals_batch(0, 0, z.ctypes.data_as(_ffi.c_dp), zi.ctypes.data_as(ctypes.POINTER(ctypes.c_int)),
+                                                 z.ctypes.data_as(_ffi.c_dp)) == -1
+        assert L.qcqpmi_last_error(None) == b'feasible_intervals_batch: bad arguments'
+
+    for call in (core, unit, core, unit, unit, core):
+        call()
 
 
 def test_every_header_compiles_on_its_own(tmp_path):
     """A header that needs something its includer happens to provide forces every new includer to fake it (cd_phase2.h once named
     a function of the file that included it: three units carried stand-in definitions).  Each csrc/*.h is compiled alone, device
-    side, syntax only, with the build's flags; the .inc files are fragments of capi.hip by design."""
+    side, syntax only, with the build's flags; capi_dense.inc is a fragment of capi.hip by design (the dense path and the core call
+    each other)."""
     from concurrent.futures import ThreadPoolExecutor
     from qcqp_amd import _build
     hipcc = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')

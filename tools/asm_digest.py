@@ -19,19 +19,22 @@ sys.path.insert(0, REPO)
 
 _BEGIN = re.compile(r'-- Begin function (\S+)')
 _END = re.compile(r'-- End function')
-_LOCAL = re.compile(r'\.L([A-Za-z_]+?)(\d+)(?=_\d|\b)')
+_LOCAL = re.compile(r'(\.L[A-Za-z_]+?|\bBB)(\d+)(?=_\d|\b)')     # (BB12_3 without .L: the loop comments of the assembly printer)
+_PAD = re.compile(r'\s+;')
 _SKIP = re.compile(r'^\s*\.(file|ident)\b|__hip_cuid_')
 
 
 def _sha(lines):
-    """Digest of a block of lines with its local labels (.LBB12_3, .Lfunc_end12, ...) renumbered by first appearance."""
+    """Digest of a block of lines with its local labels (.LBB12_3, .Lfunc_end12, ...) renumbered by first appearance.  The
+    function's number also stands in the printer's loop comments ("Header=BB12_3"), and its width sets the padding in front of
+    them: a kernel that is the 99th function of one unit and the 100th of another has the same code."""
     seen = {}
 
     def renumber(m):
         key = (m.group(1), m.group(2))
-        return '.L%s%d' % (m.group(1), seen.setdefault(key, len(seen)))
+        return '%s%d' % (m.group(1), seen.setdefault(key, len(seen)))
 
-    return hashlib.sha256('\n'.join(_LOCAL.sub(renumber, l) for l in lines).encode()).hexdigest()[:16]
+    return hashlib.sha256('\n'.join(_PAD.sub(' ;', _LOCAL.sub(renumber, l)) for l in lines).encode()).hexdigest()[:16]
 
 
 def assembly(path, include):
