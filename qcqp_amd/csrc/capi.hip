@@ -1,9 +1,9 @@
 // C ABI of libqcqp_mi.so (declared in include/qcqp_mi.h): context, problem upload, population
 // management, launches of the kernels in kernels_impl.h, HIP-event timing.  The core of the host side: the ADMM calls are in
-// capi_admm.hip, the small-problem batch calls in capi_small.hip, the unit operators in capi_units.hip, RCCL in capi_comm.hip;
-// capi_ctx.h holds what these units share.
+// capi_admm.hip, the small-problem batch calls in capi_small.hip, the unit operators in capi_units.hip, RCCL in capi_comm.hip, the
+// streamed coordinate descent (qcqpmi_cd_stream_run and what it needs: host code only) in capi_stream.hip; capi_ctx.h holds what
+// these units share.
 #include <algorithm>
-#include <chrono>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -84,32 +84,6 @@ void free_population(qcqpmi_ctx *c) {
     c->Rcap = 0;
 }
 
-int pop_reserve(qcqpmi_ctx *c, int64_t R) {
-    if (R <= 0) return fail(c, QCQPMI_EINVAL, "population size must be positive");
-    int64_t Rpad = (R + 15) / 16 * 16;
-    if (Rpad > c->Rcap) {
-        HIPCHK(c, spin_sync(c->stream));
-        free_population(c);
-        const size_t Rp = (size_t)Rpad;
-        HIPCHK(c, c->X.reserve(c->stream, Rp * (size_t)c->n16));
-        HIPCHK(c, c->d_stage.reserve(c->stream, Rp * (size_t)c->n));
-        HIPCHK(c, c->d_f0.reserve(c->stream, Rp));
-        HIPCHK(c, c->d_mv.reserve(c->stream, Rp));
-        HIPCHK(c, c->d_visits.reserve(c->stream, Rp));
-        HIPCHK(c, c->d_acc.reserve(c->stream, Rp));
-        HIPCHK(c, c->d_sweeps.reserve(c->stream, Rp));
-        HIPCHK(c, c->d_sweeps1.reserve(c->stream, Rp));
-        HIPCHK(c, c->d_status.reserve(c->stream, Rp));
-        HIPCHK(c, c->d_status1.reserve(c->stream, Rp));
-        HIPCHK(c, c->d_flag.reserve(c->stream, Rp));
-        c->Rcap = Rpad;
-    }
-    c->R = R;
-    c->Rpad = Rpad;
-    c->evaluated = false;
-    return 0;
-}
-
 bool dense_on(const qcqpmi_ctx *c);
 int launch_eval_dense(qcqpmi_ctx *c, bool with_Ft);
 int eval_parts_dense(qcqpmi_ctx *c);
@@ -137,18 +111,40 @@ int pin_reserve(qcqpmi_ctx *c, size_t bytes) {
     return 0;
 }
 
+}  // namespace
+
+namespace qcqpmi {
+
+int pop_reserve(qcqpmi_ctx *c, int64_t R) {
+    if (R <= 0) return fail(c, QCQPMI_EINVAL, "population size must be positive");
+    int64_t Rpad = (R + 15) / 16 * 16;
+    if (Rpad > c->Rcap) {
+        HIPCHK(c, spin_sync(c->stream));
+        free_population(c);
+        const size_t Rp = (size_t)Rpad;
+        HIPCHK(c, c->X.reserve(c->stream, Rp * (size_t)c->n16));
+        HIPCHK(c, c->d_stage.reserve(c->stream, Rp * (size_t)c->n));
+        HIPCHK(c, c->d_f0.reserve(c->stream, Rp));
+        HIPCHK(c, c->d_mv.reserve(c->stream, Rp));
+        HIPCHK(c, c->d_visits.reserve(c->stream, Rp));
+        HIPCHK(c, c->d_acc.reserve(c->stream, Rp));
+        HIPCHK(c, c->d_sweeps.reserve(c->stream, Rp));
+        HIPCHK(c, c->d_sweeps1.reserve(c->stream, Rp));
+        HIPCHK(c, c->d_status.reserve(c->stream, Rp));
+        HIPCHK(c, c->d_status1.reserve(c->stream, Rp));
+        HIPCHK(c, c->d_flag.reserve(c->stream, Rp));
+        c->Rcap = Rpad;
+    }
+    c->R = R;
+    c->Rpad = Rpad;
+    c->evaluated = false;
+    return 0;
+}
+
 // staging buffers (device + pinned host) of fetch_cd_outputs for R restarts
 int cd_outputs_reserve(qcqpmi_ctx *c, int64_t R) {
     HIPCHK(c, c->d_out.reserve(c->stream, (size_t)(57 * R), false));
     HIPCHK(c, c->h_out.reserve(c->stream, (size_t)(57 * R), false));
-    return 0;
-}
-
-// device buffers of the per-population winners of a streamed run (K populations)
-int cd_bestK_reserve(qcqpmi_ctx *c, int64_t K) {
-    HIPCHK(c, c->d_bestK_idx.reserve(c->stream, (size_t)K * 2, false));
-    HIPCHK(c, c->d_bestK_key.reserve(c->stream, (size_t)K * 2, false));
-    HIPCHK(c, c->d_bestK_x.reserve(c->stream, (size_t)K * c->n, false));
     return 0;
 }
 
@@ -212,6 +208,28 @@ int cd_apply_status(qcqpmi_ctx *c, const std::vector<int> &st, const std::vector
     return fail(c, QCQPMI_EREFERENCE, "phase 2: the reference raises on restart %lld (code %d: unbounded interval with zero objective / NameError in OneVarQuadraticFunction.eval)", (long long)r, s2);
 }
 
+void cd_queue_fill_batch(qcqpmi_ctx *c, CdBatch &B, uint64_t seed, uint64_t first_index) {
+    B.X = c->X; B.f0cur = c->d_f0; B.slack = c->d_mv; B.flag = c->d_flag; B.visits = c->d_visits; B.accepted = c->d_acc;
+    B.sweeps = c->d_sweeps; B.status = c->d_status; B.f0out = c->d_f0; B.mvout = c->d_mv; B.R = c->R; B.seed = seed;
+    B.first_index = first_index; B.next = c->d_qnext;
+}
+
+// does the round-4 slot-queue kernel take the problem's shape?  (the switches are the caller's: cd_queue_eligible for qcqpmi_cd_run,
+// stream_plan for the lifecycle mode of qcqpmi_cd_stream_run)
+bool cd_queue_shape_ok(const qcqpmi_ctx *c) {
+    if (!c->sep || c->maxc > 1) return false;
+    if (!(c->K == 1 && c->objclass == 1 && c->symcls && c->n % 16 == 0)) return false;
+    return cd_queue_lds_bytes(c->dp) != 0 && c->R < (1LL << 30);
+}
+
+void launch_gather_best_x(qcqpmi_ctx *c, int64_t pops, int64_t R, const int64_t *idx, double *out) {
+    hipLaunchKernelGGL(gather_best_x_kernel, dim3((unsigned)pops), dim3(256), 0, c->stream, (const double *)c->X, c->n, c->n16, R, idx, out);
+}
+
+}  // namespace qcqpmi
+
+namespace {
+
 int launch_eval(qcqpmi_ctx *c, bool want_F) {
     if (dense_on(c)) return launch_eval_dense(c, false);   // coupled constraints: every function on the matrix cores
     if (want_F) HIPCHK(c, c->d_F.reserve(c->stream, (size_t)((c->m + 1) * c->Rpad)));
@@ -245,9 +263,8 @@ int launch_eval(qcqpmi_ctx *c, bool want_F) {
 
 // does phase 2 of the resident population go through the slot-queue kernel?
 bool cd_queue_eligible(qcqpmi_ctx *c, bool profiling) {      // the problem's shape and the context's switches allow the kernel
-    if (profiling || c->force_generic || (c->dbg & 64) || !c->sep || c->maxc > 1 || c->cd_queue == 0) return false;
-    if (!(c->K == 1 && c->objclass == 1 && c->symcls && c->n % 16 == 0)) return false;
-    return cd_queue_lds_bytes(c->dp) != 0 && c->R < (1LL << 30);
+    if (profiling || c->force_generic || (c->dbg & 64) || c->cd_queue == 0) return false;
+    return cd_queue_shape_ok(c);
 }
 
 bool cd_queue_applies(qcqpmi_ctx *c, bool profiling) {
@@ -272,12 +289,6 @@ int cd_queue_prepare(qcqpmi_ctx *c) {
     return 0;
 }
 
-void cd_queue_fill_batch(qcqpmi_ctx *c, CdBatch &B, uint64_t seed, uint64_t first_index) {
-    B.X = c->X; B.f0cur = c->d_f0; B.slack = c->d_mv; B.flag = c->d_flag; B.visits = c->d_visits; B.accepted = c->d_acc;
-    B.sweeps = c->d_sweeps; B.status = c->d_status; B.f0out = c->d_f0; B.mvout = c->d_mv; B.R = c->R; B.seed = seed;
-    B.first_index = first_index; B.next = c->d_qnext;
-}
-
 template <int MAXC>
 int launch_cd(qcqpmi_ctx *c, const CdArgs &a1, bool phase1, bool &used_lds, bool *used_rs = nullptr) {
     if (used_rs) *used_rs = false;
@@ -300,11 +311,8 @@ int launch_cd(qcqpmi_ctx *c, const CdArgs &a1, bool phase1, bool &used_lds, bool
         size_t q_lds = ((size_t)RQ_LDS_COMMON + (size_t)c->n16 * 16) * sizeof(double);
         if (q_lds < RQ_LDS_MIN) q_lds = RQ_LDS_MIN;
         const int NBq = (int)(c->n16 / 16);
-        int cs = (c->dbg & 128) ? ((c->dbg >> 8) & 7) : 4;     // debug knob: blocks of the contraction the chain wave multiplies
-        cs = cs > RQ_CSMAX ? RQ_CSMAX : cs;
-        if (cs >= NBq) cs = 0;
-        cs &= ~1;
-        if (cd_queue_applies(c, a1.prof != nullptr) && NBq - cs <= RQ_NSIMD * RQ_MAXU && NBq >= 3) {
+        const int cs = chain_share(NBq, c->dbg);
+        if (cd_queue_applies(c, a1.prof != nullptr) && chain_range_ok(NBq, cs)) {
             // restart-level scheduling (cd_queue.h): 16 slots per workgroup, refilled from a device-side queue
             used_lds = true;
             int rcq;
@@ -325,7 +333,7 @@ int launch_cd(qcqpmi_ctx *c, const CdArgs &a1, bool phase1, bool &used_lds, bool
             if (used_rs) *used_rs = true;
             return 0;
         }
-        if (q_lds <= 160 * 1024 && NBq - cs <= RQ_NSIMD * RQ_MAXU && NBq >= 3) {
+        if (q_lds <= 160 * 1024 && chain_range_ok(NBq, cs)) {
             used_lds = true;
             const bool prof_ = a1.prof != nullptr;
             auto k = cd_phase2_q_kernel<4, false>;
@@ -1256,261 +1264,6 @@ int qcqpmi_cd_dense_block_step(qcqpmi_ctx *c, int phase, int64_t sweep, int64_t 
     return cd_dense_block_step(c, phase, sweep, block, coord_lo, coord_hi, viol_tol, tol, seed, first_index, slack);
 }
 
-// buffers of cd_life_kernel: the workgroups' X tiles, the staged diagonal blocks (packed once per problem), the watchdog word
-static int cd_life2_reserve(qcqpmi_ctx *c, int nmw, int cus) {
-    const size_t need = (size_t)cd_life2_max_wgs(nmw, cus, 1) * (size_t)c->n16 * 16;      // (two tiles per workgroup: half the workgroups, the same tiles)
-    HIPCHK(c, c->l2_scratch.reserve(c->stream, need));
-    HIPCHK(c, c->l2_abort.reserve(c->stream, 4));
-    HIPCHK(c, c->l2_cuslot.reserve(c->stream, 4096));
-    if (!c->l2_S) {      // (the second of the pair: a call that failed between the two starts over)
-        const size_t NB = (size_t)(c->n16 / 16);
-        HIPCHK(c, c->l2_D.reserve(c->stream, NB * 256));
-        HIPCHK(c, c->l2_S.reserve(c->stream, NB * 48));
-        hipError_t e = (hipError_t)cd_life2_pack(c->dp, c->l2_D, c->l2_S, c->stream);
-        if (e != hipSuccess) return fail(c, QCQPMI_EHIP, "cd_life2_pack: %s", hipGetErrorString(e));
-    }
-    return 0;
-}
-
-// Preloaded restarts of a prebuilt factored run of KR restarts (CdLife::y0_count): the leading ones, as many as QCQPMI_L2_Y0_MAX allows
-// (unset: all; 0: none -- every restart takes its loading sweep inside the launch, the A / B reference) and as fit L2_Y0_BUDGET bytes of
-// Y0 (whole tiles of 16 restarts x 16 RB rows; the headline's 81 920 restarts at rank 256 take 168 MB).  The rest load in-kernel: the
-// same bits either way, no second code path.
-constexpr int64_t L2_Y0_BUDGET = (int64_t)2 << 30;
-static int64_t cd_life2_y0_count(int64_t KR, int RB) {
-    int64_t cnt = KR;
-    if (const char *ev = getenv("QCQPMI_L2_Y0_MAX")) { const long long m = atoll(ev); cnt = m < 0 ? 0 : (m < cnt ? m : cnt); }
-    const int64_t fit = L2_Y0_BUDGET / ((int64_t)RB * 16 * 16 * (int64_t)sizeof(double)) * 16;
-    return cnt < fit ? cnt : fit;
-}
-
-// buffers of the pre-passes of a prebuilt factored run of KR restarts: the slacks (cd_life_prep_kernel) and Y0 (cd_life_y0_kernel)
-static int cd_life2_pre_reserve(qcqpmi_ctx *c, int64_t KR, int RB) {
-    HIPCHK(c, c->l2_preslack.reserve(c->stream, (size_t)KR));
-    const size_t need = (size_t)((cd_life2_y0_count(KR, RB) + 15) / 16) * (size_t)RB * 256;
-    HIPCHK(c, c->l2_y0.reserve(c->stream, need, false));      // (every element a restart reads is written by the pre-pass)
-    return 0;
-}
-
-// ---- lifecycle run: K populations of R restarts through ONE persistent slot-queue launch (cd_queue.h, CdLife)
-// Takes (cd_life2_config): separable constraints, up to four classes with up to two constraints per coordinate on a diagonal of P0 that is
-// positive everywhere or zero everywhere; ONE class with one constraint per coordinate on a diagonal of mixed sign (round 7, the SGN
-// kind: no objective factor); 33 <= n <= 2304 (<= 4096 with a factor).  Anything else: QCQPMI_EUNSUPPORTED, nothing touched.
-int qcqpmi_cd_stream_run(qcqpmi_ctx *c, int64_t K, int64_t R, int generate, int phase1, int64_t num_iters, double viol_tol, double tol,
-                         uint64_t seed, uint64_t seed_stride, uint64_t first_index, uint64_t first_stride, double select_tol,
-                         int64_t *sweeps1, int64_t *sweeps2, int64_t *visits2, int64_t *accepted2, uint8_t *ran_phase2, double *f0,
-                         double *maxviol, int64_t *best_index, double *best_f0, double *best_maxviol, double *best_x) {
-    int rc = check_ready(c, generate ? false : true);
-    if (rc) return rc;
-    if (K < 1 || R < 1 || num_iters < 0 || !(tol > 0.0) || K * R >= (1LL << 30)) return fail(c, QCQPMI_EINVAL, "cd_stream_run: bad K / R / num_iters / tol");
-    if (!generate && c->R != K * R) return fail(c, QCQPMI_EINVAL, "cd_stream_run: the resident population has %lld points, K R = %lld", (long long)c->R, (long long)(K * R));
-    HIPCHK(c, hipSetDevice(c->device));
-    // QCQPMI_STREAM_TIMING=1: host-side wall clock of the call's stages on stderr (set-up, kernel, fetch, status, best)
-    const bool stt = getenv("QCQPMI_STREAM_TIMING") != nullptr;
-    double stm[6] = {0, 0, 0, 0, 0, 0};
-    auto stnow = []() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-    stm[0] = stnow();
-    // ---- which kernel (decided BEFORE the resident population is touched: a refused call leaves the context as it was)
-    int nmw = 0, cs2 = 0, kind = 0;
-    const int factor_rb = (c->lr_RB > 0 && c->life_version != 3 && cd_life2_factor_ok(c->dp, 16 * (int64_t)c->lr_RB)) ? c->lr_RB : 0;
-    bool use2 = c->life_version != 1 && !c->force_generic && !(c->dbg & 64) && c->sep &&
-                cd_life2_config(c->dp, c->Kreal, c->objclass, c->symcls, factor_rb, &nmw, &cs2, &kind);
-    int cs = 0;
-    const int queue_switch = c->cd_queue;
-    c->cd_queue = 2;                                   // (qcqpmi_cd_queue chooses the phase-2 kernel of qcqpmi_cd_run; it does not apply here)
-    const bool eligible = cd_queue_eligible(c, false) && (int)(c->n16 / 16) - 4 <= RQ_NSIMD * RQ_MAXU && c->n16 >= 48;
-    c->cd_queue = queue_switch;
-    // ONE lifecycle kernel (round 6): cd_life_kernel takes every shape the round-4 kernel (cd_phase2_qs_kernel<CS, lifecycle>, cd_queue.hip)
-    // takes and more; the shape rule of round 5 (the round-4 kernel from n = 960 on for runs beyond 8192 restarts, where it is 12 % faster
-    // on a FULL-rank objective: profiles/r05_life_vs_round4.md) is gone -- the headline family has a low-rank objective and runs the
-    // factored instantiation, 1.3 x faster than either (profiles/r06_summary.md).  qcqpmi_cd_life_version(1) still launches the round-4
-    // kernel: a debug switch, kept as the independent implementation the tests compare against.
-    // factored objective (qcqpmi_cd_set_objective_factor): cd_life_kernel's products through Y = L^T X -- half the matrix work and less
-    // per block interval, a positive diagonal (band / gen kinds), three multiplying waves per tile
-    const bool lr = use2 && factor_rb > 0 && nmw == 3 && (kind == L2_KIND_BAND || kind == L2_KIND_GEN);
-    if (lr) cs2 = 0;
-    if (!use2) {
-        if (!eligible || c->life_version != 1)
-            return fail(c, QCQPMI_EUNSUPPORTED, "cd_stream_run: the lifecycle kernel needs separable constraints -- at most four classes of coordinates, at most two constraints "
-                        "per coordinate --, a diagonal of P0 that is positive everywhere or zero everywhere (a diagonal of mixed sign: ONE class with one constraint "
-                        "per coordinate only; with several classes or two constraints per coordinate it runs the serial path), and 33 <= n <= 2304: use qcqpmi_cd_run "
-                        "per population");
-        const int NBq = (int)(c->n16 / 16);
-        cs = (c->dbg & 128) ? ((c->dbg >> 8) & 7) : 4;
-        cs = cs > RQ_CSMAX ? RQ_CSMAX : cs;
-        if (cs >= NBq) cs = 0;
-        cs &= ~1;
-        if (NBq - cs > RQ_NSIMD * RQ_MAXU || NBq < 3) return fail(c, QCQPMI_EUNSUPPORTED, "cd_stream_run: n = %lld outside the range of cd_phase2_qs_kernel (n <= 1024, at least 3 blocks of 16)", (long long)c->n);
-    }
-    if (generate && (rc = pop_reserve(c, K * R))) return rc;
-    HIPCHK(c, c->d_qnext.reserve(c->stream, 16));
-    HIPCHK(c, c->d_life.reserve(c->stream, 1, false));
-    HIPCHK(c, hipMemsetAsync(c->d_qnext, 0, 16 * sizeof(int), c->stream));
-    CdLife L;
-    L.on = 1; L.generate = generate ? 1 : 0; L.phase1 = phase1 ? 1 : 0; L.Rtotal = K * R; L.Rpop = R;
-    L.seed = seed; L.seed_stride = seed_stride; L.first_index = first_index; L.first_stride = first_stride; L.viol_tol = viol_tol;
-    L.sweeps1 = c->d_sweeps1; L.status1 = c->d_status1; L.ran2 = c->d_flag;
-    L.prof = nullptr;
-    // the factored instantiation builds its columns ahead of the launch (cd_life_prep_kernel, every restart of the run at full
-    // occupancy) and its refill only copies them; QCQPMI_L2_PREBUILT=0: the build inside the launch, as before (A / B runs, tests)
-    const char *pre_ev = getenv("QCQPMI_L2_PREBUILT");
-    const bool pre = lr && !(pre_ev && atoi(pre_ev) == 0);
-    L.prebuilt = pre ? 1 : 0; L.preslack = nullptr;
-    L.y0_count = 0; L.y0 = nullptr;
-    if (pre) {
-        // (qcqpmi_cd_stream_reserve has done this for a caller that wants no allocation here)
-        if ((rc = cd_life2_pre_reserve(c, K * R, factor_rb))) return rc;
-        L.preslack = c->l2_preslack;
-        L.y0_count = cd_life2_y0_count(K * R, factor_rb);
-        L.y0 = c->l2_y0;
-    }
-    const int64_t y0_count = L.y0_count;
-    if (c->profile) {      // qcqpmi_debug_profile: tick sums of the launch (qcqpmi_debug_life_profile)
-        HIPCHK(c, c->d_life_prof.reserve(c->stream, 24, false));
-        HIPCHK(c, hipMemsetAsync(c->d_life_prof, 0, 24 * sizeof(long long), c->stream));
-        L.prof = c->d_life_prof;
-    }
-    HIPCHK(c, hipMemcpyAsync(c->d_life, &L, sizeof(L), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, spin_sync(c->stream));       // (L lives on this stack frame)
-    int cus = 0;
-    HIPCHK(c, hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device));
-    stm[1] = stnow();
-    if (use2) {
-        if ((rc = cd_life2_reserve(c, nmw, cus))) return rc;
-        if (!lr && (c->dbg & 128)) { const int k2 = (c->dbg >> 8) & 7; if (nmw == 3 && (k2 == 0 || k2 == 2 || k2 == 4) && k2 < (int)(c->n16 / 16)) cs2 = k2; }
-        const int tiles = cd_life2_tiles(c->dp, nmw, cs2, K * R, cus, 0, lr ? 1 : 0);
-        int64_t wgs = (K * R + 16 * tiles - 1) / (16 * tiles);
-        const int maxw = cd_life2_max_wgs(nmw, cus, tiles);
-        if (wgs > maxw) wgs = maxw;
-        if (c->dbg & 1024) { const int lim = (c->dbg >> 12) & 1023; if (lim > 0 && wgs > lim) wgs = lim; }     // debug knob: workgroups of the launch
-        CdLife2Args qa;
-        qa.P = c->dp; qa.num_iters = num_iters; qa.tol = tol; qa.life = c->d_life;
-        cd_queue_fill_batch(c, qa.b, seed, first_index);
-        qa.b.R = K * R;
-        qa.scratch = c->l2_scratch; qa.Dpack = c->l2_D; qa.Spack = c->l2_S; qa.abort = c->l2_abort; qa.fbound = c->fbound;
-        // which of its CU's two workgroups a workgroup is (arrival counter per CU, HW_ID), and what the second one does with it:
-        //   QCQPMI_L2_ROT=2 (the default with the factored objective): it turns its MULTIPLYING roles by one among SIMDs 1-3 -- 16 blocks of Y
-        //   are 6 + 5 + 5 over the three waves, and with both six-block waves on SIMD 1 that SIMD's matrix pipe was 83 % busy and late for
-        //   one product in ten: the chain's wait for partial tiles 0.76 k -> 0.57 k cycles per block interval, the interval 7.45 k -> 7.29 k
-        //   (A / B / A / B on one box: 32.93 / 32.57 / 32.80 / 32.45 ms per 20 x 4096 restarts; same bits);
-        //   QCQPMI_L2_ROT=1: it turns ALL roles by two SIMDs (the two chains on different SIMDs) -- measured SLOWER, 33.2 -> 35.7 ms: a chain
-        //   beside a product stream waits behind the stream's queued matrix instructions (profiles/r06_summary.md);  0: off
-        { const char *ev = getenv("QCQPMI_L2_ROT"); const int rot = ev ? atoi(ev) : (lr ? 2 : 0); qa.cuslot = rot ? c->l2_cuslot : nullptr; qa.rotmode = rot; }
-        if (qa.cuslot) HIPCHK(c, hipMemsetAsync(c->l2_cuslot, 0, 4096 * sizeof(int), c->stream));
-        qa.dbg = (c->dbg & 2048) ? 1 : 0;
-        qa.Gpack = lr ? c->lr_G : nullptr; qa.Upack = lr ? c->lr_U : nullptr; qa.RB = lr ? c->lr_RB : 0;
-        qa.nclass = c->Kreal;
-        const double l0 = stnow();
-        (void)hipEventRecord(c->timers[2].beg, c->stream);       // (the event window spans the pre-pass too)
-        const double l1 = stnow();
-        hipError_t qe = pre ? (hipError_t)cd_life2_prep_launch(c->dp, c->d_life, c->X, K * R, num_iters, tol, c->stream) : hipSuccess;
-        if (qe == hipSuccess && y0_count > 0)
-            qe = (hipError_t)cd_life2_y0_launch(c->X, c->lr_U, c->l2_y0, (int)(c->n16 / 16), factor_rb, c->n16, y0_count, c->stream);
-        if (qe == hipSuccess) qe = (hipError_t)cd_life2_launch(qa, nmw, cs2, kind, tiles, (int)wgs, c->stream);
-        const double l2 = stnow();
-        (void)hipEventRecord(c->timers[2].end, c->stream);
-        c->timers[2].valid = true;
-        if (qe != hipSuccess) return fail(c, QCQPMI_EHIP, "cd_stream_run: %s", hipGetErrorString(qe));
-        c->last_cd2_kernel = cd_life2_name(nmw, kind, tiles, lr ? 1 : 0);
-        int ab = 0;
-        HIPCHK(c, spin_sync(c->stream));
-        const double l3 = stnow();
-        HIPCHK(c, hipMemcpyAsync(&ab, c->l2_abort, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-        const double l4 = stnow();
-        HIPCHK(c, spin_sync(c->stream));
-        if (stt) fprintf(stderr, "cd_stream_run launch (ms): reserve %.3f, event %.3f, launch call %.3f, event + spin wait %.3f, copy call %.3f, sync %.3f\n", l0 - stm[1], l1 - l0, l2 - l1, l3 - l2, l4 - l3, stnow() - l4);
-        if (ab) {
-            HIPCHK(c, hipMemsetAsync(c->l2_abort, 0, sizeof(int), c->stream));
-            c->R = 0;
-            return fail(c, QCQPMI_EHIP, "cd_stream_run: a wait inside cd_life_kernel ran into its watchdog (internal error; no results)");
-        }
-    } else {
-        CdQueueArgs qa;
-        qa.P = c->dp; qa.num_iters = num_iters; qa.tol = tol;
-        qa.life = c->d_life; qa.life_on = 1;
-        cd_queue_fill_batch(c, qa.b, seed, first_index);
-        qa.b.R = K * R;
-        (void)hipEventRecord(c->timers[2].beg, c->stream);
-        hipError_t qe = (hipError_t)cd_queue_launch(qa, cs, cus, c->stream);
-        (void)hipEventRecord(c->timers[2].end, c->stream);
-        c->timers[2].valid = true;
-        if (qe != hipSuccess) return fail(c, QCQPMI_EHIP, "cd_stream_run: %s", hipGetErrorString(qe));
-        HIPCHK(c, spin_sync(c->stream));
-        c->last_cd2_kernel = "cd_phase2_qs_kernel<lifecycle>";
-    }
-    c->cd_stage = 0;
-    c->evaluated = true;                   // d_f0 / d_mv hold the values of the final points
-    if (stt) { (void)spin_sync(c->stream); stm[2] = stnow(); }
-    std::vector<int> st, st1;
-    if ((rc = fetch_cd_outputs(c, sweeps1, sweeps2, visits2, accepted2, ran_phase2, f0, maxviol, st, st1))) return rc;
-    stm[3] = stnow();
-    if ((rc = cd_apply_status(c, st, st1, f0, maxviol, 0))) return rc;
-    stm[4] = stnow();
-    if (best_index || best_f0 || best_maxviol || best_x) {
-        // the best restart of every population (QCQPForm.better folded over it, ties -> lowest index)
-        if ((rc = cd_bestK_reserve(c, K))) return rc;
-        // one workgroup per population, then one gather of the winners' columns: three launches and three copies whatever K
-        launch_select_best(c, K, c->d_f0, c->d_mv, R, select_tol, c->d_bestK_idx, c->d_bestK_key);
-        if (best_x) {
-            HIPCHK(c, hipMemsetAsync(c->d_bestK_x, 0, (size_t)K * c->n * sizeof(double), c->stream));
-            hipLaunchKernelGGL(gather_best_x_kernel, dim3((unsigned)K), dim3(256), 0, c->stream, (const double *)c->X, c->n, c->n16, R,
-                               (const int64_t *)c->d_bestK_idx, c->d_bestK_x);
-        }
-        HIPCHK(c, hipGetLastError());
-        std::vector<int64_t> idx((size_t)K * 2);
-        std::vector<double> key((size_t)K * 2);
-        HIPCHK(c, hipMemcpyAsync(idx.data(), c->d_bestK_idx, idx.size() * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipMemcpyAsync(key.data(), c->d_bestK_key, key.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-        if (best_x) HIPCHK(c, hipMemcpyAsync(best_x, c->d_bestK_x, (size_t)K * c->n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, spin_sync(c->stream));
-        for (int64_t p = 0; p < K; p++) {
-            if (best_index) best_index[p] = idx[(size_t)2 * p];            // index WITHIN the population
-            if (best_f0) best_f0[p] = key[(size_t)2 * p];
-            if (best_maxviol) best_maxviol[p] = key[(size_t)2 * p + 1];
-        }
-    }
-    if (stt) {
-        stm[5] = stnow();
-        fprintf(stderr, "cd_stream_run timing (ms): set-up %.3f, launch + kernel %.3f, fetch %.3f, status %.3f, best %.3f\n", stm[1] - stm[0], stm[2] - stm[1],
-                stm[3] - stm[2], stm[4] - stm[3], stm[5] - stm[4]);
-    }
-    return 0;
-}
-
-int qcqpmi_cd_stream_reserve(qcqpmi_ctx *c, int64_t K, int64_t R) {
-    int rc = check_ready(c, false);
-    if (rc) return rc;
-    if (K < 1 || R < 1 || K * R >= (1LL << 30)) return fail(c, QCQPMI_EINVAL, "cd_stream_reserve: bad K / R");
-    HIPCHK(c, hipSetDevice(c->device));
-    if (K * R > c->Rcap) { if ((rc = pop_reserve(c, K * R))) return rc; }       // (a resident population of that size or more stays)
-    if ((rc = cd_outputs_reserve(c, K * R))) return rc;
-    if ((rc = cd_bestK_reserve(c, K))) return rc;
-    HIPCHK(c, c->d_qnext.reserve(c->stream, 16));
-    HIPCHK(c, c->d_life.reserve(c->stream, 1, false));
-    {
-        int nmw = 0, cs2 = 0, kind = 0, cus = 0;
-        HIPCHK(c, hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device));
-        if (c->life_version != 1 && c->sep && cd_life2_config(c->dp, c->Kreal, c->objclass, c->symcls, c->lr_RB, &nmw, &cs2, &kind) && (rc = cd_life2_reserve(c, nmw, cus))) return rc;
-        // the factored instantiation's pre-passes (the same conditions as qcqpmi_cd_stream_run)
-        const int factor_rb = (c->lr_RB > 0 && c->life_version != 3 && cd_life2_factor_ok(c->dp, 16 * (int64_t)c->lr_RB)) ? c->lr_RB : 0;
-        const bool lr = factor_rb > 0 && c->life_version != 1 && !c->force_generic && !(c->dbg & 64) && c->sep &&
-                        cd_life2_config(c->dp, c->Kreal, c->objclass, c->symcls, factor_rb, &nmw, &cs2, &kind) && nmw == 3 && (kind == L2_KIND_BAND || kind == L2_KIND_GEN);
-        const char *pre_ev = getenv("QCQPMI_L2_PREBUILT");
-        if (lr && !(pre_ev && atoi(pre_ev) == 0) && (rc = cd_life2_pre_reserve(c, K * R, factor_rb))) return rc;
-    }
-    return 0;
-}
-
-int qcqpmi_debug_life_profile(qcqpmi_ctx *c, int64_t *out16) {
-    if (!c || !out16) return QCQPMI_EINVAL;
-    for (int k = 0; k < 24; k++) out16[k] = 0;
-    if (!c->d_life_prof) return 0;
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, spin_sync(c->stream));
-    HIPCHK(c, hipMemcpy(out16, c->d_life_prof, 24 * sizeof(long long), hipMemcpyDeviceToHost));
-    return 0;
-}
-
 int qcqpmi_cd_status(qcqpmi_ctx *c, int *status1, int *status2) {
     if (!c) return QCQPMI_EINVAL;
     if ((int64_t)c->last_st1.size() != c->R || (int64_t)c->last_st2.size() != c->R)
@@ -1549,37 +1302,6 @@ int qcqpmi_select_best(qcqpmi_ctx *c, double tol, int64_t *best_index, double *b
 }
 
 const char *qcqpmi_last_cd_kernel(qcqpmi_ctx *c) { return c ? c->last_cd2_kernel : ""; }
-
-int qcqpmi_cd_set_objective_factor(qcqpmi_ctx *c, const double *L, int64_t r) {
-    int rc = check_ready(c, false);
-    if (rc) return rc;
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, spin_sync(c->stream));
-    c->lr_L.release(); c->lr_G.release(); c->lr_U.release();
-    c->lr_RB = 0;
-    if (!L || r == 0) return 0;                       // cleared
-    if (r < 1 || r > c->n) return fail(c, QCQPMI_EINVAL, "cd_set_objective_factor: r = %lld outside 1 .. n", (long long)r);
-    if (!cd_life2_factor_ok(c->dp, r))
-        return fail(c, QCQPMI_EUNSUPPORTED, "cd_set_objective_factor: the factored lifecycle kernel takes factors of at most 288 columns and n >= 128");
-    const int64_t n = c->n, n16 = c->n16, r16 = (r + 15) / 16 * 16;
-    const int RB = (int)(r16 / 16), NB = (int)(n16 / 16);
-    HIPCHK(c, c->lr_L.reserve(c->stream, (size_t)n16 * r16));      // (zero-filled)
-    HIPCHK(c, c->lr_G.reserve(c->stream, (size_t)NB * RB * 256, false));
-    HIPCHK(c, c->lr_U.reserve(c->stream, (size_t)NB * RB * 256, false));
-    HIPCHK(c, hipMemcpy2DAsync(c->lr_L, (size_t)r16 * sizeof(double), L, (size_t)r * sizeof(double), (size_t)r * sizeof(double), (size_t)n,
-                               hipMemcpyHostToDevice, c->stream));
-    hipError_t e = (hipError_t)cd_life2_pack_factor(c->lr_L, c->lr_G, c->lr_U, NB, RB, c->stream);
-    if (e != hipSuccess) return fail(c, QCQPMI_EHIP, "cd_life2_pack_factor: %s", hipGetErrorString(e));
-    HIPCHK(c, spin_sync(c->stream));      // (the 2-D copy may still be reading the caller's pages)
-    c->lr_RB = RB;
-    return 0;
-}
-
-int qcqpmi_cd_life_version(qcqpmi_ctx *c, int version) {
-    if (!c || version < 0 || version > 3) return QCQPMI_EINVAL;      // (3: cd_life_kernel without the objective factor)
-    c->life_version = version;
-    return 0;
-}
 
 int qcqpmi_cd_queue(qcqpmi_ctx *c, int mode) {
     if (!c || mode < 0 || mode > 2) return QCQPMI_EINVAL;

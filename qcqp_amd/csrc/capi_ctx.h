@@ -1,5 +1,5 @@
 // Internal header of the host side of the C ABI: what two or more of its units (capi.hip, capi_admm.hip, capi_small.hip,
-// capi_units.hip, capi_comm.hip) need, and nothing else -- the context, the error slot, the event timers and the few host
+// capi_units.hip, capi_comm.hip, capi_stream.hip) need, and nothing else -- the context, the error slot, the event timers and the few host
 // functions one unit calls in another.  Types and host declarations only: no kernel is defined in anything included here,
 // so a unit that includes it compiles device code only for the kernel headers it names itself.
 #pragma once
@@ -11,7 +11,7 @@
 
 #include "../../include/qcqp_mi.h"
 #include "kernels.h"      // DevProblem
-#include "cd_life.h"      // CdLife
+#include "cd_queue.h"     // CdLife, CdBatch
 #include "dev_buf.h"
 
 typedef struct ncclComm *ncclComm_t;      // as rccl/rccl.h declares it: only capi_comm.hip includes that header
@@ -179,13 +179,26 @@ inline void toc(qcqpmi_ctx *c, int which) {
     c->timers[which].valid = true;
 }
 
-// Launches of the two kernels of kernels_impl.h that a unit other than capi.hip needs: enqueued on c->stream, no wait (the
+// Launches of the three kernels of kernels_impl.h that a unit other than capi.hip needs: enqueued on c->stream, no wait (the
 // caller checks hipGetLastError as after any launch).
 // capi.hip: one workgroup per population of R restarts selects its best (out_idx[2 p], out_key[2 p]: select_best_kernel)
 void launch_select_best(qcqpmi_ctx *c, int64_t pops, const double *f0, const double *maxviol, int64_t R, double tol, int64_t *out_idx,
                         double *out_key);
 // capi.hip: R restarts of the tile-major array Xt -> c->d_stage in the host's layout (from_tiles_kernel)
 void launch_from_tiles(qcqpmi_ctx *c, const double *Xt, int64_t R);
+// capi.hip: the columns idx[2 p] of `pops` populations of R restarts of the resident population -> out [pops][n] (gather_best_x_kernel)
+void launch_gather_best_x(qcqpmi_ctx *c, int64_t pops, int64_t R, const int64_t *idx, double *out);
+
+// capi.hip, for the streamed run of capi_stream.hip: the resident population's buffers for R restarts; the staging buffers of
+// fetch_cd_outputs; the per-restart results of a run -> host (one transfer, one wait) and the status policy on them; the restarts a
+// queue launch works on; the shape rule of the round-4 slot-queue kernel
+int pop_reserve(qcqpmi_ctx *c, int64_t R);
+int cd_outputs_reserve(qcqpmi_ctx *c, int64_t R);
+int fetch_cd_outputs(qcqpmi_ctx *c, int64_t *sweeps1, int64_t *sweeps2, int64_t *visits2, int64_t *accepted2, uint8_t *ran_phase2,
+                     double *f0, double *maxviol, std::vector<int> &st, std::vector<int> &st1);
+int cd_apply_status(qcqpmi_ctx *c, const std::vector<int> &st, const std::vector<int> &st1, double *f0, double *maxviol, int seg_cap);
+void cd_queue_fill_batch(qcqpmi_ctx *c, CdBatch &B, uint64_t seed, uint64_t first_index);
+bool cd_queue_shape_ok(const qcqpmi_ctx *c);
 
 void admm_drop_handle(qcqpmi_ctx *c);      // capi_admm.hip: the rocBLAS handle of qcqpmi_admm_setup
 void comm_drop(qcqpmi_ctx *c);             // capi_comm.hip: the communicator of qcqpmi_comm_init

@@ -29,16 +29,9 @@
 #include <stdint.h>
 #include "kernels.h"
 #include "cd_queue.h"
+#include "cd_life_plan.h"      // the step kinds (L2_KIND_*) and the shape rules: cd_life2_config, cd_life2_factor_ok, cd_life2_max_wgs, cd_life2_tiles, cd_life2_name
 
 namespace qcqpmi {
-
-// step kinds.  GENK / LINK (round 6): GEN / LIN for problems with SEVERAL constraint classes (coordinates with different
-// constraint lists: up to four classes) and up to two constraints per coordinate -- the slots keep a feasible set per class, the
-// chain looks its columns' classes up per block
-// SGN: a diagonal of P0 of MIXED sign (a box-constrained QP with an indefinite P0), one class with one constraint per coordinate:
-// the step is the GEN pick where P0[i,i] > 0, the outermost end point on the far side of the vertex where P0[i,i] < 0 (a concave scalar
-// objective), the LIN pick where P0[i,i] == 0; the objective is tracked as an absolute value like LIN's (a frozen sweep first)
-enum { L2_KIND_BAND = 0, L2_KIND_GEN = 1, L2_KIND_LIN = 2, L2_KIND_GENK = 3, L2_KIND_LINK = 4, L2_KIND_SGN = 5 };
 
 struct CdLife2Args {
     DevProblem P;
@@ -63,18 +56,8 @@ struct CdLife2Args {
     int dbg;                     // timing experiments (results INVALID when != 0): 1 = every block row reads the fragments of rows 0..7 (an L2-resident stream)
 };
 
-// does the kernel take this problem?  nmw / cs / kind: the instantiation (multiplying waves 3 | 7, chain share, step kind)
-// objclass: 1 = P0[i,i] > 0 everywhere, 2 = zero everywhere, 0 = anything else (mixed signs: the SGN kind, one class with one
-// constraint per coordinate only, never with a factor)
-// factor_rb: blocks of 16 rows of an objective factor the caller WILL hand over (0: none) -- the factored instantiation keeps Y, not X,
-// in registers, so with a factor the kernel also takes 2304 < n <= 4096 (and prefers three multiplying waves from n = 1040 on)
-bool cd_life2_config(const DevProblem &P, int Kreal, int objclass, bool symcls, int factor_rb, int *nmw, int *cs, int *kind);
 size_t cd_life2_lds_bytes(int nmw, int cs, int tiles, int lr, int kind);
-bool cd_life2_factor_ok(const DevProblem &P, int64_t r);
 int cd_life2_pack_factor(const double *Lrow, double *Gpack, double *Upack, int NB, int RB, hipStream_t st);
-int cd_life2_max_wgs(int nmw, int cus, int tiles);
-// tiles of 16 slots per workgroup (1 | 2) for a run of `restarts` restarts; requested: 0 = automatic
-int cd_life2_tiles(const DevProblem &P, int nmw, int cs, int64_t restarts, int cus, int requested, int lr);
 // masked diagonal blocks + per-block scalars (device, once per problem)
 int cd_life2_pack(const DevProblem &P, double *Dpack, double *Spack, hipStream_t st);
 // the column build of every restart of a run of `life` ahead of the lifecycle launch (sets nothing in `life`: the caller sets
@@ -84,6 +67,5 @@ int cd_life2_prep_launch(const DevProblem &P, const CdLife *life, double *X, int
 // Upack the factor's update fragments (cd_life2_pack_factor), Y0 [ceil(count / 16)][16 RB][16] (the caller sets life->y0_count, life->y0)
 int cd_life2_y0_launch(const double *X, const double *Upack, double *Y0, int NB, int RB, int64_t n16, int64_t count, hipStream_t st);
 int cd_life2_launch(const CdLife2Args &a, int nmw, int cs, int kind, int tiles, int wgs, hipStream_t st);
-const char *cd_life2_name(int nmw, int kind, int tiles, int lr);
 
 }  // namespace qcqpmi

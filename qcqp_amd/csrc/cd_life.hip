@@ -52,9 +52,7 @@ __device__ __attribute__((always_inline)) inline RqOwn l2_own(int NB, int CS, in
 //   TC: the slots' feasible sets [interval][class][slot] (one class; L2_KCL classes of up to three intervals for the multi-class
 //   kinds), clsb 2 x 16 ints: the classes of the staged block's coordinates
 constexpr int L2_SHARED_DOUBLES = 8 + 8 + 16 + 8;
-constexpr int L2_YBMAX = 18;          // blocks of 16 rows of Y a tile can hold: factor rank <= 288
-constexpr int L2_YU = 6;              // ... per multiplying wave (three per tile)
-constexpr int L2_KCL = 4;            // constraint classes of the multi-class kinds (GENK / LINK); up to two constraints per coordinate
+constexpr int L2_YU = 6;              // blocks of 16 rows of Y per multiplying wave (three per tile; L2_YBMAX, cd_life_plan.h, per tile)
 constexpr int l2_tile_doubles(int nmw, int csu, int lr, int kcl = 1, int maxc = 1) {
     return 2 * nmw * 256 + 256 + 256 + 2 * 256 + 2 * 48 + 4 * 256 + csu * 256 + 16 + 8 + 16 * 4 + 8 * 5 + 64 * 10 + 16 * 3 + 8 * 5 + 32 +
            (lr ? L2_YBMAX * 256 + 2 * 256 : 0) +
@@ -1779,13 +1777,6 @@ size_t cd_life2_lds_bytes(int nmw, int cs, int tiles, int lr, int kind) {
     return ((size_t)L2_SHARED_DOUBLES + (size_t)tiles * (size_t)l2_tile_doubles(nmw, cs > 0 ? cs : 1, lr, multi ? L2_KCL : 1, multi ? 2 : 1)) * sizeof(double) + 256;
 }
 
-// can the factored-objective kernel take a factor of r columns for this problem?  (rank, the scratch of the column build)
-bool cd_life2_factor_ok(const DevProblem &P, int64_t r) {
-    const int64_t r16 = (r + 15) / 16 * 16;
-    if (r < 1 || r16 > 16 * L2_YBMAX || P.NB < 8) return false;
-    return true;
-}
-
 int cd_life2_pack_factor(const double *Lrow, double *Gpack, double *Upack, int NB, int RB, hipStream_t st) {
     const int64_t tot = (int64_t)NB * RB * 256;
     hipLaunchKernelGGL(l2_pack_factor_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, Lrow, Gpack, Upack, NB, RB);
@@ -1804,42 +1795,6 @@ int cd_life2_y0_launch(const double *X, const double *Upack, double *Y0, int NB,
     const int64_t waves = (ntiles + L2Y_TW - 1) / L2Y_TW * ((RB + L2Y_BW - 1) / L2Y_BW);
     hipLaunchKernelGGL(cd_life_y0_kernel, dim3((unsigned)((waves + L2Y_NT / 64 - 1) / (L2Y_NT / 64))), dim3(L2Y_NT), 0, st, X, Upack, Y0, NB, RB, (int)ntiles, n16);
     return (int)hipGetLastError();
-}
-
-int cd_life2_max_wgs(int nmw, int cus, int tiles) { return (nmw == 3 && tiles == 1) ? 2 * cus : cus; }
-
-bool cd_life2_config(const DevProblem &P, int Kreal, int objclass, bool symcls, int factor_rb, int *nmw, int *cs, int *kind) {
-    // one class with one constraint per coordinate: the BAND / GEN / LIN kinds; up to L2_KCL classes with up to two constraints per
-    // coordinate (every real coordinate constrained): GENK / LINK
-    if (!P.sep || P.maxc < 1 || P.maxc > 2 || Kreal < 1 || Kreal > L2_KCL) return false;
-    const bool multi = P.maxc > 1 || Kreal > 1;
-    // objclass 0 = a diagonal of mixed sign (or zero in places): the SGN kind, one class with one constraint per coordinate only
-    if (objclass != 0 && objclass != 1 && objclass != 2) return false;
-    if (objclass == 0 && multi) return false;
-    const int NB = (int)P.NB;
-    if (NB < 3) return false;
-    int w, c;
-    if (NB <= 4) { w = 3; c = 0; }
-    else if (NB - 4 <= 3 * RQ_MAXU) { w = 3; c = (NB < 8) ? 2 : 4; }
-    else if (factor_rb > 0 && !multi && objclass == 1 && NB <= 256) { w = 3; c = 0; }      // factored: nothing in its registers grows with n
-    else if (NB - 4 <= 7 * RQ_MAXU) { w = 7; c = 4; }
-    else return false;
-    *nmw = w; *cs = c;
-    *kind = objclass == 0 ? L2_KIND_SGN : multi ? (objclass == 2 ? L2_KIND_LINK : L2_KIND_GENK) : objclass == 2 ? L2_KIND_LIN : (symcls ? L2_KIND_BAND : L2_KIND_GEN);
-    return true;
-}
-
-// tiles per workgroup (0 = automatic; QCQPMI_L2_TILES overrides: experiments).  Two tiles per workgroup -- one eight-wave workgroup
-// per CU, joint episodes, the build by 512 threads -- exist for the factored objective only and are NOT the default: measured at
-// n = 1024 (20 x 4096 restarts) 33.7-35.4 ms against 32.6-34.4 ms for two four-wave workgroups per CU, whose column builds overlap
-// the neighbour's products (profiles/r06_summary.md; without a factor: 52.0-53.5 against 49.5-51.0 ms,
-// profiles/r06_headline_experiments.md -- that instantiation was removed).
-int cd_life2_tiles(const DevProblem &P, int nmw, int cs, int64_t restarts, int cus, int requested, int lr) {
-    (void)P; (void)restarts; (void)cus;
-    if (!lr || nmw != 3 || cs != 0) return 1;
-    int t = requested;
-    if (const char *ev = getenv("QCQPMI_L2_TILES")) t = atoi(ev);
-    return t == 2 ? 2 : 1;
 }
 
 int cd_life2_pack(const DevProblem &P, double *Dpack, double *Spack, hipStream_t st) {
@@ -1876,17 +1831,6 @@ int cd_life2_launch(const CdLife2Args &a, int nmw, int cs, int kind, int tiles, 
     }
     if (nmw == 7 && cs == 4) return l2_launch_kind<7, 4, 1, 0>(a, kind, wgs, lds, st);
     return (int)hipErrorInvalidValue;
-}
-
-const char *cd_life2_name(int nmw, int kind, int tiles, int lr) {
-    if (kind == L2_KIND_GENK) return nmw == 3 ? "cd_life_kernel<3,gen,classes>" : "cd_life_kernel<7,gen,classes>";
-    if (kind == L2_KIND_LINK) return nmw == 3 ? "cd_life_kernel<3,lin,classes>" : "cd_life_kernel<7,lin,classes>";
-    if (kind == L2_KIND_SGN) return nmw == 3 ? "cd_life_kernel<3,sgn>" : "cd_life_kernel<7,sgn>";
-    if (lr) return tiles == 2 ? (kind == L2_KIND_BAND ? "cd_life_kernel<3,band,2 tiles,factored>" : "cd_life_kernel<3,gen,2 tiles,factored>")
-                              : (kind == L2_KIND_BAND ? "cd_life_kernel<3,band,factored>" : "cd_life_kernel<3,gen,factored>");
-    if (tiles == 2) return kind == L2_KIND_BAND ? "cd_life_kernel<3,band,2 tiles>" : kind == L2_KIND_GEN ? "cd_life_kernel<3,gen,2 tiles>" : "cd_life_kernel<3,lin,2 tiles>";
-    if (nmw == 3) return kind == L2_KIND_BAND ? "cd_life_kernel<3,band>" : kind == L2_KIND_GEN ? "cd_life_kernel<3,gen>" : "cd_life_kernel<3,lin>";
-    return kind == L2_KIND_BAND ? "cd_life_kernel<7,band>" : kind == L2_KIND_GEN ? "cd_life_kernel<7,gen>" : "cd_life_kernel<7,lin>";
 }
 
 }  // namespace qcqpmi

@@ -870,10 +870,8 @@ int cd_queue_launch(const CdQueueArgs &a, int cs, int max_wgs, hipStream_t st) {
     const size_t lds = cd_queue_lds_bytes(a.P);
     if (!lds) return (int)hipErrorInvalidValue;
     const int NB = (int)a.P.NB;
-    cs = cs > RQ_CSMAX ? RQ_CSMAX : cs;
-    if (cs >= NB) cs = 0;
-    cs &= ~1;
-    if (NB - cs > RQ_NSIMD * RQ_MAXU) return (int)hipErrorInvalidValue;
+    // (the caller's share comes from chain_share: an instantiated one, short of the whole contraction, that leaves the SIMDs what they hold)
+    if (cs < 0 || cs > RQ_CSMAX || (cs & 1) || (cs && cs >= NB) || !chain_range_ok(NB, cs)) return (int)hipErrorInvalidValue;
     auto k = a.life_on ? (cs == 0 ? cd_phase2_qs_kernel<0, true> : cs == 2 ? cd_phase2_qs_kernel<2, true> : cs == 4 ? cd_phase2_qs_kernel<4, true> : cd_phase2_qs_kernel<6, true>)
                        : (cs == 0 ? cd_phase2_qs_kernel<0, false> : cs == 2 ? cd_phase2_qs_kernel<2, false> : cs == 4 ? cd_phase2_qs_kernel<4, false> : cd_phase2_qs_kernel<6, false>);
     hipError_t e = hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);

@@ -6,18 +6,14 @@
 #include <stdint.h>
 #include "dev_util.h"
 #include "mfma_block.h"
+#include "cd_life_plan.h"      // RQ_NSIMD, RQ_MAXU, RQ_CSMAX: the constants the launch rules read too
 
 namespace qcqpmi {
 
 constexpr int RQ_NMW = 6;     // mfma waves: two per SIMD on three SIMDs, taking turns
-constexpr int RQ_NSIMD = 3;   // SIMDs that multiply (the fourth runs the chain)
 constexpr int RQ_PFU = 5;     // A-fragment ring of an mfma wave: units (blocks of 16 coordinates) resident at a time
 constexpr int RQ_RND = 4;     // passes over the ring per product
 constexpr int RQ_PERS = 20;   // units whose B operands stay in registers; any others are re-read for every product
-constexpr int RQ_MAXU = 20;   // blocks one SIMD can own (<= RQ_RND * RQ_PFU): n = 1024 needs the chain to take >= 4 blocks.
-                              // (22 units = 5 passes + 2 re-read units measured 2.5 % slower at the same split, and smaller
-                              //  chain shares do not pay: the mfma waves become the bottleneck)
-constexpr int RQ_CSMAX = 6;   // blocks the chain wave can own
 
 // LDS doubles besides the X tile
 constexpr int RQ_LDS_COMMON = 2 * RQ_NSIMD * 256 + 256 + 2 * 256 + 2 * 16 + 2 * 16 + 2 * 16 + 16 + 4 * 16 + 8 + 8 + 8;

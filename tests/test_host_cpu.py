@@ -852,6 +852,15 @@ def test_build_units_cover_every_source_file():
                 assert _build.needs_build()
             finally:
                 os.utime(path, (st.st_atime, st.st_mtime))
+        # the streamed path likewise: its unit alone for the unit file; the units that read the shape rules for their header
+        for name, units in (('capi_stream.hip', {'capi_stream.hip'}), ('cd_life_plan.h', {'capi_stream.hip', 'cd_life.hip', 'cd_queue.hip', 'capi.hip'})):
+            path = os.path.join(_build.SRC, name)
+            st = os.stat(path)
+            try:
+                os.utime(path, (st.st_atime, newest + 10))
+                assert set(_build.stale_units()) == before | units, name
+            finally:
+                os.utime(path, (st.st_atime, st.st_mtime))
 
 
 def test_every_kernel_is_compiled_into_one_unit():
@@ -877,11 +886,11 @@ def test_every_kernel_is_compiled_into_one_unit():
 
 
 def test_only_the_owning_unit_reaches_a_kernel_header():
-    """The seams of the C ABI's host side: capi_small.hip and capi_comm.hip are host code (nothing they are built from defines a
-    kernel), rccl/rccl.h is included by capi_comm.hip alone, and the kernels of admm.h and gemm_pk.h are compiled into
+    """The seams of the C ABI's host side: capi_small.hip, capi_comm.hip and capi_stream.hip are host code (nothing they are built from
+    defines a kernel), rccl/rccl.h is included by capi_comm.hip alone, and the kernels of admm.h and gemm_pk.h are compiled into
     capi_admm.hip alone."""
     from qcqp_amd import _build
-    for unit in ('capi_small.hip', 'capi_comm.hip'):
+    for unit in ('capi_small.hip', 'capi_comm.hip', 'capi_stream.hip'):
         with_kernel = [os.path.basename(p) for p in _build.unit_sources(unit) if '__global__' in open(p).read()]
         assert not with_kernel, (unit, with_kernel)
     text = {f: open(os.path.join(_build.SRC, f)).read() for f in os.listdir(_build.SRC) if f.endswith(('.hip', '.h', '.inc'))}
@@ -889,6 +898,21 @@ def test_only_the_owning_unit_reaches_a_kernel_header():
     for hdr in ('admm.h', 'gemm_pk.h'):
         reach = sorted(u for u in _build.TRANSLATION_UNITS if os.path.join(_build.SRC, hdr) in _build.unit_sources(u))
         assert reach == ['capi_admm.hip'], (hdr, reach)
+
+
+def test_the_streamed_launch_is_decided_in_one_place():
+    """What a streamed run launches is decided by stream_plan (csrc/cd_life_plan.h) for reserve and run alike: each environment
+    switch of that decision is read by one getenv in one file under csrc/ (stream_switches of capi_stream.hip), and cd_life_kernel's
+    shape rule is called from one place, the plan.  (Reserve used to restate the run's conditions by hand, and the copies drifted.)"""
+    from qcqp_amd import _build
+    text = {f: open(os.path.join(_build.SRC, f)).read() for f in os.listdir(_build.SRC) if f.endswith(('.hip', '.h', '.inc'))}
+    for name in ('QCQPMI_L2_PREBUILT', 'QCQPMI_L2_Y0_MAX', 'QCQPMI_L2_ROT', 'QCQPMI_L2_TILES'):
+        reads = {f: len(re.findall(r'getenv\(\s*"%s"\s*\)' % name, t)) for f, t in text.items()}
+        assert {f: k for f, k in reads.items() if k} == {'capi_stream.hip': 1}, (name, reads)
+    # calls of the rule: NAME( outside its definition (a line that starts with the return type) and outside comments
+    calls = [(f, line.strip()) for f, t in text.items() for line in t.splitlines()
+             if 'cd_life2_config(' in line.split('//')[0] and not re.match(r'^(?:inline |static )*bool cd_life2_config\(', line)]
+    assert len(calls) == 1 and calls[0][0] == 'cd_life_plan.h', calls
 
 
 def test_errors_without_a_context_share_one_slot():
@@ -951,7 +975,7 @@ def test_shared_device_helpers_are_defined_once():
     fix had to be made in two or three places and nothing failed when one was missed)."""
     from qcqp_amd import _build
     names = ['block_rows_times_X', 'keyed_normal_pair', 'ordered_key', 'ordered_unkey', 'wave_max', 'p1_class_visit',
-             'small_ticket_frame', 'small_stage_matrix', 'small_stage_q', 'small_stage_cons', 'small_asym_scan']
+             'small_ticket_frame', 'small_stage_matrix', 'small_stage_q', 'small_stage_cons', 'small_asym_scan', 'chain_share']
     text = {f: open(os.path.join(_build.SRC, f)).read() for f in os.listdir(_build.SRC) if f.endswith(('.hip', '.h', '.inc'))}
     for name in names:
         # a line that starts the definition: qualifiers and a return type at the start of the line, then NAME( -- a call sits
