@@ -121,6 +121,22 @@ struct L2Par {
     const int *cls;                       // [n16] class of each coordinate (multi-class kinds)
 };
 static_assert(sizeof(L2Par) <= 32 * sizeof(double), "L2Par outgrew its LDS slot");
+// LR instantiations: what the code between episodes reads of CdLife and of the constraint class, copied once at kernel start
+// (constants of the launch; through the opaque pointer every use was a global round trip of its own).  It lives in the 256 bytes
+// cd_life2_lds_bytes keeps behind the last tile's block (clsb of the multi-class kinds, which have no factored instantiation).
+struct L2Life {
+    int64_t Rtotal, Rpop, y0_count;
+    uint64_t seed, seed_stride, first_index, first_stride;
+    const double *preslack, *y0;
+    int64_t *sweeps1;
+    int *status1;
+    uint8_t *ran2;
+    unsigned long long *prof;
+    double cp, cq, cr;                    // the one constraint every coordinate carries: (cp x + cq) x + cr
+    int rel, prebuilt;
+    int turn, pad_;                       // turn: the turnover pass runs between episodes (prebuilt, and the launch has more restarts than slots)
+};
+static_assert(sizeof(L2Life) <= 256, "L2Life outgrew the tail of the LDS allocation");
 __device__ __attribute__((always_inline)) inline int l2_uni(int v) { return __builtin_amdgcn_readfirstlane(v); }
 __device__ __attribute__((always_inline)) inline long long l2_uni(long long v) {
     const int lo = __builtin_amdgcn_readfirstlane((int)(v & 0xffffffffll)), hi = __builtin_amdgcn_readfirstlane((int)(v >> 32));
@@ -1117,6 +1133,21 @@ __global__ __launch_bounds__((NMW == 3 && TILES == 1) ? 256 : 512, 2) void cd_li
         pr->NB = NB; pr->KS = KS; pr->n = (int)P.n; pr->nlast = nlast; pr->Rtotal = (int)lf0->Rtotal; pr->dbg = a0.dbg;
         pr->cls = P.cls;
     }
+    L2Life *const lfl = (L2Life *)(smem + L2_SHARED_DOUBLES + TILES * TD);
+    (void)lfl;
+    if constexpr (LR != 0) {
+        if (tid0 == 0) {
+            lfl->Rtotal = lf0->Rtotal; lfl->Rpop = lf0->Rpop; lfl->y0_count = lf0->y0_count;
+            lfl->seed = lf0->seed; lfl->seed_stride = lf0->seed_stride; lfl->first_index = lf0->first_index; lfl->first_stride = lf0->first_stride;
+            lfl->preslack = lf0->preslack; lfl->y0 = lf0->y0; lfl->sweeps1 = lf0->sweeps1; lfl->status1 = lf0->status1; lfl->ran2 = lf0->ran2;
+            lfl->prof = (unsigned long long *)lf0->prof; lfl->prebuilt = lf0->prebuilt;
+            const int e0 = P.cptr[P.krep[0]];
+            lfl->cp = P.cp[e0]; lfl->cq = P.cq[e0]; lfl->cr = P.cr[e0]; lfl->rel = P.crel[e0];
+            // a launch whose restarts fill its slots once has nothing to turn over: it measured slower through the pass (n = 4096,
+            // 8192 restarts on 8192 slots: profiles/r20_turnover.md) and keeps the refill and write-out below
+            lfl->turn = (lf0->prebuilt && lf0->Rtotal > (int64_t)gridDim.x * NS) ? 1 : 0; lfl->pad_ = 0;
+        }
+    }
     __syncthreads();
 
     for (;;) {
@@ -1127,35 +1158,199 @@ __global__ __launch_bounds__((NMW == 3 && TILES == 1) ? 256 : 512, 2) void cd_li
         const CdLife *lifep = a0.life;
         asm volatile("" : "+s"(lifep));
         const int lane = tid & 63, r = lane >> 2;
-        // ================================================================ refill: free slots take the next restarts
-        if (tid == 0) { ctl[0] = 0; jn[0] = 0; jn[1] = 0; }
-        __syncthreads();
-        if (tid < NS) {
-            const int st = tid >> 4, sc = tid & 15;          // slot sc of tile st
-            int id = l2_tl(sid, st, TD)[sc], nw = 0;
-            if (id < 0) {
-                GLB const CdLife *lf = glb(lifep);
-                const int idx = glb_add(glb(a0.b.next), 1);
-                if (idx < (int)lf->Rtotal) {
-                    id = idx; nw = 1;
-                    const uint64_t pop = (uint64_t)idx / (uint64_t)lf->Rpop, rho = (uint64_t)idx % (uint64_t)lf->Rpop;
-                    l2_tl(sseed, st, TD)[sc] = lf->seed + pop * lf->seed_stride;
-                    l2_tl(sfirst, st, TD)[sc] = lf->first_index + pop * lf->first_stride + rho - (uint64_t)idx;    // + id = the global restart index
+        bool turned = false;                       // the prebuilt factored path: write-out and refill are ONE pass (below)
+        if constexpr (LR != 0) {
+            if (l2_uni(lfl->turn)) {
+                // ============================================================ turnover (prebuilt columns, factored objective):
+                // the slots that finished are written out and the free slots refilled in one pass.  Everything it copies is
+                // addressed by a restart index alone, so every load is requested before any is used: (a) the slot threads retire
+                // the finished slots, draw the next indices and request the new restarts' scalars; (b) every thread requests the
+                // old and the new value of the elements it owns -- item = (column, row k NT + tid): the same thread reads an
+                // element of the tile and overwrites it, no barrier between write-out and refill -- and the new columns' rows of
+                // Y0; (c) one wait per chunk of L2_TCH items, then the stores.  The max violation of a finished column is a
+                // wave_max and one LDS atomicMax per wave and column (a maximum: exact in any order).
+                turned = true;
+                __builtin_amdgcn_s_setprio(3);
+                unsigned long long *const profp = l2_uni(lfl->prof);
+                const long long pt0 = profp ? (long long)__builtin_amdgcn_s_memtime() : 0;
+                const int r16 = 16 * a0.RB;
+                const int y0n = (int)l2_uni((long long)lfl->y0_count);
+                int oldid = -1, idv = -1, nwv = 0, nnew = 0;          // slot threads: the restart written out, the slot's restart now, new?
+                double nslack = 0.0;
+                long long nsw1 = 0;
+                int nst1 = 0, nran2 = 0;
+                if (tid < NS) {
+                    const int st = tid >> 4, sc = tid & 15;          // slot sc of tile st
+                    int id = l2_tl(sid, st, TD)[sc];
+                    if (l2_tl(sfin, st, TD)[sc]) {
+                        // counters, status and objective of the finished restart (its max violation follows the column's pass)
+                        oldid = id; id = -1;
+                        glb(a0.b.visits)[oldid] = l2_tl(ovis, st, TD)[sc]; glb(a0.b.accepted)[oldid] = l2_tl(oacc, st, TD)[sc]; glb(a0.b.sweeps)[oldid] = l2_tl(oswp, st, TD)[sc];
+                        glb(a0.b.status)[oldid] = l2_tl(ost, st, TD)[sc];
+                        if (a0.b.f0out) glb(a0.b.f0out)[oldid] = l2_tl(of0, st, TD)[sc];
+                        glb(lfl->sweeps1)[oldid] = l2_tl(p1sw, st, TD)[sc]; glb(lfl->status1)[oldid] = l2_tl(p1st, st, TD)[sc];
+                        glb(lfl->ran2)[oldid] = (uint8_t)l2_tl(gatep, st, TD)[sc];
+                        l2_tl(sfin, st, TD)[sc] = 0;
+                    }
+                    if (id < 0) {
+                        const int idx = glb_add(glb(a0.b.next), 1);
+                        if (idx < (int)lfl->Rtotal) {
+                            id = idx; nwv = 1;
+                            nslack = glb(lfl->preslack)[idx]; nsw1 = glb(lfl->sweeps1)[idx]; nst1 = glb(lfl->status1)[idx]; nran2 = glb(lfl->ran2)[idx];
+                            const uint64_t pop = (uint64_t)idx / (uint64_t)lfl->Rpop, rho = (uint64_t)idx % (uint64_t)lfl->Rpop;
+                            l2_tl(sseed, st, TD)[sc] = lfl->seed + pop * lfl->seed_stride;
+                            l2_tl(sfirst, st, TD)[sc] = lfl->first_index + pop * lfl->first_stride + rho - (uint64_t)idx;    // + id = the global restart index
+                        }
+                    }
+                    idv = id;
+                    l2_tl(sid, st, TD)[sc] = id; l2_tl(snew, st, TD)[sc] = nwv; l2_tl(p1upd, st, TD)[sc] = oldid;
+                    l2_tl(p1key, st, TD)[sc] = ordered_key(-QM_INF);
+                    *(volatile rq_lds_int *)(l2_tl((int *)sy, st, TD) + sc) = (sc >= RQ_PARTS + NMW) ? 0x7fffffff : 0;
+                    // the columns of this pass, in slot order: written out, refilled, or empty (a zero column that never moves)
+                    const unsigned long long mturn = __builtin_amdgcn_ballot_w64(oldid >= 0 || nwv || id < 0);
+                    const unsigned long long mocc = __builtin_amdgcn_ballot_w64(id >= 0), mnew = __builtin_amdgcn_ballot_w64(nwv != 0);
+                    if (oldid >= 0 || nwv || id < 0) p1cols[__builtin_popcountll(mturn & ((1ull << tid) - 1ull))] = tid;
+                    nnew = __builtin_popcountll(mnew);
+                    if (tid == 0) { ctl[0] = __builtin_popcountll(mocc); ctl[4] = __builtin_popcountll(mturn); jn[0] = 0; jn[1] = 0; }
                 }
+                __syncthreads();
+                {
+                    const double cp = l2_uni(lfl->cp), cq = l2_uni(lfl->cq), cr = l2_uni(lfl->cr);
+                    const int rel = l2_uni(lfl->rel);
+                    GLB const double *y0g = glb(l2_uni(lfl->y0));
+                    const int nturn = l2_uni(ctl[4]);
+                    const int KR = (int)((n16 + NT - 1) / NT), KI = KR + (r16 + NT - 1) / NT;      // items of a column: its rows of X, then of Y
+                    const int np = (int)P.n, nx = (int)n16;
+                    constexpr int L2_TCH = 16;         // items per chunk: at most 32 loads in flight per thread
+                    double vacc = -QM_INF;
+                    int ci0 = 0, k0 = 0;
+                    while (ci0 < nturn) {
+                        double xo[L2_TCH], xn[L2_TCH];
+                        int ci = ci0, k = k0;
+#pragma unroll
+                        for (int q = 0; q < L2_TCH; q++) {
+                            xo[q] = 0.0; xn[q] = 0.0;
+                            if (ci < nturn) {
+                                const int c = l2_uni(p1cols[ci]), ct = c >> 4, cc = c & 15;
+                                const int oid = l2_uni(l2_tl(p1upd, ct, TD)[cc]), id = l2_uni(l2_tl(sid, ct, TD)[cc]), nw = l2_uni(l2_tl(snew, ct, TD)[cc]);
+                                if (k < KR) {
+                                    const int j = k * NT + tid;
+                                    if (oid >= 0 && j < np) xo[q] = (Xg0 + (int64_t)ct * n16 * 16)[(int64_t)j * 16 + cc];
+                                    if (nw && j < nx) xn[q] = glb(a0.b.X)[((int64_t)(id >> 4) * n16 + j) * 16 + (id & 15)];
+                                } else {
+                                    const int row = (k - KR) * NT + tid;
+                                    if (nw && id < y0n && row < r16) xn[q] = y0g[((int64_t)(id >> 4) * r16 + row) * 16 + (id & 15)];
+                                }
+                                if (++k == KI) { k = 0; ci++; }
+                            }
+                        }
+                        ci = ci0; k = k0;
+#pragma unroll
+                        for (int q = 0; q < L2_TCH; q++) {
+                            if (ci < nturn) {
+                                const int c = l2_uni(p1cols[ci]), ct = c >> 4, cc = c & 15;
+                                const int oid = l2_uni(l2_tl(p1upd, ct, TD)[cc]), id = l2_uni(l2_tl(sid, ct, TD)[cc]), nw = l2_uni(l2_tl(snew, ct, TD)[cc]);
+                                if (k < KR) {
+                                    const int j = k * NT + tid;
+                                    if (oid >= 0) {
+                                        // the old column to the population (padded rows: zero), its max violation: same expression as eval_kernel
+                                        if (j < nx) glb(a0.b.X)[((int64_t)(oid >> 4) * n16 + j) * 16 + (oid & 15)] = xo[q];
+                                        if (j < np) {
+                                            const double f = (cp * xo[q] + cq) * xo[q] + cr;
+                                            const double vv = (rel == RELOP_EQ) ? fabs(f) : (f > 0.0 ? f : 0.0);
+                                            vacc = vv > vacc ? vv : vacc;
+                                        }
+                                        if (k == KR - 1) {
+                                            const double vw = wave_max(vacc);
+                                            if (lane == 0) atomicMax(&l2_tl(p1key, ct, TD)[cc], ordered_key(vw));
+                                            vacc = -QM_INF;
+                                        }
+                                    }
+                                    if ((nw || id < 0) && j < nx) {
+                                        // the new column (an empty slot: zeros) to the tile; its last two blocks are the preloaded restart's
+                                        // pending moves (the padded rows of both follow the padding step)
+                                        (Xg0 + (int64_t)ct * n16 * 16)[(int64_t)j * 16 + cc] = xn[q];
+                                        if (j >= nx - 32) l2_tl(pend, ct, TD)[(j - (nx - 32)) * 16 + cc] = (nw && id < y0n) ? xn[q] : 0.0;
+                                    }
+                                } else {
+                                    const int row = (k - KR) * NT + tid;
+                                    if ((nw || id < 0) && row < r16) l2_tl(ytile, ct, TD)[row * 16 + cc] = xn[q];
+                                }
+                                if (++k == KI) { k = 0; ci++; }
+                            }
+                        }
+                        ci0 = ci; k0 = k;
+                    }
+                }
+                if (tid < NS && (nwv || idv < 0)) {
+                    // slack, phase-1 counters, gate and feasible set of the new restart (an empty slot: the set of slack 0, the restart
+                    // counts as converged)
+                    const int st = tid >> 4, sc = tid & 15;
+                    if (nwv) { l2_tl(p1fin, st, TD)[sc] = 0; l2_tl(p1sw, st, TD)[sc] = (int)nsw1; l2_tl(p1st, st, TD)[sc] = nst1; l2_tl(gatep, st, TD)[sc] = nran2; }
+                    l2_tl(slk, st, TD)[sc] = nslack;
+                    L2_STORE_SETS(st, sc, nslack)
+                }
+                __syncthreads();
+                if (tid < NS && oldid >= 0 && a0.b.mvout) glb(a0.b.mvout)[oldid] = ordered_unkey(l2_tl(p1key, tid >> 4, TD)[tid & 15]);
+                if (ctl[0] == 0) break;            // nothing left anywhere: done
+                if (nlast < 16) {
+                    // n is not a multiple of 16: the padded coordinates of the last block hold the step's fixed point (see the
+                    // in-kernel build below), in the tile and -- a preloaded restart -- among the pending moves
+                    for (int w = tid; w < NS * (16 - nlast); w += NT) {
+                        const int c = w % NS, ct = c >> 4, cc = c & 15, row = w / NS;
+                        const int id = l2_tl(sid, ct, TD)[cc];
+                        if (l2_tl(snew, ct, TD)[cc] || id < 0) {
+                            const int nn = l2_tl(TC.n, ct, TD)[cc];
+                            double xp = 0.0;
+                            // (the build's padding step below has a third branch for the zero-diagonal kinds: none of them is factored)
+                            static_assert(BK == L2_KIND_BAND || BK == L2_KIND_GEN, "turnover pass: padding fixed point of the band and gen kinds only");
+                            if (BK == L2_KIND_BAND) xp = nn >= 2 ? l2_tl(TC.lo, ct, TD)[16 * KCLV + cc] : 0.0;
+                            else xp = nn >= 1 ? l2_tl(TC.hi, ct, TD)[cc] : 0.0;
+                            if (!(xp == xp) || __builtin_isinf(xp)) xp = 0.0;
+                            (Xg0 + (int64_t)ct * n16 * 16)[(P.n + row) * 16 + cc] = xp;
+                            l2_tl(pend, ct, TD)[(16 + nlast + row) * 16 + cc] = (id >= 0 && id < y0n) ? xp : 0.0;
+                        }
+                    }
+                }
+                if (profp && tid == 0) {
+                    atomicAdd(profp + 0, (unsigned long long)((long long)__builtin_amdgcn_s_memtime() - pt0));
+                    atomicAdd(profp + 2, 1ull);
+                    atomicAdd(profp + 3, (unsigned long long)nnew);
+                }
+                __builtin_amdgcn_s_setprio(0);
             }
-            l2_tl(sid, st, TD)[sc] = id; l2_tl(snew, st, TD)[sc] = nw;
-            if (nw) { l2_tl(p1fin, st, TD)[sc] = 0; l2_tl(p1sw, st, TD)[sc] = 0; l2_tl(p1st, st, TD)[sc] = 0; l2_tl(gatep, st, TD)[sc] = 0; }
-            if (id < 0) {
-                // an empty slot: a zero column that never moves (feasible set of slack 0, restart marked converged)
-                l2_tl(slk, st, TD)[sc] = 0.0;
-                L2_STORE_SETS(st, sc, 0.0)
-            }
-            if (id >= 0) atomicAdd(&ctl[0], 1);
-            *(volatile rq_lds_int *)(l2_tl((int *)sy, st, TD) + sc) = (sc >= RQ_PARTS + NMW) ? 0x7fffffff : 0;
         }
-        __syncthreads();
-        if (ctl[0] == 0) break;                    // nothing left anywhere: done
-        {
+        // ================================================================ refill: free slots take the next restarts
+        if (!turned) {
+            if (tid == 0) { ctl[0] = 0; jn[0] = 0; jn[1] = 0; }
+            __syncthreads();
+            if (tid < NS) {
+                const int st = tid >> 4, sc = tid & 15;          // slot sc of tile st
+                int id = l2_tl(sid, st, TD)[sc], nw = 0;
+                if (id < 0) {
+                    GLB const CdLife *lf = glb(lifep);
+                    const int idx = glb_add(glb(a0.b.next), 1);
+                    if (idx < (int)lf->Rtotal) {
+                        id = idx; nw = 1;
+                        const uint64_t pop = (uint64_t)idx / (uint64_t)lf->Rpop, rho = (uint64_t)idx % (uint64_t)lf->Rpop;
+                        l2_tl(sseed, st, TD)[sc] = lf->seed + pop * lf->seed_stride;
+                        l2_tl(sfirst, st, TD)[sc] = lf->first_index + pop * lf->first_stride + rho - (uint64_t)idx;    // + id = the global restart index
+                    }
+                }
+                l2_tl(sid, st, TD)[sc] = id; l2_tl(snew, st, TD)[sc] = nw;
+                if (nw) { l2_tl(p1fin, st, TD)[sc] = 0; l2_tl(p1sw, st, TD)[sc] = 0; l2_tl(p1st, st, TD)[sc] = 0; l2_tl(gatep, st, TD)[sc] = 0; }
+                if (id < 0) {
+                    // an empty slot: a zero column that never moves (feasible set of slack 0, restart marked converged)
+                    l2_tl(slk, st, TD)[sc] = 0.0;
+                    L2_STORE_SETS(st, sc, 0.0)
+                }
+                if (id >= 0) atomicAdd(&ctl[0], 1);
+                *(volatile rq_lds_int *)(l2_tl((int *)sy, st, TD) + sc) = (sc >= RQ_PARTS + NMW) ? 0x7fffffff : 0;
+            }
+            __syncthreads();
+            if (ctl[0] == 0) break;                    // nothing left anywhere: done
+        }
+        if (!turned) {
             // ---- build the columns of the restarts just taken: suggest(RANDOM) (qcqp.py:381-382: keyed normals, the stream
             // of randn_tiles_kernel) or the resident point, phase 1 (qcqp.py:101-149 through the visit of cd_phase1_sep.h), the
             // max violation = slack of phase 2 (qcqp.py:157) and the gate (qcqp.py:189).  The tiles live in global memory;
@@ -1399,9 +1594,8 @@ __global__ __launch_bounds__((NMW == 3 && TILES == 1) ? 256 : 512, 2) void cd_li
                 const int pass = l2_tl(gatep, rtile, TD)[r];
                 // (factored objective: the loading sweep first -- unless the refill preloaded the slot's Y, see there)
                 bool load = LR != 0;
-                if (LR) {
-                    GLB const CdLife *lf = glb(lifep);
-                    if (lf->prebuilt && l2_tl(sid, rtile, TD)[r] < (int)lf->y0_count) load = false;
+                if constexpr (LR != 0) {
+                    if (lfl->prebuilt && l2_tl(sid, rtile, TD)[r] < (int)lfl->y0_count) load = false;
                 }
                 cs_[6 * 64 + lane] = 0;
                 cs_[4 * 64 + lane] = (pass && !PRE && !load) ? 0 : 1;
@@ -1413,7 +1607,9 @@ __global__ __launch_bounds__((NMW == 3 && TILES == 1) ? 256 : 512, 2) void cd_li
             }
         }
         __syncthreads();
-        if (tid == 0 && glb(lifep)->prof) *(long long *)(ctl + 6) = (long long)__builtin_amdgcn_s_memtime();
+        if constexpr (LR != 0) {
+            if (tid == 0 && lfl->prof) *(long long *)(ctl + 6) = (long long)__builtin_amdgcn_s_memtime();
+        } else if (tid == 0 && glb(lifep)->prof) *(long long *)(ctl + 6) = (long long)__builtin_amdgcn_s_memtime();
 
         // ================================================================ episode: the roles
         if (role > 0) {
@@ -1426,14 +1622,20 @@ __global__ __launch_bounds__((NMW == 3 && TILES == 1) ? 256 : 512, 2) void cd_li
             if (tid == 0) __hip_atomic_store(glb(a0.abort), 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             break;
         }
-        if (tid == 0 && glb(lifep)->prof)
+        if constexpr (LR != 0) {
+            if (tid == 0 && lfl->prof) {
+                const long long now_ = (long long)__builtin_amdgcn_s_memtime();
+                atomicAdd(lfl->prof + 5, (unsigned long long)(now_ - *(long long *)(ctl + 6)));
+                atomicAdd(lfl->prof + 20, (unsigned long long)(now_ - *(long long *)(ctl + 8)));    // from the chain's last interval to the barrier
+            }
+        } else if (tid == 0 && glb(lifep)->prof)
         {
             const long long now_ = (long long)__builtin_amdgcn_s_memtime();
             atomicAdd((unsigned long long *)glb(lifep)->prof + 5, (unsigned long long)(now_ - *(long long *)(ctl + 6)));
             atomicAdd((unsigned long long *)glb(lifep)->prof + 20, (unsigned long long)(now_ - *(long long *)(ctl + 8)));    // from the chain's last interval to the barrier
         }
-        // ================================================================ write out the slots that finished
-        {
+        // ================================================================ write out the slots that finished (the turnover pass does it otherwise)
+        if (!turned) {
             // max violation of the final points, same expression as eval_kernel: (p x + q) x + r of the one constraint
             // every coordinate carries (single class, one constraint per coordinate)
             const int e0 = P.cptr[P.krep[0]];
