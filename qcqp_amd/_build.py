@@ -1,7 +1,6 @@
 """Builds libqcqp_mi.so (hand-written HIP for gfx950) in-tree with hipcc.
 
-Several translation units, compiled in parallel and only when one of their sources changed (the big one takes two
-minutes): objects under qcqp_amd/_obj/ (git-ignored), linked into qcqp_amd/libqcqp_mi.so."""
+Several translation units, compiled in parallel and only when one of their sources changed (the biggest take a minute or two): objects under qcqp_amd/_obj/ (git-ignored), linked into qcqp_amd/libqcqp_mi.so."""
 import os
 import re
 import subprocess
@@ -16,7 +15,7 @@ HEADER = os.path.join(REPO, 'include', 'qcqp_mi.h')
 
 # translation units; what each one includes is found by scanning its `#include "..."` lines recursively (round 4 shipped a
 # hand-kept list that missed a header: an edit to it rebuilt nothing)
-TRANSLATION_UNITS = ['capi.hip', 'capi_admm.hip', 'capi_small.hip', 'capi_units.hip', 'capi_comm.hip', 'capi_stream.hip',
+TRANSLATION_UNITS = ['capi.hip', 'capi_cd.hip', 'capi_dense.hip', 'capi_admm.hip', 'capi_small.hip', 'capi_units.hip', 'capi_comm.hip', 'capi_stream.hip',
                      'admm_fused.hip', 'cd_queue.hip', 'cd_life.hip', 'cd_small.hip', 'sdr_small.hip', 'admm_small.hip']
 _INC = re.compile(r'^\s*#\s*include\s+"([^"]+)"', re.M)
 
@@ -33,7 +32,7 @@ def _scan(path, seen):
 
 
 def unit_sources(unit):
-    """Absolute paths of every file the translation unit is built from (itself, headers, .inc files, the C ABI header)."""
+    """Absolute paths of every file the translation unit is built from (itself, its headers, the C ABI header)."""
     seen = set()
     _scan(os.path.join(SRC, unit), seen)
     return sorted(seen)

@@ -1,6 +1,6 @@
 // Fused, persistent consensus-ADMM iteration (round 3): improve_admm (qcqp.py:254-285) -- phase 1 (qcqp.py:195-212),
 // `better`, phase 2 (qcqp.py:215-251), `better` -- for a tile of 16 restarts inside ONE kernel, no host in the loop.
-// Interface between capi_admm.inc (host side, in the big translation unit) and admm_fused.hip (own translation unit).
+// Interface between capi_admm.hip (host side) and admm_fused.hip (own translation unit).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -8,7 +8,7 @@
 //
 // Formulation: the reduced bases of admm.h (low-rank constraints: the dual of constraint k lives in span(B_k), rp <= 8
 // numbers) with a diagonal P0 -- BASELINE.json configs[3] (beamforming: P0 = I, rank-2 constraints).  Other problems keep
-// the multi-launch path of capi_admm.inc, which this kernel reproduces to rounding (same expressions, other summation
+// the multi-launch path of capi_admm.hip, which this kernel reproduces to rounding (same expressions, other summation
 // order in the two products) and which stays available as the cross-check (qcqpmi_admm_fused(ctx, 0)).
 //
 // Work split.  A tile of 16 restarts is owned by a CLUSTER of C workgroups (C = 1, 2, 4, 8, 16; chosen by the host so

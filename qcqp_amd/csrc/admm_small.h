@@ -1,4 +1,4 @@
-// Small-problem ADMM batch kernel: interface between capi.hip (its driver: capi_small.inc) and admm_small.hip (own translation unit).
+// Small-problem ADMM batch kernel: interface between its driver (capi_small.hip) and admm_small.hip (own translation unit).
 //
 // improve_admm (qcqp.py:254-285: phase 1, `better`, phase 2 with its bestx bookkeeping, `better`) for B problems of n <= 64 variables
 // with separable constraints (up to four per coordinate: the lists of qcqpmi_cd_small_batch_run) that differ in their objective

@@ -53,7 +53,7 @@ __device__ __attribute__((always_inline)) inline double as_entry(double p, doubl
     fz += rk; fv += rk;
     const double w = (relop == RELOP_EQ) ? fabs(fz) : (fz > 0.0 ? fz : 0.0);
     viol = w > viol ? w : viol;
-    // the bracket of one row (admm_brackets, capi_admm.inc)
+    // the bracket of one row (admm_brackets, capi_admm.hip)
     double br[2];
     br[0] = L[0] > 0.0 ? -1.0 / L[0] : -QM_INF;
     br[1] = L[0] < 0.0 ? -1.0 / L[0] : QM_INF;
@@ -93,7 +93,7 @@ __device__ inline double as_project(const AsList<MAXC> &K, double z, bool first,
         fz += rk; fv += rk;
         const double w = (relop == RELOP_EQ) ? fabs(fz) : (fz > 0.0 ? fz : 0.0);
         viol = w > viol ? w : viol;
-        // the bracket of one row (admm_brackets, capi_admm.inc)
+        // the bracket of one row (admm_brackets, capi_admm.hip)
         double br[2];
         br[0] = L[0] > 0.0 ? -1.0 / L[0] : -QM_INF;
         br[1] = L[0] < 0.0 ? -1.0 / L[0] : QM_INF;

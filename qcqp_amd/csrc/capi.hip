@@ -1,8 +1,9 @@
-// C ABI of libqcqp_mi.so (declared in include/qcqp_mi.h): context, problem upload, population
-// management, launches of the kernels in kernels_impl.h, HIP-event timing.  The core of the host side: the ADMM calls are in
-// capi_admm.hip, the small-problem batch calls in capi_small.hip, the unit operators in capi_units.hip, RCCL in capi_comm.hip, the
-// streamed coordinate descent (qcqpmi_cd_stream_run and what it needs: host code only) in capi_stream.hip; capi_ctx.h holds what
-// these units share.
+// C ABI of libqcqp_mi.so (declared in include/qcqp_mi.h): context and error slot, problem upload and finalize, population
+// management, evaluation, SDR sampling and the mixing-method solver, selection, HIP-event timing; launches of the kernels in
+// kernels_impl.h and sdr_solve.h.  The core of the host side: coordinate descent on the resident population is in capi_cd.hip, the
+// dense-constraint path in capi_dense.hip, the ADMM calls in capi_admm.hip, the small-problem batch calls in capi_small.hip, the
+// unit operators in capi_units.hip, RCCL in capi_comm.hip, the streamed coordinate descent (qcqpmi_cd_stream_run and what it
+// needs: host code only) in capi_stream.hip; capi_ctx.h holds what these units share.
 #include <algorithm>
 #include <cmath>
 #include <cstdarg>
@@ -11,8 +12,6 @@
 
 #include "capi_ctx.h"
 #include "kernels_impl.h"
-#include "cd_queue.h"
-#include "cd_dense.h"
 #include "sdr_solve.h"
 
 using namespace qcqpmi;
@@ -56,59 +55,11 @@ void launch_from_tiles(qcqpmi_ctx *c, const double *Xt, int64_t R) {
 
 namespace {
 
-// `count` elements of the problem's own storage: owned by prob_allocs until the context goes
-template <typename T>
-int prob_alloc(qcqpmi_ctx *c, T **dst, size_t count) {
-    DevBuf<char> b;
-    HIPCHK(c, b.reserve(c->stream, std::max<size_t>(count, 1) * sizeof(T), false));
-    *dst = (T *)b.p;
-    c->prob_allocs.push_back(std::move(b));
-    return 0;
-}
-
-template <typename T>
-int prob_upload(qcqpmi_ctx *c, const T **dst, const std::vector<T> &src) {
-    T *p = nullptr;
-    int rc = prob_alloc(c, &p, src.size());
-    if (rc) return rc;
-    if (!src.empty())
-        HIPCHK(c, hipMemcpyAsync(p, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice, c->stream));
-    *dst = p;
-    return 0;
-}
-
 void free_population(qcqpmi_ctx *c) {
     c->X.release(); c->Xi.release(); c->d_f0.release(); c->d_mv.release(); c->d_F.release(); c->d_stage.release();
     c->d_visits.release(); c->d_acc.release(); c->d_sweeps.release(); c->d_sweeps1.release();
     c->d_status.release(); c->d_status1.release(); c->d_flag.release();
     c->Rcap = 0;
-}
-
-bool dense_on(const qcqpmi_ctx *c);
-int launch_eval_dense(qcqpmi_ctx *c, bool with_Ft);
-int eval_parts_dense(qcqpmi_ctx *c);
-
-// per-restart results of a coordinate-descent run -> host: one pack kernel, one copy into pinned memory,
-// one synchronisation (nine pageable copies cost ~0.3 ms of staging kernels per call)
-__global__ void pack_cd_outputs_kernel(char *out, int64_t R, const int64_t *s1, const int64_t *s2, const int64_t *vis,
-                                       const int64_t *acc, const double *f0, const double *mv, const int *st,
-                                       const int *st1, const uint8_t *flag) {
-    const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (r >= R) return;
-    int64_t *o64 = (int64_t *)out;
-    o64[r] = s1[r]; o64[R + r] = s2[r]; o64[2 * R + r] = vis[r]; o64[3 * R + r] = acc[r];
-    double *od = (double *)(out + 32 * R);
-    od[r] = f0[r]; od[R + r] = mv[r];
-    int *oi = (int *)(out + 48 * R);
-    oi[r] = st[r]; oi[R + r] = st1[r];
-    ((uint8_t *)(out + 56 * R))[r] = flag[r];
-}
-
-// pinned host memory for downloads that are repeated thousands of times (a 2-D copy into pageable memory is staged row by
-// row by the runtime: 1025 rows of 47 doubles cost 15 ms)
-int pin_reserve(qcqpmi_ctx *c, size_t bytes) {
-    HIPCHK(c, c->h_pin.reserve(c->stream, bytes, false));
-    return 0;
 }
 
 }  // namespace
@@ -141,94 +92,9 @@ int pop_reserve(qcqpmi_ctx *c, int64_t R) {
     return 0;
 }
 
-// staging buffers (device + pinned host) of fetch_cd_outputs for R restarts
-int cd_outputs_reserve(qcqpmi_ctx *c, int64_t R) {
-    HIPCHK(c, c->d_out.reserve(c->stream, (size_t)(57 * R), false));
-    HIPCHK(c, c->h_out.reserve(c->stream, (size_t)(57 * R), false));
-    return 0;
-}
-
-int fetch_cd_outputs(qcqpmi_ctx *c, int64_t *sweeps1, int64_t *sweeps2, int64_t *visits2, int64_t *accepted2,
-                     uint8_t *ran_phase2, double *f0, double *maxviol, std::vector<int> &st, std::vector<int> &st1) {
-    const int64_t R = c->R, bytes = 57 * R;
-    int rco = cd_outputs_reserve(c, R);
-    if (rco) return rco;
-    hipLaunchKernelGGL(pack_cd_outputs_kernel, dim3((unsigned)((R + 255) / 256)), dim3(256), 0, c->stream, c->d_out, R,
-                       (const int64_t *)c->d_sweeps1, (const int64_t *)c->d_sweeps, (const int64_t *)c->d_visits,
-                       (const int64_t *)c->d_acc, (const double *)c->d_f0, (const double *)c->d_mv,
-                       (const int *)c->d_status, (const int *)c->d_status1, (const uint8_t *)c->d_flag);
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(c->h_out, c->d_out, (size_t)bytes, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, spin_sync(c->stream));
-    const char *h = c->h_out;
-    const size_t n8 = (size_t)R * 8;
-    if (sweeps1) memcpy(sweeps1, h, n8);
-    if (sweeps2) memcpy(sweeps2, h + n8, n8);
-    if (visits2) memcpy(visits2, h + 2 * n8, n8);
-    if (accepted2) memcpy(accepted2, h + 3 * n8, n8);
-    if (f0) memcpy(f0, h + 4 * n8, n8);
-    if (maxviol) memcpy(maxviol, h + 5 * n8, n8);
-    st.resize((size_t)R); st1.resize((size_t)R);
-    memcpy(st.data(), h + 6 * n8, (size_t)R * 4);
-    memcpy(st1.data(), h + 6 * n8 + (size_t)R * 4, (size_t)R * 4);
-    if (ran_phase2) memcpy(ran_phase2, h + 7 * n8, (size_t)R);
-    return 0;
-}
-
-// Per-restart status policy of a coordinate-descent run.  A restart on which the reference would raise
-// (code != 0) is a FAILED restart, not a failed population: its objective / max violation become +inf (host
-// outputs and the device copies select_best reads), the codes stay readable through qcqpmi_cd_status.  The call
-// itself fails -- with the reference's message -- only when every restart failed (in particular R == 1, the
-// reference's single-point behaviour).
-int cd_apply_status(qcqpmi_ctx *c, const std::vector<int> &st, const std::vector<int> &st1, double *f0, double *maxviol,
-                    int seg_cap) {
-    const int64_t R = c->R;
-    c->last_st1 = st1; c->last_st2 = st;
-    int64_t nfail = 0, first = -1;
-    for (int64_t r = 0; r < R; r++)
-        if (st1[(size_t)r] || st[(size_t)r]) { if (first < 0) first = r; nfail++; }
-    if (nfail == 0) return 0;
-    if (nfail < R) {
-        const double inf = INFINITY;
-        for (int64_t r = 0; r < R; r++) {
-            if (!(st1[(size_t)r] || st[(size_t)r])) continue;
-            if (f0) f0[r] = inf;
-            if (maxviol) maxviol[r] = inf;
-            HIPCHK(c, hipMemcpyAsync(c->d_f0 + r, &inf, sizeof(double), hipMemcpyHostToDevice, c->stream));
-            HIPCHK(c, hipMemcpyAsync(c->d_mv + r, &inf, sizeof(double), hipMemcpyHostToDevice, c->stream));
-        }
-        HIPCHK(c, spin_sync(c->stream));
-        return 0;
-    }
-    const int64_t r = first;
-    const int s1 = st1[(size_t)r], s2 = st[(size_t)r];
-    if (s1 == -3) return fail(c, QCQPMI_EREFERENCE, "phase 1: a variable appears in no constraint (reference: ValueError: max() arg is an empty sequence, qcqp.py:117); restart %lld", (long long)r);
-    if (s1 == -4 || s2 == -4) return fail(c, QCQPMI_EUNSUPPORTED, "feasible set with more than %d segments; restart %lld", seg_cap, (long long)r);
-    if (s1) return fail(c, QCQPMI_EREFERENCE, "phase 1: unbounded feasible interval with zero objective (reference: OverflowError in np.random.uniform, utilities.py:267); restart %lld", (long long)r);
-    return fail(c, QCQPMI_EREFERENCE, "phase 2: the reference raises on restart %lld (code %d: unbounded interval with zero objective / NameError in OneVarQuadraticFunction.eval)", (long long)r, s2);
-}
-
-void cd_queue_fill_batch(qcqpmi_ctx *c, CdBatch &B, uint64_t seed, uint64_t first_index) {
-    B.X = c->X; B.f0cur = c->d_f0; B.slack = c->d_mv; B.flag = c->d_flag; B.visits = c->d_visits; B.accepted = c->d_acc;
-    B.sweeps = c->d_sweeps; B.status = c->d_status; B.f0out = c->d_f0; B.mvout = c->d_mv; B.R = c->R; B.seed = seed;
-    B.first_index = first_index; B.next = c->d_qnext;
-}
-
-// does the round-4 slot-queue kernel take the problem's shape?  (the switches are the caller's: cd_queue_eligible for qcqpmi_cd_run,
-// stream_plan for the lifecycle mode of qcqpmi_cd_stream_run)
-bool cd_queue_shape_ok(const qcqpmi_ctx *c) {
-    if (!c->sep || c->maxc > 1) return false;
-    if (!(c->K == 1 && c->objclass == 1 && c->symcls && c->n % 16 == 0)) return false;
-    return cd_queue_lds_bytes(c->dp) != 0 && c->R < (1LL << 30);
-}
-
 void launch_gather_best_x(qcqpmi_ctx *c, int64_t pops, int64_t R, const int64_t *idx, double *out) {
     hipLaunchKernelGGL(gather_best_x_kernel, dim3((unsigned)pops), dim3(256), 0, c->stream, (const double *)c->X, c->n, c->n16, R, idx, out);
 }
-
-}  // namespace qcqpmi
-
-namespace {
 
 int launch_eval(qcqpmi_ctx *c, bool want_F) {
     if (dense_on(c)) return launch_eval_dense(c, false);   // coupled constraints: every function on the matrix cores
@@ -240,18 +106,11 @@ int launch_eval(qcqpmi_ctx *c, bool want_F) {
     tic(c, 0);
     const int NB = (int)(c->n16 / 16), ntiles = (int)(c->Rpad / 16);
     if (NB >= 8 && ntiles >= 8) {
-        // x'P0x through the LDS-tiled GEMM: 8 row blocks x 8 tiles per workgroup share their operands
-        // (the per-tile MFMA loop of eval_kernel re-reads all of P0 from L2 for every tile)
-        const int groups = (NB + DP_FG - 1) / DP_FG, nplanes = 2 * groups;
+        // x'P0x through the LDS-tiled GEMM of the dense unit, in partial planes that eval_kernel sums
+        const int nplanes = dense_product_planes(NB);
         HIPCHK(c, c->d_planes.reserve(c->stream, (size_t)nplanes * c->Rpad));
-        DenseProdArgs pa;
-        pa.D.Gpack = c->dp.Apack; pa.D.q = nullptr; pa.D.qT = nullptr; pa.D.r = nullptr; pa.D.relop = nullptr;
-        pa.D.n = c->n; pa.D.n16 = c->n16; pa.D.NB = NB; pa.D.KS = (int)(c->n16 / 4); pa.D.m1 = 1; pa.D.m1p = 64;
-        pa.X = c->X; pa.ntiles = ntiles; pa.b = 0; pa.zs = 1; pa.G = nullptr; pa.F = c->d_planes; pa.Rpad = c->Rpad;
-        pa.tile_on = nullptr; pa.hole = -1; pa.ch_only = -1; pa.zplane = 0;
-        auto kg = dense_products_kernel<2>;
-        HIPCHK(c, hipFuncSetAttribute((const void *)kg, hipFuncAttributeMaxDynamicSharedMemorySize, DP_LDS_BYTES));
-        hipLaunchKernelGGL(kg, dim3((unsigned)groups, (unsigned)((ntiles + DP_TG - 1) / DP_TG), 1), dim3(256), DP_LDS_BYTES, c->stream, pa);
+        int rc = launch_dense_product(c, 2, c->dp.Apack, nullptr, c->X, c->d_planes);
+        if (rc) return rc;
         a.planes = c->d_planes; a.nplanes = nplanes;
     }
     hipLaunchKernelGGL(eval_kernel, dim3((unsigned)(c->Rpad / 16)), dim3(256), 0, c->stream, a);
@@ -261,226 +120,7 @@ int launch_eval(qcqpmi_ctx *c, bool want_F) {
     return 0;
 }
 
-// does phase 2 of the resident population go through the slot-queue kernel?
-bool cd_queue_eligible(qcqpmi_ctx *c, bool profiling) {      // the problem's shape and the context's switches allow the kernel
-    if (profiling || c->force_generic || (c->dbg & 64) || c->cd_queue == 0) return false;
-    return cd_queue_shape_ok(c);
-}
-
-bool cd_queue_applies(qcqpmi_ctx *c, bool profiling) {
-    if (!cd_queue_eligible(c, profiling)) return false;
-    int cus = 0;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device) != hipSuccess) return false;
-    if (c->cd_queue == 1) return true;
-    if (c->cd_queue == 2) return c->Rpad / 16 > cus;
-    return false;
-}
-
-// reset the queue of the resident population and the per-restart outputs the kernel only writes for the restarts it runs,
-// then publish the population (generation number) to whoever may pull from it
-int cd_queue_prepare(qcqpmi_ctx *c) {
-    HIPCHK(c, c->d_qnext.reserve(c->stream, 16));
-    HIPCHK(c, hipMemsetAsync(c->d_visits, 0, (size_t)c->Rpad * sizeof(int64_t), c->stream));
-    HIPCHK(c, hipMemsetAsync(c->d_acc, 0, (size_t)c->Rpad * sizeof(int64_t), c->stream));
-    HIPCHK(c, hipMemsetAsync(c->d_sweeps, 0, (size_t)c->Rpad * sizeof(int64_t), c->stream));
-    HIPCHK(c, hipMemsetAsync(c->d_status, 0, (size_t)c->Rpad * sizeof(int), c->stream));
-    HIPCHK(c, hipMemsetAsync(c->d_qnext, 0, 16 * sizeof(int), c->stream));
-    c->q_prepared = true;
-    return 0;
-}
-
-template <int MAXC>
-int launch_cd(qcqpmi_ctx *c, const CdArgs &a1, bool phase1, bool &used_lds, bool *used_rs = nullptr) {
-    if (used_rs) *used_rs = false;
-    if (!phase1) c->last_cd2_kernel = "cd_phase2_kernel";
-    const bool cd_debug = getenv("QCQPMI_CD_DEBUG") != nullptr;     // tests: one line per launch with the template arguments chosen below
-    dim3 grid((unsigned)(c->Rpad / 16)), block(256);
-    if (phase1) {
-        if (cd_debug) fprintf(stderr, "launch_cd: cd_phase1_sep_kernel MAXC %d\n", MAXC);
-        tic(c, 1);
-        hipLaunchKernelGGL(cd_phase1_sep_kernel<MAXC>, grid, dim3(P1_THREADS), 0, c->stream, a1);
-        toc(c, 1);
-        HIPCHK(c, hipGetLastError());
-        return 0;
-    }
-    const DevProblem &dp = c->dp;
-    // second-generation role-split kernel (cd_phase2_q.h): one mirrored equality class, positive diagonal, n a
-    // multiple of 16, the tile resident in LDS -- the Boolean least squares family of the headline benchmark
-    if (MAXC == 1 && c->K == 1 && c->objclass == 1 && c->symcls && c->n % 16 == 0 && !c->force_generic && !(c->dbg & 64)) {
-        // (at least RQ_LDS_MIN: the product loop's look-ahead loads address a full-size tile)
-        size_t q_lds = ((size_t)RQ_LDS_COMMON + (size_t)c->n16 * 16) * sizeof(double);
-        if (q_lds < RQ_LDS_MIN) q_lds = RQ_LDS_MIN;
-        const int NBq = (int)(c->n16 / 16);
-        const int cs = chain_share(NBq, c->dbg);
-        if (cd_queue_applies(c, a1.prof != nullptr) && chain_range_ok(NBq, cs)) {
-            // restart-level scheduling (cd_queue.h): 16 slots per workgroup, refilled from a device-side queue
-            used_lds = true;
-            int rcq;
-            if (!c->q_prepared && (rcq = cd_queue_prepare(c))) return rcq;
-            c->q_prepared = false;
-            CdQueueArgs qa;
-            qa.P = dp; qa.num_iters = a1.num_iters; qa.tol = a1.tol; qa.life = nullptr; qa.life_on = 0;
-            cd_queue_fill_batch(c, qa.b, a1.seed, a1.first_index);
-            if (cd_debug) fprintf(stderr, "launch_cd: cd_phase2_qs_kernel CS %d\n", cs);
-            int cus = 0;
-            HIPCHK(c, hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device));
-            (void)hipEventRecord(c->timers[2].beg, c->stream);
-            hipError_t qe = (hipError_t)cd_queue_launch(qa, cs, cus, c->stream);
-            (void)hipEventRecord(c->timers[2].end, c->stream);
-            c->timers[2].valid = true;
-            if (qe != hipSuccess) return fail(c, QCQPMI_EHIP, "cd_queue_launch: %s", hipGetErrorString(qe));
-            c->last_cd2_kernel = "cd_phase2_qs_kernel";
-            if (used_rs) *used_rs = true;
-            return 0;
-        }
-        if (q_lds <= 160 * 1024 && chain_range_ok(NBq, cs)) {
-            used_lds = true;
-            const bool prof_ = a1.prof != nullptr;
-            auto k = cd_phase2_q_kernel<4, false>;
-            if (prof_) k = cs == 0 ? cd_phase2_q_kernel<0, true> : cs == 2 ? cd_phase2_q_kernel<2, true> : cs == 4 ? cd_phase2_q_kernel<4, true> : cd_phase2_q_kernel<6, true>;
-            else k = cs == 0 ? cd_phase2_q_kernel<0, false> : cs == 2 ? cd_phase2_q_kernel<2, false> : cs == 4 ? cd_phase2_q_kernel<4, false> : cd_phase2_q_kernel<6, false>;
-            HIPCHK(c, hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)q_lds));
-            if (cd_debug) fprintf(stderr, "launch_cd: cd_phase2_q_kernel CS %d\n", cs);
-            tic(c, 2);
-            hipLaunchKernelGGL(k, grid, dim3(512), q_lds, c->stream, a1, dp.Apack, dp.Apack2, dp.P0, dp.q0, dp.rcp2d);
-            toc(c, 2);
-            c->last_cd2_kernel = "cd_phase2_q_kernel";
-            HIPCHK(c, hipGetLastError());
-            if (used_rs) *used_rs = true;
-            return 0;
-        }
-    }
-    // role-split pipelined kernel for the single-class Boolean / box families
-    if (MAXC == 1 && c->K == 1 && (c->objclass == 1 || c->objclass == 2) && !c->force_generic) {
-        const size_t rs_common = (size_t)(2 * 6 * 256 + 256 + 2 * 256 + 2 * 16 + 2 * 16 + 16 + 4 * 16 + 8 + 8 + 8) * sizeof(double);
-        const size_t rs_with_x = rs_common + (size_t)c->n16 * 16 * sizeof(double);
-        used_lds = rs_with_x <= 160 * 1024;
-        const size_t rs_lds = used_lds ? rs_with_x : rs_common;
-        dim3 block512(512);
-#define QM_RS(XL, FA)                                                                               \
-    do {                                                                                            \
-        auto k = cd_phase2_rs_kernel<XL, FA, false, false, false>;                                  \
-        const bool full_ = (c->n % 16 == 0), sym_ = c->symcls, prof_ = a1.prof != nullptr;          \
-        if (prof_) k = full_ ? (sym_ ? cd_phase2_rs_kernel<XL, FA, true, true, true> : cd_phase2_rs_kernel<XL, FA, true, false, true>) \
-                             : (sym_ ? cd_phase2_rs_kernel<XL, FA, false, true, true> : cd_phase2_rs_kernel<XL, FA, false, false, true>); \
-        else k = full_ ? (sym_ ? cd_phase2_rs_kernel<XL, FA, true, true, false> : cd_phase2_rs_kernel<XL, FA, true, false, false>) \
-                       : (sym_ ? cd_phase2_rs_kernel<XL, FA, false, true, false> : cd_phase2_rs_kernel<XL, FA, false, false, false>); \
-        HIPCHK(c, hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)rs_lds)); \
-        if (cd_debug) fprintf(stderr, "launch_cd: cd_phase2_rs_kernel XL %d FA %d FULL %d SYM %d\n", (int)XL, FA, (int)full_, (int)sym_); \
-        tic(c, 2);                                                                                  \
-        hipLaunchKernelGGL(k, grid, block512, rs_lds, c->stream, a1, dp.Apack, dp.Apack2, dp.P0, dp.q0, dp.rcp2d); \
-        toc(c, 2);                                                                                  \
-    } while (0)
-        if (used_lds && c->objclass == 1) QM_RS(true, 1);
-        else if (used_lds) QM_RS(true, 2);
-        else if (c->objclass == 1) QM_RS(false, 1);
-        else QM_RS(false, 2);
-#undef QM_RS
-        c->last_cd2_kernel = "cd_phase2_rs_kernel";
-        HIPCHK(c, hipGetLastError());
-        if (used_rs) *used_rs = true;
-        return 0;
-    }
-    // dynamic LDS: [X tile] + partial tiles + G + diagonal block + slack + feasible-set table
-    const bool use_cls = c->K <= 16;
-    const size_t slots = use_cls ? (size_t)c->K * 16 : 0;
-    size_t common = (size_t)(4 * 256 + 256 + 256 + 3 * 16 + 512) * sizeof(double) +              // part, G, Dblk, slk/q0b/rcpb, midb/thrb
-                    (size_t)(2 * (MAXC + 1) * 256 + 256) * sizeof(double) +                      // block table
-                    ((size_t)(2 * (MAXC + 1)) * slots + ((slots + 1) / 2) * 2) * sizeof(double) + // class table
-                    64;
-    size_t with_x = common + (size_t)c->n16 * 16 * sizeof(double);
-    used_lds = with_x <= 160 * 1024;
-    const size_t lds = used_lds ? with_x : common;
-    const int fast = (MAXC == 1) ? c->objclass : 0;
-    const bool uni = use_cls && c->K == 1;
-#define QM_LAUNCH2(XL, CL, FA, UN)                                                                     \
-    do {                                                                                            \
-        auto k = cd_phase2_kernel<MAXC, XL, CL, FA, UN>;                                                \
-        HIPCHK(c, hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-        if (cd_debug) fprintf(stderr, "launch_cd: cd_phase2_kernel MAXC %d XL %d CL %d FA %d UN %d\n", MAXC, (int)XL, (int)CL, FA, (int)UN); \
-        tic(c, 2);                                                                                  \
-        hipLaunchKernelGGL(k, grid, block, lds, c->stream, a1, dp.Apack, dp.P0, dp.q0, dp.rcp2d, dp.cls);      \
-        toc(c, 2);                                                                                  \
-    } while (0)
-#define QM_LAUNCH(XL, CL)                                                 \
-    do {                                                                  \
-        if (fast == 1 && uni && CL) QM_LAUNCH2(XL, CL, 1, CL);            \
-        else if (fast == 2 && uni && CL) QM_LAUNCH2(XL, CL, 2, CL);       \
-        else if (fast == 1) QM_LAUNCH2(XL, CL, 1, false);                 \
-        else if (fast == 2) QM_LAUNCH2(XL, CL, 2, false);                 \
-        else QM_LAUNCH2(XL, CL, 0, false);                                \
-    } while (0)
-    if (used_lds && use_cls) QM_LAUNCH(true, true);
-    else if (used_lds) QM_LAUNCH(true, false);
-    else if (use_cls) QM_LAUNCH(false, true);
-    else QM_LAUNCH(false, false);
-#undef QM_LAUNCH
-#undef QM_LAUNCH2
-    HIPCHK(c, hipGetLastError());
-    return 0;
-}
-
-}  // namespace
-
-#include "cd_dense_mw.h"
-// which chain kernel the dense path dispatches to (four waves per restart unless a thread would hold more than 8 slots)
-static bool dense_chain_mw(const qcqpmi_ctx *c) { return c->dense_chain_mode != 1 && mw_geometry((int)c->m + 1).SL <= 8; }
-static const char *dense_chain_name(const qcqpmi_ctx *c) { return dense_chain_mw(c) ? "dense_chain_mw_kernel" : "dense_chain_kernel"; }
-#include "capi_dense.inc"
-
-// coordinate descent for constraints that couple coordinates (cd_general.h)
-int cd_run_general(qcqpmi_ctx *c, int phase1, int64_t num_iters, double viol_tol, double tol, uint64_t seed,
-                   uint64_t first_index, int64_t *sweeps1, int64_t *sweeps2, int64_t *visits2, int64_t *accepted2,
-                   uint8_t *ran_phase2, double *f0, double *maxviol) {
-    if (!c->d_gP) return fail(c, QCQPMI_EUNSUPPORTED, "coupled constraints: dense storage m*n*n exceeds 16 GB");
-    if (num_iters < 0 || !(tol > 0.0)) return fail(c, QCQPMI_EINVAL, "cd_run: bad num_iters / tol");
-    const int64_t m = c->m;
-    const size_t lds = ((size_t)(m + 1) * 16 * 4 + 4 * 16 * GEN_CAP + 16 * GEN_CAP + 16) * sizeof(double);
-    if (lds > 160 * 1024) return fail(c, QCQPMI_EUNSUPPORTED, "coupled constraints: m = %lld too large for the LDS-resident coefficient table", (long long)m);
-    HIPCHK(c, hipSetDevice(c->device));
-    int rc;
-    CdGenArgs g;
-    CdArgs &a = g.b;
-    a.P = c->dp; a.X = c->X; a.R = c->R; a.f0cur = c->d_f0; a.slack = c->d_mv;
-    a.num_iters = num_iters; a.viol_tol = viol_tol; a.tol = tol; a.seed = seed; a.first_index = first_index;
-    a.visits = c->d_visits; a.accepted = c->d_acc; a.sweeps = c->d_sweeps; a.status = c->d_status;
-    a.flag = c->d_flag; a.prof = nullptr; a.dbg = 0; a.f0out = nullptr; a.mvout = nullptr;
-    g.gP = c->d_gP; g.Rpad = c->Rpad;
-    g.exact_t0 = ((c->n <= 64 || c->cd_ref_order) && !(c->dbg & 16)) ? 1 : 0;   // small problems (or on request): the reference's own arithmetic for t0
-    dim3 grid((unsigned)(c->Rpad / 16)), block(256);
-    auto k1 = cd_general_kernel<1>;
-    auto k2 = cd_general_kernel<2>;
-    HIPCHK(c, hipFuncSetAttribute((const void *)k1, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    HIPCHK(c, hipFuncSetAttribute((const void *)k2, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    HIPCHK(c, hipMemsetAsync(c->d_sweeps1, 0, (size_t)c->Rpad * sizeof(int64_t), c->stream));
-    HIPCHK(c, hipMemsetAsync(c->d_status1, 0, (size_t)c->Rpad * sizeof(int), c->stream));
-    if (phase1) {
-        if ((rc = launch_eval(c, true))) return rc;
-        g.F = c->d_F;
-        CdGenArgs g1 = g;
-        g1.b.sweeps = c->d_sweeps1;
-        g1.b.status = c->d_status1;
-        tic(c, 1);
-        hipLaunchKernelGGL(k1, grid, block, lds, c->stream, g1);
-        toc(c, 1);
-        HIPCHK(c, hipGetLastError());
-    }
-    if ((rc = launch_eval(c, true))) return rc;
-    g.F = c->d_F;
-    hipLaunchKernelGGL(gate_kernel, dim3((unsigned)((c->Rpad + 255) / 256)), dim3(256), 0, c->stream, c->d_mv,
-                       c->d_status1, c->d_flag, c->R, c->Rpad, viol_tol);
-    HIPCHK(c, hipGetLastError());
-    if (ran_phase2) HIPCHK(c, hipMemcpyAsync(ran_phase2, c->d_flag, (size_t)c->R, hipMemcpyDeviceToHost, c->stream));
-    tic(c, 2);
-    hipLaunchKernelGGL(k2, grid, block, lds, c->stream, g);
-    toc(c, 2);
-    HIPCHK(c, hipGetLastError());
-    if ((rc = launch_eval(c, false))) return rc;
-    std::vector<int> st, st1;
-    if ((rc = fetch_cd_outputs(c, sweeps1, sweeps2, visits2, accepted2, nullptr, f0, maxviol, st, st1))) return rc;
-    if ((rc = cd_apply_status(c, st, st1, f0, maxviol, GEN_CAP))) return rc;
-    return 0;
-}
+}  // namespace qcqpmi
 
 // ============================================================================================
 
@@ -622,10 +262,7 @@ int qcqpmi_set_quad(qcqpmi_ctx *c, int64_t k, int format, const double *vals, co
             src = dense.data();
         }
         HIPCHK(c, hipMemcpyAsync(c->dn_tmp, src, (size_t)n * n * sizeof(double), hipMemcpyHostToDevice, c->stream));
-        const int64_t total = n16 * n16;
-        // (dense_pack_kernel addresses function k at gP + (k - 1) n n: hand it a base that puts the staging buffer there)
-        hipLaunchKernelGGL(dense_pack_kernel, dim3((unsigned)((total + 255) / 256), 1), dim3(256), 0, c->stream, (const double *)nullptr,
-                           (const double *)(c->dn_tmp - (k - 1) * n * n), c->dn_gp_pre, n, n16, (int)m1, (int)k);
+        launch_dense_pack_staged(c, k, c->dn_gp_pre);
         HIPCHK(c, hipGetLastError());
         HIPCHK(c, spin_sync(c->stream));      // the staging buffer and the caller's array are free again
         std::vector<int>().swap(h.ci); std::vector<int>().swap(h.cj); std::vector<double>().swap(h.cv);
@@ -633,28 +270,6 @@ int qcqpmi_set_quad(qcqpmi_ctx *c, int64_t k, int format, const double *vals, co
     }
     h.q.assign(q, q + n);
     h.r = r; h.relop = relop; h.set = true;
-    return 0;
-}
-
-int qcqpmi_set_quad_generated(qcqpmi_ctx *c, int64_t k, uint64_t seed, double scale, double qscale,
-                              double diag_add, double r, int relop) {
-    if (!c) return QCQPMI_EINVAL;
-    if (c->finalized) return fail(c, QCQPMI_ESTATE, "set_quad_generated after finalize");
-    if (k < 0 || k > c->m) return fail(c, QCQPMI_EINVAL, "set_quad_generated: bad k");
-    if ((k == 0) != (relop == 0) || relop < 0 || relop > 2)
-        return fail(c, QCQPMI_EINVAL, "set_quad_generated: relop %d invalid for function %lld", relop, (long long)k);
-    HostQuad &h = c->quads[(size_t)k];
-    h = HostQuad();
-    h.gen = true; h.gseed = seed; h.gscale = scale; h.gqscale = qscale; h.gdiag = diag_add;
-    h.r = r; h.relop = relop; h.set = true;
-    // the linear term comes back to the host (n values): the generic finalize code reads it there
-    HIPCHK(c, hipSetDevice(c->device));
-    DevBuf<double> dq;
-    HIPCHK(c, dq.reserve(c->stream, (size_t)c->n, false));
-    hipLaunchKernelGGL(dense_gen_q_kernel, dim3((unsigned)((c->n + 255) / 256)), dim3(256), 0, c->stream, dq.p, c->n, (int)k, seed, qscale);
-    h.q.resize((size_t)c->n);
-    HIPCHK(c, hipMemcpyAsync(h.q.data(), dq.p, (size_t)c->n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, spin_sync(c->stream));
     return 0;
 }
 
@@ -677,8 +292,7 @@ int qcqpmi_finalize(qcqpmi_ctx *c) {
         if (h.gen) {   // generated on the device, mirrored to the host for the diagonal classification below
             DevBuf<double> tmp;
             HIPCHK(c, tmp.reserve(c->stream, (size_t)n16 * n16, false));
-            hipLaunchKernelGGL(dense_gen_rowmajor_kernel, dim3((unsigned)((n16 * n16 + 255) / 256)), dim3(256), 0, c->stream,
-                               tmp.p, n, n16, 0, h.gseed, h.gscale, h.gdiag);
+            launch_dense_gen_rowmajor(c, tmp.p, 0, h.gseed, h.gscale, h.gdiag);
             HIPCHK(c, hipMemcpyAsync(P.data(), tmp.p, P.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
             HIPCHK(c, spin_sync(c->stream));
         }
@@ -999,15 +613,7 @@ int qcqpmi_pop_sdr_sample(qcqpmi_ctx *c, const double *mu, const double *F, int6
     tic(c, 3);
     if (c->dp.NB >= 8 && c->Rpad / 16 >= 8) {
         // x = mu + F xi as one LDS-tiled MFMA GEMM (8 row blocks of F x 8 tiles of samples per workgroup)
-        DenseProdArgs pa;
-        pa.D.Gpack = c->d_Fpack; pa.D.q = c->d_mu; pa.D.qT = nullptr; pa.D.r = nullptr; pa.D.relop = nullptr;
-        pa.D.n = n; pa.D.n16 = n16; pa.D.NB = (int)c->dp.NB; pa.D.KS = (int)c->dp.KS; pa.D.m1 = 1; pa.D.m1p = 64;
-        pa.X = c->Xi; pa.ntiles = (int)(c->Rpad / 16); pa.b = 0; pa.zs = 1; pa.G = c->X; pa.F = nullptr; pa.Rpad = c->Rpad;
-        pa.tile_on = nullptr; pa.hole = -1; pa.ch_only = -1; pa.zplane = 0;
-        auto kg = dense_products_kernel<3>;
-        HIPCHK(c, hipFuncSetAttribute((const void *)kg, hipFuncAttributeMaxDynamicSharedMemorySize, DP_LDS_BYTES));
-        hipLaunchKernelGGL(kg, dim3((unsigned)((pa.D.NB + DP_FG - 1) / DP_FG), (unsigned)((pa.ntiles + DP_TG - 1) / DP_TG), 1),
-                           dim3(256), DP_LDS_BYTES, c->stream, pa);
+        if ((rc = launch_dense_product(c, 3, c->d_Fpack, c->d_mu, c->Xi, c->X))) return rc;
     } else {
         hipLaunchKernelGGL(affine_tiles_kernel, dim3((unsigned)(c->Rpad / 16)), dim3(256), 0, c->stream,
                            c->d_Fpack, c->d_mu, c->Xi, c->X, n, n16, c->dp.NB, c->dp.KS);
@@ -1065,45 +671,6 @@ int qcqpmi_sdr_sample_eval(qcqpmi_ctx *c, const double *mu, const double *F, int
     return 0;
 }
 
-int qcqpmi_pop_weighted_product(qcqpmi_ctx *c, const double *w, double *Y) {
-    int rc = check_ready(c, true);
-    if (rc) return rc;
-    if (!w || !Y) return fail(c, QCQPMI_EINVAL, "pop_weighted_product: w / Y missing");
-    HIPCHK(c, hipSetDevice(c->device));
-    DenseProblem D = dense_problem(c);
-    if (!c->dn_Gpack) {
-        // separable constraints: only the objective has a matrix (the packed P0 of the separable path: the same fragment
-        // layout with one function); the weights of the constraints are the caller's business (elementwise operators)
-        D.Gpack = c->dp.Apack; D.m1 = 1; D.m1p = 64; D.q = nullptr; D.qT = nullptr; D.r = nullptr; D.relop = nullptr;
-    }
-    const int64_t n16 = c->n16, ntiles = c->Rpad / 16;
-    HIPCHK(c, c->d_ww.reserve(c->stream, (size_t)D.m1, false));
-    HIPCHK(c, c->d_wS.reserve(c->stream, (size_t)n16 * n16, false));
-    HIPCHK(c, c->d_wz.reserve(c->stream, (size_t)n16));   // zero offset vector of the affine map
-    HIPCHK(c, c->d_wY.reserve(c->stream, (size_t)c->Rpad * n16, false));
-    double *dw = c->d_ww, *dS = c->d_wS, *dY = c->d_wY, *dz = c->d_wz;
-    const int64_t total = c->R * c->n;
-    if ((rc = pin_reserve(c, (size_t)total * sizeof(double) + (size_t)D.m1 * sizeof(double)))) return rc;
-    char *hw = c->h_pin + (size_t)total * sizeof(double);       // the weights go up through pinned memory too
-    memcpy(hw, w, (size_t)D.m1 * sizeof(double));
-    HIPCHK(c, hipMemcpyAsync(dw, hw, (size_t)D.m1 * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    hipLaunchKernelGGL(dense_wsum_pack_kernel, dim3((unsigned)((n16 * n16 + 255) / 256)), dim3(256), 0, c->stream, D, (const double *)dw, dS);
-    DenseProdArgs pa;
-    pa.D = D; pa.D.Gpack = dS; pa.D.q = dz; pa.D.m1 = 1; pa.D.m1p = 64;
-    pa.X = c->X; pa.ntiles = (int)ntiles; pa.b = 0; pa.zs = 1; pa.G = dY; pa.F = nullptr; pa.Rpad = c->Rpad;
-    pa.tile_on = nullptr; pa.hole = -1; pa.ch_only = -1; pa.zplane = 0;
-    auto kg = dense_products_kernel<3>;
-    HIPCHK(c, hipFuncSetAttribute((const void *)kg, hipFuncAttributeMaxDynamicSharedMemorySize, DP_LDS_BYTES));
-    hipLaunchKernelGGL(kg, dim3((unsigned)((D.NB + DP_FG - 1) / DP_FG), (unsigned)((ntiles + DP_TG - 1) / DP_TG), 1),
-                       dim3(256), DP_LDS_BYTES, c->stream, pa);
-    launch_from_tiles(c, dY, c->R);
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(c->h_pin, c->d_stage, (size_t)total * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, spin_sync(c->stream));
-    memcpy(Y, c->h_pin, (size_t)total * sizeof(double));
-    return 0;
-}
-
 int qcqpmi_get_linear(qcqpmi_ctx *c, int64_t k, double *q, double *r, int *relop) {
     if (!c) return QCQPMI_EINVAL;
     if (k < 0 || k > c->m || !c->quads[(size_t)k].set) return fail(c, QCQPMI_EINVAL, "get_linear: bad k");
@@ -1114,163 +681,10 @@ int qcqpmi_get_linear(qcqpmi_ctx *c, int64_t k, double *q, double *r, int *relop
     return 0;
 }
 
-int qcqpmi_weighted_matrix(qcqpmi_ctx *c, const double *w, double *S) {
-    int rc = check_ready(c, false);
-    if (rc) return rc;
-    if (!w || !S) return fail(c, QCQPMI_EINVAL, "weighted_matrix: w / S missing");
-    if (!c->dn_Gpack) return fail(c, QCQPMI_EUNSUPPORTED, "weighted_matrix needs the packed dense matrices");
-    HIPCHK(c, hipSetDevice(c->device));
-    const DenseProblem D = dense_problem(c);
-    const int64_t n = c->n, n16 = c->n16;
-    DevBuf<double> dw, dS, dU;
-    HIPCHK(c, dw.reserve(c->stream, (size_t)D.m1, false));
-    HIPCHK(c, dS.reserve(c->stream, (size_t)n16 * n16, false));
-    HIPCHK(c, dU.reserve(c->stream, (size_t)n * n, false));
-    HIPCHK(c, hipMemcpyAsync(dw.p, w, (size_t)D.m1 * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    hipLaunchKernelGGL(dense_wsum_pack_kernel, dim3((unsigned)((n16 * n16 + 255) / 256)), dim3(256), 0, c->stream, D, (const double *)dw.p, dS.p);
-    hipLaunchKernelGGL(dense_unpack_kernel, dim3((unsigned)((n * n + 255) / 256)), dim3(256), 0, c->stream, (const double *)dS.p, dU.p, n, (int)(n16 / 4));
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(S, dU.p, (size_t)n * n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, spin_sync(c->stream));
-    return 0;
-}
-
-int qcqpmi_pop_eval_parts(qcqpmi_ctx *c, double *quad, double *lin) {
-    int rc = check_ready(c, true);
-    if (rc) return rc;
-    if (!quad || !lin) return fail(c, QCQPMI_EINVAL, "pop_eval_parts: outputs missing");
-    if (!c->dn_Gpack) return fail(c, QCQPMI_EUNSUPPORTED, "pop_eval_parts needs the packed dense matrices (constraints that couple coordinates)");
-    HIPCHK(c, hipSetDevice(c->device));
-    if ((rc = eval_parts_dense(c))) return rc;
-    const int64_t m1 = c->m + 1;
-    const double *dlin = c->d_F + (int64_t)c->eval_zs * m1 * c->Rpad;
-    // the two planes ([m1][Rpad], contiguous) through pinned memory in one copy each, the padding columns dropped on the host
-    const size_t plane = (size_t)m1 * c->Rpad * sizeof(double);
-    if ((rc = pin_reserve(c, 2 * plane))) return rc;
-    HIPCHK(c, hipMemcpyAsync(c->h_pin, c->d_F, plane, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->h_pin + plane, dlin, plane, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, spin_sync(c->stream));
-    const double *hq = (const double *)c->h_pin.p, *hl = (const double *)(c->h_pin + plane);
-    for (int64_t k = 0; k < m1; k++) {
-        memcpy(quad + k * c->R, hq + k * c->Rpad, (size_t)c->R * sizeof(double));
-        memcpy(lin + k * c->R, hl + k * c->Rpad, (size_t)c->R * sizeof(double));
-    }
-    c->evaluated = false;    // plane 0 no longer holds the full function values
-    return 0;
-}
-
 int qcqpmi_eval_batch(qcqpmi_ctx *c, const double *X, int64_t S, double *f0, double *maxviol, double *F) {
     int rc = qcqpmi_pop_upload(c, X, S);
     if (rc) return rc;
     return qcqpmi_pop_eval(c, f0, maxviol, F);
-}
-
-// ------------------------------------------------------------------------- coordinate descent
-
-// stage 0: the whole run.  Stages 1-3 split it for callers that overlap the preparation of the NEXT population with the
-// phase-2 kernel of the current one (two contexts = two streams): 1 = phase 1 + evaluation + gate (asynchronous),
-// 2 = launch of phase 2 (asynchronous), 3 = results (blocking).  Paths without a pipelined phase-2 kernel run everything
-// in stage 3.
-int qcqpmi_cd_run_stage(qcqpmi_ctx *c, int stage, int phase1, int64_t num_iters, double viol_tol, double tol,
-                        uint64_t seed, uint64_t first_index, int64_t *sweeps1, int64_t *sweeps2,
-                        int64_t *visits2, int64_t *accepted2, uint8_t *ran_phase2, double *f0,
-                        double *maxviol) {
-    int rc = check_ready(c, true);
-    if (rc) return rc;
-    if (stage < 0 || stage > 3) return fail(c, QCQPMI_EINVAL, "cd_run_stage: stage %d", stage);
-    if (stage >= 2 && c->cd_stage != stage - 1) return fail(c, QCQPMI_ESTATE, "cd_run_stage: stage %d without stage %d", stage, stage - 1);
-    const bool whole = dense_on(c) || !c->sep;      // these paths are not split
-    if (whole) {
-        if (stage == 1 || stage == 2) { c->cd_stage = stage; return 0; }
-        c->cd_stage = 0;
-        c->last_cd2_kernel = (dense_on(c) && !c->cd_ref_order) ? dense_chain_name(c) : "cd_general_kernel";
-        if (c->cd_ref_order && !c->d_gP)
-            return fail(c, QCQPMI_EUNSUPPORTED, "reference-order coordinate descent needs the row-major constraint matrices "
-                        "(uploaded functions, m n^2 <= 2e9 entries); device-generated functions only exist packed");
-        if (dense_on(c) && !c->cd_ref_order) return cd_run_dense(c, phase1, num_iters, viol_tol, tol, seed, first_index, sweeps1, sweeps2, visits2,
-                                             accepted2, ran_phase2, f0, maxviol);
-        return cd_run_general(c, phase1, num_iters, viol_tol, tol, seed, first_index, sweeps1, sweeps2, visits2,
-                              accepted2, ran_phase2, f0, maxviol);
-    }
-    if (num_iters < 0 || !(tol > 0.0)) return fail(c, QCQPMI_EINVAL, "cd_run: bad num_iters / tol");
-    HIPCHK(c, hipSetDevice(c->device));
-    CdArgs a;
-    a.P = c->dp; a.X = c->X; a.R = c->R; a.f0cur = c->d_f0; a.slack = c->d_mv;
-    a.num_iters = num_iters; a.viol_tol = viol_tol; a.tol = tol; a.seed = seed; a.first_index = first_index;
-    a.visits = c->d_visits; a.accepted = c->d_acc; a.sweeps = c->d_sweeps; a.status = c->d_status;
-    a.flag = c->d_flag;
-    a.prof = nullptr; a.f0out = nullptr; a.mvout = nullptr;
-    a.dbg = c->dbg;
-    bool used_lds = false;
-    // Everything below is enqueued on the context's stream without a host round trip: phase 1,
-    // evaluation, the improve_coord_descent gate, phase 2, final evaluation, result copies.
-    if (stage == 0 || stage == 1) {
-        HIPCHK(c, hipMemsetAsync(c->d_sweeps1, 0, (size_t)c->Rpad * sizeof(int64_t), c->stream));
-        HIPCHK(c, hipMemsetAsync(c->d_status1, 0, (size_t)c->Rpad * sizeof(int), c->stream));
-        if (phase1) {
-            CdArgs a1 = a;
-            a1.sweeps = c->d_sweeps1;
-            a1.status = c->d_status1;
-            rc = (c->maxc <= 1) ? launch_cd<1>(c, a1, true, used_lds) : launch_cd<4>(c, a1, true, used_lds);
-            if (rc) return rc;
-        }
-        // gate of improve_coord_descent (qcqp.py:189): phase 2 only if max violation < viol_tol.
-        // The evaluation also provides the phase-2 slack (qcqp.py:157) and the running objective.
-        if ((rc = launch_eval(c, false))) return rc;
-        hipLaunchKernelGGL(gate_kernel, dim3((unsigned)((c->Rpad + 255) / 256)), dim3(256), 0, c->stream, c->d_mv,
-                           c->d_status1, c->d_flag, c->R, c->Rpad, viol_tol);
-        HIPCHK(c, hipGetLastError());
-        c->q_prepared = false;
-        if (cd_queue_applies(c, c->profile) && (rc = cd_queue_prepare(c))) return rc;     // queue reset + population published
-        if (stage == 1) { c->cd_stage = 1; return 0; }
-    }
-    if (stage == 0 || stage == 2) {
-        if (c->profile) {
-            const size_t words = (size_t)(c->Rpad / 16) * 16 + QCQPMI_TRACE_WORDS;
-            HIPCHK(c, c->d_prof.reserve(c->stream, words, false));
-            HIPCHK(c, hipMemsetAsync(c->d_prof, 0, words * sizeof(long long), c->stream));
-            a.prof = c->d_prof;
-        }
-        // the pipelined kernel leaves objective and max violation of the restarts it ran in place (tracked objective,
-        // element-wise violations of the final tile): no evaluation pass afterwards
-        bool used_rs = false;
-        a.f0out = c->d_f0; a.mvout = c->d_mv;
-        rc = (c->maxc <= 1) ? launch_cd<1>(c, a, false, used_lds, &used_rs) : launch_cd<4>(c, a, false, used_lds, &used_rs);
-        if (rc) return rc;
-        if (!used_rs && (rc = launch_eval(c, false))) return rc;
-        if (stage == 2) { c->cd_stage = 2; return 0; }
-    }
-    c->cd_stage = 0;
-    std::vector<int> st, st1;
-    if ((rc = fetch_cd_outputs(c, sweeps1, sweeps2, visits2, accepted2, ran_phase2, f0, maxviol, st, st1))) return rc;
-    if ((rc = cd_apply_status(c, st, st1, f0, maxviol, 0))) return rc;
-    return 0;
-}
-
-int qcqpmi_cd_run(qcqpmi_ctx *c, int phase1, int64_t num_iters, double viol_tol, double tol,
-                  uint64_t seed, uint64_t first_index, int64_t *sweeps1, int64_t *sweeps2,
-                  int64_t *visits2, int64_t *accepted2, uint8_t *ran_phase2, double *f0,
-                  double *maxviol) {
-    return qcqpmi_cd_run_stage(c, 0, phase1, num_iters, viol_tol, tol, seed, first_index, sweeps1, sweeps2, visits2, accepted2,
-                               ran_phase2, f0, maxviol);
-}
-
-int qcqpmi_cd_dense_block_step(qcqpmi_ctx *c, int phase, int64_t sweep, int64_t block, int coord_lo, int coord_hi, double viol_tol,
-                               double tol, uint64_t seed, uint64_t first_index, const double *slack) {
-    int rc = check_ready(c, true);
-    if (rc) return rc;
-    if (!dense_on(c)) return fail(c, QCQPMI_EUNSUPPORTED, "cd_dense_block_step: the problem does not take the dense-constraint path");
-    c->last_cd2_kernel = dense_chain_name(c);
-    return cd_dense_block_step(c, phase, sweep, block, coord_lo, coord_hi, viol_tol, tol, seed, first_index, slack);
-}
-
-int qcqpmi_cd_status(qcqpmi_ctx *c, int *status1, int *status2) {
-    if (!c) return QCQPMI_EINVAL;
-    if ((int64_t)c->last_st1.size() != c->R || (int64_t)c->last_st2.size() != c->R)
-        return fail(c, QCQPMI_ESTATE, "cd_status: no coordinate-descent run on the resident population");
-    if (status1) memcpy(status1, c->last_st1.data(), (size_t)c->R * sizeof(int));
-    if (status2) memcpy(status2, c->last_st2.data(), (size_t)c->R * sizeof(int));
-    return 0;
 }
 
 // -------------------------------------------------------------------------------- best of pop
@@ -1303,18 +717,6 @@ int qcqpmi_select_best(qcqpmi_ctx *c, double tol, int64_t *best_index, double *b
 
 const char *qcqpmi_last_cd_kernel(qcqpmi_ctx *c) { return c ? c->last_cd2_kernel : ""; }
 
-int qcqpmi_cd_queue(qcqpmi_ctx *c, int mode) {
-    if (!c || mode < 0 || mode > 2) return QCQPMI_EINVAL;
-    c->cd_queue = mode;
-    return 0;
-}
-
-int qcqpmi_cd_reference_order(qcqpmi_ctx *c, int enable) {
-    if (!c) return QCQPMI_EINVAL;
-    c->cd_ref_order = enable != 0;
-    return 0;
-}
-
 int qcqpmi_last_kernel_ms(qcqpmi_ctx *c, int which, double *ms) {
     if (!c || which < 0 || which > 4 || !ms) return QCQPMI_EINVAL;
     if (!c->timers[which].valid) return fail(c, QCQPMI_ESTATE, "kernel %d has not been launched", which);
@@ -1323,48 +725,6 @@ int qcqpmi_last_kernel_ms(qcqpmi_ctx *c, int which, double *ms) {
     HIPCHK(c, hipEventElapsedTime(&f, c->timers[which].beg, c->timers[which].end));
     *ms = (double)f;
     return 0;
-}
-
-int qcqpmi_dense_chain_geometry(int64_t m, int *out4) {
-    if (m < 0 || m > (1 << 24) || !out4) return QCQPMI_EINVAL;
-    const MwGeom g = mw_geometry((int)m + 1);
-    out4[0] = g.SL; out4[1] = g.Tc; out4[2] = g.ts; out4[3] = g.T;
-    return 0;
-}
-
-int qcqpmi_dense_chain_mode(qcqpmi_ctx *c, int mode) {
-    if (!c || mode < 0 || mode > 1) return QCQPMI_EINVAL;
-    c->dense_chain_mode = mode;
-    return 0;
-}
-
-int qcqpmi_debug_profile(qcqpmi_ctx *c, int enable, int64_t *sums8) {
-    if (!c) return QCQPMI_EINVAL;
-    c->profile = (enable & 1) != 0;
-    c->force_generic = (enable & 2) != 0;
-    c->dbg = enable >> 4;
-    if (sums8 && c->d_prof && c->Rpad > 0) {
-        std::vector<long long> h((size_t)(c->Rpad / 16) * 16);
-        HIPCHK(c, hipMemcpy(h.data(), c->d_prof, h.size() * sizeof(long long), hipMemcpyDeviceToHost));
-        for (int k = 0; k < 16; k++) sums8[k] = 0;
-        for (size_t t = 0; t < h.size(); t++) sums8[t & 15] += h[t];
-    }
-    return 0;
-}
-
-// debug: event trace of tile 0 written by the profiled phase-2 kernel (8 slices of 256 words, one per wave: entries of
-// 4 timestamps per block / product; see cd_phase2_q.h)
-int qcqpmi_debug_trace(qcqpmi_ctx *c, int64_t *out, int count) {
-    if (!c || !out || count < 0 || count > QCQPMI_TRACE_WORDS) return QCQPMI_EINVAL;
-    if (!c->d_prof || c->Rpad <= 0) return fail(c, QCQPMI_EINVAL, "no profiled run to trace");
-    HIPCHK(c, hipMemcpy(out, c->d_prof + (size_t)(c->Rpad / 16) * 16, (size_t)count * sizeof(long long), hipMemcpyDeviceToHost));
-    return 0;
-}
-
-int qcqpmi_debug_dense_profile(qcqpmi_ctx *c, int64_t *out64) {
-    if (!c || !out64) return QCQPMI_EINVAL;
-    HIPCHK(c, hipSetDevice(c->device));
-    return dense_profile_read(c, out64);
 }
 
 int qcqpmi_sync(qcqpmi_ctx *c) {

@@ -1,11 +1,12 @@
-// Internal header of the host side of the C ABI: what two or more of its units (capi.hip, capi_admm.hip, capi_small.hip,
-// capi_units.hip, capi_comm.hip, capi_stream.hip) need, and nothing else -- the context, the error slot, the event timers and the few host
-// functions one unit calls in another.  Types and host declarations only: no kernel is defined in anything included here,
+// Internal header of the host side of the C ABI: what two or more of its units (capi.hip, capi_cd.hip, capi_dense.hip, capi_admm.hip,
+// capi_small.hip, capi_units.hip, capi_comm.hip, capi_stream.hip) need, and nothing else -- the context, the error slot, the event timers
+// and the few host functions one unit calls in another.  Types and host declarations only: no kernel is defined in anything included here,
 // so a unit that includes it compiles device code only for the kernel headers it names itself.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <algorithm>
 #include <string>
 #include <vector>
 
@@ -179,7 +180,29 @@ inline void toc(qcqpmi_ctx *c, int which) {
     c->timers[which].valid = true;
 }
 
-// Launches of the three kernels of kernels_impl.h that a unit other than capi.hip needs: enqueued on c->stream, no wait (the
+// `count` elements of the problem's own storage: owned by prob_allocs until the context goes (qcqpmi_finalize, and dense_build of
+// capi_dense.hip for the packed matrices and their vectors)
+template <typename T>
+int prob_alloc(qcqpmi_ctx *c, T **dst, size_t count) {
+    DevBuf<char> b;
+    HIPCHK(c, b.reserve(c->stream, std::max<size_t>(count, 1) * sizeof(T), false));
+    *dst = (T *)b.p;
+    c->prob_allocs.push_back(std::move(b));
+    return 0;
+}
+
+template <typename T>
+int prob_upload(qcqpmi_ctx *c, const T **dst, const std::vector<T> &src) {
+    T *p = nullptr;
+    int rc = prob_alloc(c, &p, src.size());
+    if (rc) return rc;
+    if (!src.empty())
+        HIPCHK(c, hipMemcpyAsync(p, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice, c->stream));
+    *dst = p;
+    return 0;
+}
+
+// Launches of the kernels of kernels_impl.h that a unit other than capi.hip needs: enqueued on c->stream, no wait (the
 // caller checks hipGetLastError as after any launch).
 // capi.hip: one workgroup per population of R restarts selects its best (out_idx[2 p], out_key[2 p]: select_best_kernel)
 void launch_select_best(qcqpmi_ctx *c, int64_t pops, const double *f0, const double *maxviol, int64_t R, double tol, int64_t *out_idx,
@@ -188,17 +211,43 @@ void launch_select_best(qcqpmi_ctx *c, int64_t pops, const double *f0, const dou
 void launch_from_tiles(qcqpmi_ctx *c, const double *Xt, int64_t R);
 // capi.hip: the columns idx[2 p] of `pops` populations of R restarts of the resident population -> out [pops][n] (gather_best_x_kernel)
 void launch_gather_best_x(qcqpmi_ctx *c, int64_t pops, int64_t R, const int64_t *idx, double *out);
-
-// capi.hip, for the streamed run of capi_stream.hip: the resident population's buffers for R restarts; the staging buffers of
-// fetch_cd_outputs; the per-restart results of a run -> host (one transfer, one wait) and the status policy on them; the restarts a
-// queue launch works on; the shape rule of the round-4 slot-queue kernel
+// capi.hip: objective and max violation of the resident population into d_f0 / d_mv, every function value into d_F when want_F
+// (eval_kernel, behind the planes GEMM from 8 row blocks x 8 tiles; the dense path's launch_eval_dense where dense_on); timer 0
+int launch_eval(qcqpmi_ctx *c, bool want_F);
+// capi.hip: the resident population's buffers for R restarts
 int pop_reserve(qcqpmi_ctx *c, int64_t R);
+
+// capi_cd.hip, for the streamed run of capi_stream.hip and the dense run of capi_dense.hip: the staging buffers of fetch_cd_outputs;
+// the per-restart results of a run -> host (one transfer, one wait) and the status policy on them; the restarts a queue launch works
+// on; the shape rule of the round-4 slot-queue kernel; the gate of improve_coord_descent on d_mv / d_status1 -> d_flag (gate_kernel:
+// enqueued, no wait)
 int cd_outputs_reserve(qcqpmi_ctx *c, int64_t R);
 int fetch_cd_outputs(qcqpmi_ctx *c, int64_t *sweeps1, int64_t *sweeps2, int64_t *visits2, int64_t *accepted2, uint8_t *ran_phase2,
                      double *f0, double *maxviol, std::vector<int> &st, std::vector<int> &st1);
 int cd_apply_status(qcqpmi_ctx *c, const std::vector<int> &st, const std::vector<int> &st1, double *f0, double *maxviol, int seg_cap);
 void cd_queue_fill_batch(qcqpmi_ctx *c, CdBatch &B, uint64_t seed, uint64_t first_index);
 bool cd_queue_shape_ok(const qcqpmi_ctx *c);
+void launch_gate(qcqpmi_ctx *c, double viol_tol);
+
+// capi_dense.hip, the dense-constraint path (the kernels of cd_dense.h and cd_dense_mw.h).  Does the problem take it; the name of its
+// chain kernel; its evaluation (every function on the matrix cores; with_Ft: the tracked values too) and its coordinate descent
+bool dense_on(const qcqpmi_ctx *c);
+const char *dense_chain_name(const qcqpmi_ctx *c);
+int launch_eval_dense(qcqpmi_ctx *c, bool with_Ft);
+int cd_run_dense(qcqpmi_ctx *c, int phase1, int64_t num_iters, double viol_tol, double tol, uint64_t seed, uint64_t first_index,
+                 int64_t *sweeps1, int64_t *sweeps2, int64_t *visits2, int64_t *accepted2, uint8_t *ran_phase2, double *f0,
+                 double *maxviol);
+// for qcqpmi_set_quad and qcqpmi_finalize (launches on c->stream, no wait): the row-major n x n matrix of function k >= 1 in
+// c->dn_tmp -> its place in the packed array gpack (dense_pack_kernel); function k of a generator -> row-major padded P
+// (dense_gen_rowmajor_kernel); every matrix packed and the vectors of the dense path uploaded (gq, gr, grel: the constraints')
+void launch_dense_pack_staged(qcqpmi_ctx *c, int64_t k, double *gpack);
+void launch_dense_gen_rowmajor(qcqpmi_ctx *c, double *P, int k, uint64_t seed, double scale, double diag_add);
+int dense_build(qcqpmi_ctx *c, const std::vector<double> &gq, const std::vector<double> &gr, const std::vector<int> &grel);
+// ONE packed n16 x n16 matrix (the fragment layout of dp.Apack) times the Rpad columns of the tile-major X, 8 row blocks x 8 tiles per
+// workgroup (dense_products_kernel<mode>): mode 2: x'Mx per group of row blocks into the dense_product_planes(NB) partial planes
+// out[plane][Rpad]; mode 3: out = mu 1' + M X, tile-major
+int dense_product_planes(int NB);
+int launch_dense_product(qcqpmi_ctx *c, int mode, const double *Mpack, const double *mu, const double *X, double *out);
 
 void admm_drop_handle(qcqpmi_ctx *c);      // capi_admm.hip: the rocBLAS handle of qcqpmi_admm_setup
 void comm_drop(qcqpmi_ctx *c);             // capi_comm.hip: the communicator of qcqpmi_comm_init

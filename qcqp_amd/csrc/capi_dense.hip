@@ -1,9 +1,20 @@
-// Host side of the dense-constraint path (cd_dense.h): packing at finalize, MFMA evaluation of all
-// m+1 functions, and the sweep / block loops of coordinate descent.  Included by capi.hip.
+// C ABI of libqcqp_mi.so, the dense-constraint path (cd_dense.h, cd_dense_mw.h; this unit alone compiles their kernels): packing
+// at upload and finalize, MFMA evaluation of all m+1 functions, the sweep / block loops of coordinate descent, and the operators
+// of the relaxation solver on the packed matrices (weighted sum, weighted product, quadratic and linear parts).  The LDS-tiled
+// GEMM of cd_dense.h also multiplies ONE packed matrix with the population for the core (launch_dense_product).
+#include <algorithm>
+#include <cstdlib>
+#include <cstring>
+
+#include "capi_ctx.h"
+#include "cd_dense_mw.h"      // with it cd_dense.h
+
+using namespace qcqpmi;
 
 namespace {
 
-bool dense_on(const qcqpmi_ctx *c) { return !c->sep && c->dn_Gpack && (c->n > 64 || c->dn_force || (c->dbg & 32)); }
+// which chain kernel the dense path dispatches to (four waves per restart unless a thread would hold more than 8 slots)
+bool dense_chain_mw(const qcqpmi_ctx *c) { return c->dense_chain_mode != 1 && mw_geometry((int)c->m + 1).SL <= 8; }
 
 DenseProblem dense_problem(const qcqpmi_ctx *c) {
     DenseProblem D;
@@ -12,6 +23,34 @@ DenseProblem dense_problem(const qcqpmi_ctx *c) {
     D.n = c->n; D.n16 = c->n16; D.NB = (int)(c->n16 / 16); D.KS = (int)(c->n16 / 4); D.m1 = (int)c->m + 1;
     D.m1p = (D.m1 + 63) / 64 * 64;
     return D;
+}
+
+// pinned host memory for downloads that are repeated thousands of times (a 2-D copy into pageable memory is staged row by
+// row by the runtime: 1025 rows of 47 doubles cost 15 ms)
+int pin_reserve(qcqpmi_ctx *c, size_t bytes) {
+    HIPCHK(c, c->h_pin.reserve(c->stream, bytes, false));
+    return 0;
+}
+
+}  // namespace
+
+namespace qcqpmi {
+
+bool dense_on(const qcqpmi_ctx *c) { return !c->sep && c->dn_Gpack && (c->n > 64 || c->dn_force || (c->dbg & 32)); }
+
+const char *dense_chain_name(const qcqpmi_ctx *c) { return dense_chain_mw(c) ? "dense_chain_mw_kernel" : "dense_chain_kernel"; }
+
+// (dense_pack_kernel addresses function k at gP + (k - 1) n n: hand it a base that puts the staging buffer there)
+void launch_dense_pack_staged(qcqpmi_ctx *c, int64_t k, double *gpack) {
+    const int64_t n = c->n, n16 = c->n16, total = n16 * n16;
+    hipLaunchKernelGGL(dense_pack_kernel, dim3((unsigned)((total + 255) / 256), 1), dim3(256), 0, c->stream, (const double *)nullptr,
+                       (const double *)(c->dn_tmp - (k - 1) * n * n), gpack, n, n16, (int)(c->m + 1), (int)k);
+}
+
+void launch_dense_gen_rowmajor(qcqpmi_ctx *c, double *P, int k, uint64_t seed, double scale, double diag_add) {
+    const int64_t n16 = c->n16;
+    hipLaunchKernelGGL(dense_gen_rowmajor_kernel, dim3((unsigned)((n16 * n16 + 255) / 256)), dim3(256), 0, c->stream, P, c->n, n16, k, seed,
+                       scale, diag_add);
 }
 
 // finalize: every matrix into the block-major fragment layout
@@ -43,8 +82,7 @@ int dense_build(qcqpmi_ctx *c, const std::vector<double> &gq, const std::vector<
             std::vector<double> dense((size_t)n * n, 0.0);
             for (size_t e = 0; e < h.cv.size(); e++) dense[(size_t)h.ci[e] * n + h.cj[e]] += h.cv[e];
             HIPCHK(c, hipMemcpyAsync(c->dn_tmp, dense.data(), (size_t)n * n * sizeof(double), hipMemcpyHostToDevice, c->stream));
-            hipLaunchKernelGGL(dense_pack_kernel, dim3(pb, 1), dim3(256), 0, c->stream, (const double *)nullptr,
-                               (const double *)(c->dn_tmp - (k - 1) * n * n), gp, n, n16, (int)m1, (int)k);
+            launch_dense_pack_staged(c, k, gp);
             HIPCHK(c, hipGetLastError());
             HIPCHK(c, spin_sync(c->stream));      // the staging buffer is free again
         }
@@ -75,10 +113,9 @@ int dense_build(qcqpmi_ctx *c, const std::vector<double> &gq, const std::vector<
     return 0;
 }
 
-int ensure_F(qcqpmi_ctx *c) {
-    HIPCHK(c, c->d_F.reserve(c->stream, (size_t)((c->m + 1) * c->Rpad)));
-    return 0;
-}
+}  // namespace qcqpmi
+
+namespace {
 
 // grid.z of the products kernel (K-split of the contraction) when functions x tiles alone do not fill the chip's 512
 // workgroup slots (2 per CU): the split that minimises rounds of workgroups per unit of work, with a small charge per plane
@@ -97,6 +134,29 @@ int dense_zsplit(int m1, int ntiles, int limit) {
     if (const char *e = getenv("QCQPMI_DENSE_ZS")) zs = atoi(e);      // experiments
     zs = std::min(std::min(zs, 7), limit);
     return std::max(zs, 1);
+}
+
+}  // namespace
+
+namespace qcqpmi {
+
+int dense_product_planes(int NB) { return 2 * ((NB + DP_FG - 1) / DP_FG); }
+
+// ONE matrix times the population through the LDS-tiled GEMM (8 row blocks x 8 tiles per workgroup share their operands).
+// mode 2: x'Mx, one partial plane per wave row of a group of row blocks (launch_eval: M = the packed P0; the per-tile MFMA loop of
+// eval_kernel re-reads all of P0 from L2 for every tile); mode 3: OUT = mu 1' + M X (qcqpmi_pop_sdr_sample: x = mu + F xi;
+// qcqpmi_pop_weighted_product: Y = S X with a zero mu).  The kernel reads Gpack, q, n, n16, NB, KS of the problem in these modes.
+int launch_dense_product(qcqpmi_ctx *c, int mode, const double *Mpack, const double *mu, const double *X, double *out) {
+    DenseProdArgs pa;
+    pa.D.Gpack = Mpack; pa.D.q = mu; pa.D.qT = nullptr; pa.D.r = nullptr; pa.D.relop = nullptr;
+    pa.D.n = c->n; pa.D.n16 = c->n16; pa.D.NB = (int)(c->n16 / 16); pa.D.KS = (int)(c->n16 / 4); pa.D.m1 = 1; pa.D.m1p = 64;
+    pa.X = X; pa.ntiles = (int)(c->Rpad / 16); pa.b = 0; pa.zs = 1; pa.G = mode == 3 ? out : nullptr; pa.F = mode == 2 ? out : nullptr;
+    pa.Rpad = c->Rpad; pa.tile_on = nullptr; pa.hole = -1; pa.ch_only = -1; pa.zplane = 0;
+    auto kg = mode == 2 ? dense_products_kernel<2> : dense_products_kernel<3>;
+    HIPCHK(c, hipFuncSetAttribute((const void *)kg, hipFuncAttributeMaxDynamicSharedMemorySize, DP_LDS_BYTES));
+    hipLaunchKernelGGL(kg, dim3((unsigned)((pa.D.NB + DP_FG - 1) / DP_FG), (unsigned)((pa.ntiles + DP_TG - 1) / DP_TG), 1), dim3(256),
+                       DP_LDS_BYTES, c->stream, pa);
+    return 0;
 }
 
 // all function values on the matrix cores, then f0 / max violation per candidate
@@ -123,6 +183,10 @@ int launch_eval_dense(qcqpmi_ctx *c, bool with_Ft) {
     c->evaluated = true;
     return 0;
 }
+
+}  // namespace qcqpmi
+
+namespace {
 
 // quadratic parts x'P_k x + r_k (plane 0 of d_F) and linear parts q_k'x (the plane after the partial planes) of all
 // functions, kept separate: the homogeneous forms of the SDP solver need them apart
@@ -295,8 +359,6 @@ int dense_phase(qcqpmi_ctx *c, int64_t num_iters, double viol_tol, double tol, u
     return 0;
 }
 
-}  // namespace
-
 // debug: stage tick sums of the chain kernel's wave of restart 0 since the profile was enabled ([0..15] phase 1,
 // [16..31] phase 2 of the serial thread / the one-wave kernel's wave, [32..63] the same for thread 0 of the multi-wave
 // kernel; slots: DnProf in cd_dense.h); reading resets them
@@ -335,6 +397,10 @@ int cd_dense_block_step(qcqpmi_ctx *c, int phase, int64_t sweep, int64_t block, 
     return 0;
 }
 
+}  // namespace
+
+namespace qcqpmi {
+
 int cd_run_dense(qcqpmi_ctx *c, int phase1, int64_t num_iters, double viol_tol, double tol, uint64_t seed,
                  uint64_t first_index, int64_t *sweeps1, int64_t *sweeps2, int64_t *visits2, int64_t *accepted2,
                  uint8_t *ran_phase2, double *f0, double *maxviol) {
@@ -349,8 +415,7 @@ int cd_run_dense(qcqpmi_ctx *c, int phase1, int64_t num_iters, double viol_tol, 
         if ((rc = dense_phase<1>(c, num_iters, viol_tol, tol, seed, first_index))) return rc;
     }
     if ((rc = launch_eval_dense(c, true))) return rc;   // fresh f_k(x): the slack of phase 2 (qcqp.py:157,189)
-    hipLaunchKernelGGL(gate_kernel, dim3((unsigned)((c->Rpad + 255) / 256)), dim3(256), 0, c->stream, c->d_mv,
-                       c->d_status1, c->d_flag, c->R, c->Rpad, viol_tol);
+    launch_gate(c, viol_tol);
     HIPCHK(c, hipGetLastError());
     if (ran_phase2) HIPCHK(c, hipMemcpyAsync(ran_phase2, c->d_flag, (size_t)c->R, hipMemcpyDeviceToHost, c->stream));
     if ((rc = dense_phase<2>(c, num_iters, viol_tol, tol, seed, first_index))) return rc;
@@ -364,3 +429,138 @@ int cd_run_dense(qcqpmi_ctx *c, int phase1, int64_t num_iters, double viol_tol, 
     if ((rc = cd_apply_status(c, st, st1, f0, maxviol, DN_SC))) return rc;
     return 0;
 }
+
+}  // namespace qcqpmi
+
+// ============================================================================================
+
+extern "C" {
+
+int qcqpmi_set_quad_generated(qcqpmi_ctx *c, int64_t k, uint64_t seed, double scale, double qscale,
+                              double diag_add, double r, int relop) {
+    if (!c) return QCQPMI_EINVAL;
+    if (c->finalized) return fail(c, QCQPMI_ESTATE, "set_quad_generated after finalize");
+    if (k < 0 || k > c->m) return fail(c, QCQPMI_EINVAL, "set_quad_generated: bad k");
+    if ((k == 0) != (relop == 0) || relop < 0 || relop > 2)
+        return fail(c, QCQPMI_EINVAL, "set_quad_generated: relop %d invalid for function %lld", relop, (long long)k);
+    HostQuad &h = c->quads[(size_t)k];
+    h = HostQuad();
+    h.gen = true; h.gseed = seed; h.gscale = scale; h.gqscale = qscale; h.gdiag = diag_add;
+    h.r = r; h.relop = relop; h.set = true;
+    // the linear term comes back to the host (n values): the generic finalize code reads it there
+    HIPCHK(c, hipSetDevice(c->device));
+    DevBuf<double> dq;
+    HIPCHK(c, dq.reserve(c->stream, (size_t)c->n, false));
+    hipLaunchKernelGGL(dense_gen_q_kernel, dim3((unsigned)((c->n + 255) / 256)), dim3(256), 0, c->stream, dq.p, c->n, (int)k, seed, qscale);
+    h.q.resize((size_t)c->n);
+    HIPCHK(c, hipMemcpyAsync(h.q.data(), dq.p, (size_t)c->n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, spin_sync(c->stream));
+    return 0;
+}
+
+int qcqpmi_pop_weighted_product(qcqpmi_ctx *c, const double *w, double *Y) {
+    int rc = check_ready(c, true);
+    if (rc) return rc;
+    if (!w || !Y) return fail(c, QCQPMI_EINVAL, "pop_weighted_product: w / Y missing");
+    HIPCHK(c, hipSetDevice(c->device));
+    DenseProblem D = dense_problem(c);
+    if (!c->dn_Gpack) {
+        // separable constraints: only the objective has a matrix (the packed P0 of the separable path: the same fragment
+        // layout with one function); the weights of the constraints are the caller's business (elementwise operators)
+        D.Gpack = c->dp.Apack; D.m1 = 1; D.m1p = 64; D.q = nullptr; D.qT = nullptr; D.r = nullptr; D.relop = nullptr;
+    }
+    const int64_t n16 = c->n16;
+    HIPCHK(c, c->d_ww.reserve(c->stream, (size_t)D.m1, false));
+    HIPCHK(c, c->d_wS.reserve(c->stream, (size_t)n16 * n16, false));
+    HIPCHK(c, c->d_wz.reserve(c->stream, (size_t)n16));   // zero offset vector of the affine map
+    HIPCHK(c, c->d_wY.reserve(c->stream, (size_t)c->Rpad * n16, false));
+    double *dw = c->d_ww, *dS = c->d_wS, *dY = c->d_wY, *dz = c->d_wz;
+    const int64_t total = c->R * c->n;
+    if ((rc = pin_reserve(c, (size_t)total * sizeof(double) + (size_t)D.m1 * sizeof(double)))) return rc;
+    char *hw = c->h_pin + (size_t)total * sizeof(double);       // the weights go up through pinned memory too
+    memcpy(hw, w, (size_t)D.m1 * sizeof(double));
+    HIPCHK(c, hipMemcpyAsync(dw, hw, (size_t)D.m1 * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(dense_wsum_pack_kernel, dim3((unsigned)((n16 * n16 + 255) / 256)), dim3(256), 0, c->stream, D, (const double *)dw, dS);
+    if ((rc = launch_dense_product(c, 3, dS, dz, c->X, dY))) return rc;
+    launch_from_tiles(c, dY, c->R);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(c->h_pin, c->d_stage, (size_t)total * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, spin_sync(c->stream));
+    memcpy(Y, c->h_pin, (size_t)total * sizeof(double));
+    return 0;
+}
+
+int qcqpmi_weighted_matrix(qcqpmi_ctx *c, const double *w, double *S) {
+    int rc = check_ready(c, false);
+    if (rc) return rc;
+    if (!w || !S) return fail(c, QCQPMI_EINVAL, "weighted_matrix: w / S missing");
+    if (!c->dn_Gpack) return fail(c, QCQPMI_EUNSUPPORTED, "weighted_matrix needs the packed dense matrices");
+    HIPCHK(c, hipSetDevice(c->device));
+    const DenseProblem D = dense_problem(c);
+    const int64_t n = c->n, n16 = c->n16;
+    DevBuf<double> dw, dS, dU;
+    HIPCHK(c, dw.reserve(c->stream, (size_t)D.m1, false));
+    HIPCHK(c, dS.reserve(c->stream, (size_t)n16 * n16, false));
+    HIPCHK(c, dU.reserve(c->stream, (size_t)n * n, false));
+    HIPCHK(c, hipMemcpyAsync(dw.p, w, (size_t)D.m1 * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(dense_wsum_pack_kernel, dim3((unsigned)((n16 * n16 + 255) / 256)), dim3(256), 0, c->stream, D, (const double *)dw.p, dS.p);
+    hipLaunchKernelGGL(dense_unpack_kernel, dim3((unsigned)((n * n + 255) / 256)), dim3(256), 0, c->stream, (const double *)dS.p, dU.p, n, (int)(n16 / 4));
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(S, dU.p, (size_t)n * n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, spin_sync(c->stream));
+    return 0;
+}
+
+int qcqpmi_pop_eval_parts(qcqpmi_ctx *c, double *quad, double *lin) {
+    int rc = check_ready(c, true);
+    if (rc) return rc;
+    if (!quad || !lin) return fail(c, QCQPMI_EINVAL, "pop_eval_parts: outputs missing");
+    if (!c->dn_Gpack) return fail(c, QCQPMI_EUNSUPPORTED, "pop_eval_parts needs the packed dense matrices (constraints that couple coordinates)");
+    HIPCHK(c, hipSetDevice(c->device));
+    if ((rc = eval_parts_dense(c))) return rc;
+    const int64_t m1 = c->m + 1;
+    const double *dlin = c->d_F + (int64_t)c->eval_zs * m1 * c->Rpad;
+    // the two planes ([m1][Rpad], contiguous) through pinned memory in one copy each, the padding columns dropped on the host
+    const size_t plane = (size_t)m1 * c->Rpad * sizeof(double);
+    if ((rc = pin_reserve(c, 2 * plane))) return rc;
+    HIPCHK(c, hipMemcpyAsync(c->h_pin, c->d_F, plane, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->h_pin + plane, dlin, plane, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, spin_sync(c->stream));
+    const double *hq = (const double *)c->h_pin.p, *hl = (const double *)(c->h_pin + plane);
+    for (int64_t k = 0; k < m1; k++) {
+        memcpy(quad + k * c->R, hq + k * c->Rpad, (size_t)c->R * sizeof(double));
+        memcpy(lin + k * c->R, hl + k * c->Rpad, (size_t)c->R * sizeof(double));
+    }
+    c->evaluated = false;    // plane 0 no longer holds the full function values
+    return 0;
+}
+
+int qcqpmi_cd_dense_block_step(qcqpmi_ctx *c, int phase, int64_t sweep, int64_t block, int coord_lo, int coord_hi, double viol_tol,
+                               double tol, uint64_t seed, uint64_t first_index, const double *slack) {
+    int rc = check_ready(c, true);
+    if (rc) return rc;
+    if (!dense_on(c)) return fail(c, QCQPMI_EUNSUPPORTED, "cd_dense_block_step: the problem does not take the dense-constraint path");
+    c->last_cd2_kernel = dense_chain_name(c);
+    return cd_dense_block_step(c, phase, sweep, block, coord_lo, coord_hi, viol_tol, tol, seed, first_index, slack);
+}
+
+int qcqpmi_dense_chain_geometry(int64_t m, int *out4) {
+    if (m < 0 || m > (1 << 24) || !out4) return QCQPMI_EINVAL;
+    const MwGeom g = mw_geometry((int)m + 1);
+    out4[0] = g.SL; out4[1] = g.Tc; out4[2] = g.ts; out4[3] = g.T;
+    return 0;
+}
+
+int qcqpmi_dense_chain_mode(qcqpmi_ctx *c, int mode) {
+    if (!c || mode < 0 || mode > 1) return QCQPMI_EINVAL;
+    c->dense_chain_mode = mode;
+    return 0;
+}
+
+int qcqpmi_debug_dense_profile(qcqpmi_ctx *c, int64_t *out64) {
+    if (!c || !out64) return QCQPMI_EINVAL;
+    HIPCHK(c, hipSetDevice(c->device));
+    return dense_profile_read(c, out64);
+}
+
+}  // extern "C"

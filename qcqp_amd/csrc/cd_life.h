@@ -1,4 +1,4 @@
-// Lifecycle kernel, second generation (round 5): interface between capi.hip and cd_life.hip (own translation unit).
+// Lifecycle kernel, second generation (round 5): interface between capi_stream.hip and cd_life.hip (own translation unit).
 //
 // improve_coord_descent (qcqp.py:181-192) for a QUEUE of restarts -- suggest(RANDOM) (qcqp.py:381-382) or resident start
 // points, phase 1 (qcqp.py:101-149), the gate (qcqp.py:189), phase 2 (qcqp.py:152-178), objective and max violation of the

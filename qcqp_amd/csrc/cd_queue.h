@@ -1,5 +1,5 @@
-// Coordinate descent phase 2 (qcqp.py:152-178) with RESTART-LEVEL scheduling (round 3): interface between capi.hip and
-// cd_queue.hip (own translation unit).
+// Coordinate descent phase 2 (qcqp.py:152-178) with RESTART-LEVEL scheduling (round 3): interface between its callers
+// (capi_cd.hip: launch_cd; capi_stream.hip: the lifecycle mode) and cd_queue.hip (own translation unit).
 //
 // cd_phase2_q_kernel binds 16 restarts to a workgroup for the whole launch: the workgroup runs until its slowest restart
 // has converged (lanes of converged restarts keep multiplying), and the launch until the slowest workgroup has.  Here a

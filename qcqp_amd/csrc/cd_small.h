@@ -1,4 +1,4 @@
-// Small-problem batch kernel: interface between capi.hip (its driver: capi_small.inc) and cd_small.hip (own translation unit).
+// Small-problem batch kernel: interface between its driver (capi_small.hip) and cd_small.hip (own translation unit).
 //
 // improve_coord_descent (qcqp.py:181-192) for B problems of n <= 64 variables that share ONE set of separable constraint lists
 // and differ in their objective (P0_b, q0_b, r0_b) -- a frame of MIMO detection problems: thousands of Boolean least squares

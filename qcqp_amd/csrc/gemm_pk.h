@@ -15,7 +15,7 @@
 // The contraction can be split over grid.z into `zs` partial planes C + z * plane (summed by the consumer in a
 // fixed order: deterministic) for products with few outputs and a long K (the ADMM consensus sum).
 //
-// Used by the ADMM improve path (capi_admm.inc): ZQ = W^T Z, S = W D, z = Minv rhs, Y = P0 z.
+// Used by the ADMM improve path (capi_admm.hip): ZQ = W^T Z, S = W D, z = Minv rhs, Y = P0 z.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -1,4 +1,4 @@
-// Small-problem SDR batch kernel: interface between capi.hip and sdr_small.hip (own translation unit).
+// Small-problem SDR batch kernel: interface between its driver (capi_small.hip) and sdr_small.hip (own translation unit).
 //
 // suggest(SDR) (qcqp.py:72-97 + 394-396) for B problems of n <= 64 variables that share the constraints x_i^2 = d_i (the unit-diagonal
 // family of sdr.unit_diagonal_family) and differ in their objective (P0_b, q0_b, r0_b) -- the batch of cd_small.h -- inside ONE

@@ -1,4 +1,4 @@
-// Small-problem batch: what the batch kernels (cd_small.hip, admm_small.hip, sdr_small.hip) and their drivers (capi_small.inc) share.
+// Small-problem batch: what the batch kernels (cd_small.hip, admm_small.hip, sdr_small.hip) and their drivers (capi_small.hip) share.
 //
 // The ticket frame.  A persistent workgroup draws a ticket -- a problem b and a chunk [r_lo, r_hi) of its R restarts -- from a global
 // counter (an ordinary atomic add), stages the problem's LDS image once

@@ -44,7 +44,7 @@ def geometry(L, m):
 
 
 def template_of(SL):
-    """The instantiation dense_phase launches for SL slots (csrc/capi_dense.inc)."""
+    """The instantiation dense_phase launches for SL slots (csrc/capi_dense.hip)."""
     return 1 if SL <= 1 else 2 if SL <= 2 else 4 if SL <= 4 else 8
 
 

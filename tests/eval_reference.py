@@ -55,7 +55,7 @@ def K_coo(nnz, n):
 
 # ------------------------------------------------------------------------------------------- dense_zsplit, restated
 def dense_zsplit_expected(m1, ntiles, NB):
-    """csrc/capi_dense.inc:dense_zsplit without its environment override: grid.z of dense_products_kernel<0> / <1>."""
+    """csrc/capi_dense.hip:dense_zsplit without its environment override: grid.z of dense_products_kernel<0> / <1>."""
     wg = ((m1 + 7) // 8) * ((ntiles + 7) // 8)
     zs = 1
     if wg < 512:

@@ -1,4 +1,4 @@
-"""qcqpmi_cd_run on the resident population of a separable problem over the whole dispatch domain of launch_cd (csrc/capi.hip):
+"""qcqpmi_cd_run on the resident population of a separable problem over the whole dispatch domain of launch_cd (csrc/capi_cd.hip):
 every case uploads or generates R starts, calls Engine.cd_run, runs the fast separable oracle (Problem.improve_cd_sep, keyed
 generator, pinned to the restatement by tests/test_oracle_golden.py and tests/test_cd_run_domain_cpu.py) on the same starts and
 checks EVERY restart with life_oracle.check_restart: point 1e-9 relative, phase-1 sweeps, ran_phase2, phase-2 visits and accepted
@@ -50,7 +50,7 @@ pytestmark = pytest.mark.gpu
 LINE = re.compile(r'launch_cd: (cd_phase\w+ [^\n]*)')
 COUNTERS = ('sweeps1', 'sweeps2', 'visits2', 'accepted2', 'ran_phase2', 'status1', 'status2')
 
-# ---- launch_cd's thresholds (csrc/capi.hip, csrc/cd_roles.h), in doubles unless said
+# ---- launch_cd's thresholds (csrc/capi_cd.hip, csrc/cd_roles.h), in doubles unless said
 LDS_BYTES = 160 * 1024
 RQ_NSIMD, RQ_MAXU, RQ_CSMAX = 3, 20, 6
 RQ_LDS_COMMON = 2 * RQ_NSIMD * 256 + 256 + 2 * 256 + 2 * 16 + 2 * 16 + 2 * 16 + 16 + 4 * 16 + 8 + 8 + 8

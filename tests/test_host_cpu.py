@@ -825,7 +825,7 @@ def test_build_units_cover_every_source_file():
         deps = _build.unit_sources(unit)
         assert os.path.join(_build.SRC, unit) in deps
     assert os.path.join(_build.SRC, 'cd_phase1_sep.h') in _build.unit_sources('cd_queue.hip')
-    assert os.path.join(_build.SRC, 'cd_phase1_sep.h') in _build.unit_sources('capi.hip')
+    assert os.path.join(_build.SRC, 'cd_phase1_sep.h') in _build.unit_sources('capi_cd.hip')
     assert os.path.join(_build.SRC, 'cd_phase1_sep.h') in _build.unit_sources('cd_life.hip')
     # staleness: an object older than one of its sources is rebuilt
     obj = _build._obj('cd_life.hip')
@@ -853,7 +853,11 @@ def test_build_units_cover_every_source_file():
             finally:
                 os.utime(path, (st.st_atime, st.st_mtime))
         # the streamed path likewise: its unit alone for the unit file; the units that read the shape rules for their header
-        for name, units in (('capi_stream.hip', {'capi_stream.hip'}), ('cd_life_plan.h', {'capi_stream.hip', 'cd_life.hip', 'cd_queue.hip', 'capi.hip'})):
+        # (capi_cd.hip through cd_phase2_q.h's cd_roles.h; the core no longer).  The dense path, coordinate descent on the
+        # resident population and the core: each its own unit, for the unit file and for a kernel header only it includes
+        for name, units in (('capi_stream.hip', {'capi_stream.hip'}), ('cd_life_plan.h', {'capi_stream.hip', 'cd_life.hip', 'cd_queue.hip', 'capi_cd.hip'}),
+                            ('capi_dense.hip', {'capi_dense.hip'}), ('cd_dense.h', {'capi_dense.hip'}),
+                            ('capi_cd.hip', {'capi_cd.hip'}), ('cd_phase2_rs.h', {'capi_cd.hip'}), ('capi.hip', {'capi.hip'})):
             path = os.path.join(_build.SRC, name)
             st = os.stat(path)
             try:
@@ -888,16 +892,40 @@ def test_every_kernel_is_compiled_into_one_unit():
 def test_only_the_owning_unit_reaches_a_kernel_header():
     """The seams of the C ABI's host side: capi_small.hip, capi_comm.hip and capi_stream.hip are host code (nothing they are built from
     defines a kernel), rccl/rccl.h is included by capi_comm.hip alone, and the kernels of admm.h and gemm_pk.h are compiled into
-    capi_admm.hip alone."""
+    capi_admm.hip alone, those of the dense path into capi_dense.hip alone, the phase-2 families, phase 1 and the gate into
+    capi_cd.hip alone -- the core (capi.hip) is built from none of them."""
     from qcqp_amd import _build
     for unit in ('capi_small.hip', 'capi_comm.hip', 'capi_stream.hip'):
         with_kernel = [os.path.basename(p) for p in _build.unit_sources(unit) if '__global__' in open(p).read()]
         assert not with_kernel, (unit, with_kernel)
     text = {f: open(os.path.join(_build.SRC, f)).read() for f in os.listdir(_build.SRC) if f.endswith(('.hip', '.h', '.inc'))}
     assert sorted(f for f, t in text.items() if re.search(r'^\s*#\s*include\s*<rccl/', t, re.M)) == ['capi_comm.hip']
-    for hdr in ('admm.h', 'gemm_pk.h'):
+    owners = {'admm.h': 'capi_admm.hip', 'gemm_pk.h': 'capi_admm.hip', 'cd_dense.h': 'capi_dense.hip', 'cd_dense_mw.h': 'capi_dense.hip',
+              'cd_phase2.h': 'capi_cd.hip', 'cd_phase2_rs.h': 'capi_cd.hip', 'cd_phase2_q.h': 'capi_cd.hip', 'cd_kernels.h': 'capi_cd.hip'}
+    for hdr, owner in owners.items():
+        assert os.path.exists(os.path.join(_build.SRC, hdr)), hdr
         reach = sorted(u for u in _build.TRANSLATION_UNITS if os.path.join(_build.SRC, hdr) in _build.unit_sources(u))
-        assert reach == ['capi_admm.hip'], (hdr, reach)
+        assert reach == [owner], (hdr, reach)
+    core = {os.path.basename(p) for p in _build.unit_sources('capi.hip')}
+    assert not core & {h for h, o in owners.items() if o in ('capi_dense.hip', 'capi_cd.hip')}, sorted(core)
+
+
+def test_the_library_exports_exactly_the_declared_entry_points():
+    """The dynamic symbols qcqpmi_* that libqcqp_mi.so defines are the functions include/qcqp_mi.h declares, no more and no less.
+    The entry points are spread over eight units: one that moved without its extern "C" would be exported under a mangled name and
+    surface only as a missing symbol at the first ctypes lookup of it."""
+    import shutil
+    from qcqp_amd import _build
+    if not shutil.which('nm') or not os.path.exists(_build.LIB):
+        pytest.skip('no nm / no library of an in-tree build')
+    header = open(_build.HEADER).read()
+    header = re.sub(r'/\*.*?\*/', ' ', header, flags=re.S)
+    header = re.sub(r'//[^\n]*', ' ', header)
+    declared = set(re.findall(r'\b(qcqpmi_\w+)\s*\(', header))
+    assert len(declared) > 50, sorted(declared)
+    out = subprocess.run(['nm', '-D', '--defined-only', _build.LIB], stdout=subprocess.PIPE, check=True).stdout.decode()
+    exported = {line.split()[-1] for line in out.splitlines() if line.split() and line.split()[-1].startswith('qcqpmi_')}
+    assert exported == declared, (sorted(declared - exported), sorted(exported - declared))
 
 
 def test_the_streamed_launch_is_decided_in_one_place():
@@ -942,10 +970,11 @@ def test_errors_without_a_context_share_one_slot():
 def test_every_header_compiles_on_its_own(tmp_path):
     """A header that needs something its includer happens to provide forces every new includer to fake it (cd_phase2.h once named
     a function of the file that included it: three units carried stand-in definitions).  Each csrc/*.h is compiled alone, device
-    side, syntax only, with the build's flags; capi_dense.inc is a fragment of capi.hip by design (the dense path and the core call
-    each other)."""
+    side, syntax only, with the build's flags.  No exception: csrc/ holds units and headers, no .inc fragment that only compiles in
+    the middle of another file."""
     from concurrent.futures import ThreadPoolExecutor
     from qcqp_amd import _build
+    assert not [f for f in os.listdir(_build.SRC) if f.endswith('.inc')]
     hipcc = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
     if not os.path.exists(hipcc):
         pytest.skip('no hipcc')
