@@ -444,6 +444,19 @@ int qcqpmi_sdr_small_batch(qcqpmi_ctx *ctx, int64_t B, const double *P0s, const 
 int qcqpmi_sdr_small_batch_pc(qcqpmi_ctx *ctx, int64_t B, const double *P0s, const double *q0s, const double *r0s, const double *ds,
                               int64_t S, int max_sweeps, double tol, uint64_t seed, uint64_t seed_stride, uint64_t first_index,
                               const double *V0s, double *V, double *primal, double *y, int64_t *sweeps, double *X);
+/* THE SAME TWO CALLS FOR 1 <= n <= 128 (added within ABI 6: two new symbols, nothing else changes).  The arguments, outputs and
+ * refusals are those of qcqpmi_sdr_small_batch and qcqpmi_sdr_small_batch_pc.  For n <= 64 they make exactly that launch: bit for bit
+ * the same results.  For 65 <= n <= 128 the wide kernel runs (sdr_small_kernel<true>, csrc/sdr_small.h): still one wavefront per
+ * problem, rank 64, the same start, passes, stop rule and sums in the same order, with C_b stored as its lower triangle (N (N + 1) / 2
+ * doubles: the LDS image is 134 672 bytes at n = 128, one wavefront per CU) and two coordinates per lane in the samples (lane l forms
+ * x_l and x_{l+64}).  V0s and V stay [B][N][64].  The bit-for-bit statements above hold as they stand.  QCQPMI_EUNSUPPORTED: n > 128,
+ * constraints outside the family.  The old symbols refuse n > 64 as before. */
+int qcqpmi_sdr_batch(qcqpmi_ctx *ctx, int64_t B, const double *P0s, const double *q0s, const double *r0s, int64_t S, int max_sweeps,
+                     double tol, uint64_t seed, uint64_t seed_stride, uint64_t first_index, const double *V0s, double *V,
+                     double *primal, double *y, int64_t *sweeps, double *X);
+int qcqpmi_sdr_batch_pc(qcqpmi_ctx *ctx, int64_t B, const double *P0s, const double *q0s, const double *r0s, const double *ds,
+                        int64_t S, int max_sweeps, double tol, uint64_t seed, uint64_t seed_stride, uint64_t first_index,
+                        const double *V0s, double *V, double *primal, double *y, int64_t *sweeps, double *X);
 /* IMPROVE(ADMM) FOR MANY SMALL PROBLEMS IN ONE LAUNCH (added within ABI 6: a new symbol, nothing else changes).  The batch of
  * qcqpmi_cd_small_batch_run -- B objectives P0s [B][n][n] (each symmetric), q0s [B][n], r0s [B] over this context's separable
  * constraint lists (up to four per coordinate, m >= 1 in all), 1 <= n <= 64 -- through improve_admm (qcqp.py:254-285): phase 1, x1 =

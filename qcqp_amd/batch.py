@@ -8,12 +8,14 @@ wide kernels, two coordinates per lane).  improve(ADMM) runs the reference's con
 (n <= 64: ``Engine.admm_small_batch_run``, qcqpmi_admm_small_batch_run; 64 < n <= 128, asked for with wide=True:
 ``Engine.admm_batch_run``, qcqpmi_admm_batch_run, wide kernels again), with rho per problem by the reference's rule and
 (2 (P0_b + rho_b m I))^-1 from one batched host inverse.  suggest(SDR) -- for constraints x_i^2 == d_i -- solves the
-semidefinite relaxation of all B problems and draws their samples in one launch as well (``Engine.sdr_small_batch``,
-qcqpmi_sdr_small_batch) and publishes the certified bounds in ``sdr_bound``; improve() then starts from the samples.  Problem b's results are those of
+semidefinite relaxation of all B problems and draws their samples in one launch as well (n <= 64: ``Engine.sdr_small_batch``,
+qcqpmi_sdr_small_batch; 64 < n <= 128, asked for with wide=True: ``Engine.sdr_batch``, qcqpmi_sdr_batch, the wide kernel with C_b
+packed in LDS) and publishes the certified bounds in ``sdr_bound``; improve() then starts from the samples.  Problem b's results are those of
 ``QCQP(Problem(funcs_b))`` with suggest(RANDOM, num_samples=R, seed=seed + b seed_stride, first_index=...) followed by
 improve(COORD_DESCENT, ..., seed=seed + b seed_stride, first_index=...).  Problems whose constraints differ in their COEFFICIENTS
 only (boxes with bounds per instance, x_i^2 == d_{b,i}: problems.per_problem_constraints_batch) run through the same launches with
-per-problem coefficients.  suggest(SDR) is defined for n <= 64 (the relaxation's LDS image does not fit beyond).
+per-problem coefficients.  suggest(SDR) takes n <= 64 by default and n <= 128 with wide=True (the LDS image of the relaxation fits a
+CU up to n = 128 once C_b is stored as its lower triangle).
 
     from qcqp_amd.batch import QCQPBatch
     from qcqp_amd import problems, settings as s
@@ -77,7 +79,7 @@ def _structure(funcs):
     return None if any(e is None for e in out) else out
 
 
-MAX_N = 128          # qcqpmi_cd_batch_run, qcqpmi_admm_batch_run: two coordinates per lane
+MAX_N = 128          # qcqpmi_cd_batch_run, qcqpmi_admm_batch_run, qcqpmi_sdr_batch: two coordinates per lane
 MAX_N_SMALL = 64     # qcqpmi_cd_small_batch_run, qcqpmi_sdr_small_batch, qcqpmi_admm_small_batch_run: one coordinate per lane
 
 
@@ -107,7 +109,7 @@ def admm_minvs(P0s, rhos, m):
 
 class QCQPBatch(object):
     """``funcs_list`` = [funcs_0, ..., funcs_{B-1}], every funcs_b = [(P, q, r, relop), ...] in minimise form with the objective
-    first (what qcqp_amd.problems returns).  All problems must have the same n (<= 128; suggest(SDR): <= 64) and constraints of the same STRUCTURE: the
+    first (what qcqp_amd.problems returns).  All problems must have the same n (<= 128; suggest(SDR) and improve(ADMM) past 64: with wide=True) and constraints of the same STRUCTURE: the
     same number of them, and constraint k with the same relop on the same coordinate in every problem.  Their coefficients may
     differ from problem to problem (separable constraints only): ``cons`` (B, m, 3) then holds (p, q, r) of every constraint and the
     launches are qcqpmi_cd_small_batch_run_pc / qcqpmi_sdr_small_batch_pc; with equal coefficients ``cons`` is None and the calls are
@@ -159,21 +161,23 @@ class QCQPBatch(object):
         self.best_index = None
         self.last_stats = None
 
-    def suggest(self, method=s.RANDOM, num_samples=1, seed=0, first_index=0, seed_stride=1, max_sweeps=5000, tol=1e-11):
+    def suggest(self, method=s.RANDOM, num_samples=1, seed=0, first_index=0, seed_stride=1, max_sweeps=5000, tol=1e-11, wide=False):
         """RANDOM: R = num_samples random starts per problem: problem b draws the keyed normals (seed + b seed_stride, first_index + r).
         The points are drawn inside the launch of improve(); nothing runs here.
         SDR (constraints x_i^2 == d_i): one launch solves the relaxation of every problem (mixing method, max_sweeps / tol) and
         draws R samples of N(mu_b, Sigma_b) from the keyed normals (seed + b seed_stride, first_index + r); every solve is certified
         (sdr.certify_batch, which logs the warning for problems that are not certified).  Sets .sdr_bound (B,) -- the rigorous lower bound, NaN where the problem is not certified -- and
-        .sdr_info (primal, sweeps, lambda_min, converged); the samples are the starts of improve()."""
+        .sdr_info (primal, sweeps, lambda_min, converged); the samples are the starts of improve().
+        wide=True admits 65 <= n <= 128 to SDR (``Engine.sdr_batch``: the wide kernel, C_b packed, two coordinates per lane in the
+        samples); n <= 64 runs as without it.  The default refuses n > 64 as before.  RANDOM ignores it."""
         if method not in (s.RANDOM, s.SDR):
             raise Exception("QCQPBatch.suggest is defined for the RANDOM and SDR methods")
         if int(num_samples) < 1:
             raise Exception("QCQPBatch.suggest: num_samples must be positive")
         if method == s.SDR:
-            if self.n > MAX_N_SMALL:      # before any launch: (65 N + N^2 + 64) doubles of LDS, N = n + 1, do not fit a CU past N = 114
-                raise Exception("QCQPBatch.suggest(SDR) is defined for n <= %d (n = %d): the batched relaxation keeps V_b and C_b in "
-                                "LDS; use suggest(RANDOM), or QCQP per problem" % (MAX_N_SMALL, self.n))
+            if self.n > MAX_N_SMALL and not wide:      # before any launch
+                raise Exception("QCQPBatch.suggest(SDR) is defined for n <= %d (n = %d) unless wide=True is given (n <= %d: the wide "
+                                "kernel, C_b packed in LDS); or use suggest(RANDOM), or QCQP per problem" % (MAX_N_SMALL, self.n, MAX_N))
             d = _sdr.unit_diagonal_family(self.form)
             if d is None:
                 raise Exception("QCQPBatch.suggest(SDR) is defined for constraints x_i^2 == d_i (one per coordinate)")
@@ -188,8 +192,9 @@ class QCQPBatch(object):
                     raise Exception("QCQPBatch.suggest(SDR) is defined for constraints x_i^2 == d_i (one per coordinate): problem %d is "
                                     "not of the family" % int(np.nonzero(bad)[0][0]))
                 d = ds
-            out = self.engine.sdr_small_batch(self.P0s, self.q0s, self.r0s, int(num_samples), max_sweeps=max_sweeps, tol=tol, seed=seed,
-                                              seed_stride=seed_stride, first_index=first_index, want_V=False, ds=ds)
+            run = self.engine.sdr_small_batch if self.n <= MAX_N_SMALL else self.engine.sdr_batch
+            out = run(self.P0s, self.q0s, self.r0s, int(num_samples), max_sweeps=max_sweeps, tol=tol, seed=seed, seed_stride=seed_stride,
+                      first_index=first_index, want_V=False, ds=ds)
             cert = _sdr.certify_batch(_sdr.lifted_cost_batch(self.P0s, self.q0s, self.r0s, d), out['y'], out['sweeps'], max_sweeps)
             self.sdr_bound = np.where(cert['converged'], cert['bound'], np.nan)
             self.sdr_info = dict(primal=out['primal'], sweeps=out['sweeps'], lambda_min=cert['lambda_min'], converged=cert['converged'])

@@ -194,13 +194,15 @@ int cd_small_batch(qcqpmi_ctx *c, int64_t maxn, bool per_problem, const double *
 }
 
 // ---- suggest(SDR) for problems of the unit-diagonal family that share the context's constraints x_i^2 == d_i: the relaxation (mixing
-// method), its multipliers and S samples per problem.  ds == nullptr: the context's d; else [B][n], per_problem set (the _pc symbol)
-int sdr_small_batch(qcqpmi_ctx *c, bool per_problem, const double *ds, int64_t B, const double *P0s, const double *q0s, const double *r0s,
+// method), its multipliers and S samples per problem.  ds == nullptr: the context's d; else [B][n], per_problem set (the _pc symbol).
+// maxn: SDR_SMALL_MAXN, or SDR_WIDE_MAXN for qcqpmi_sdr_batch[_pc], whose problems of more than SDR_SMALL_MAXN variables run the wide kernel
+int sdr_small_batch(qcqpmi_ctx *c, int64_t maxn, bool per_problem, const double *ds, int64_t B, const double *P0s, const double *q0s, const double *r0s,
                     int64_t S, int max_sweeps, double tol, uint64_t seed, uint64_t seed_stride, uint64_t first_index, const double *V0s,
                     double *V, double *primal, double *y, int64_t *sweeps, double *X) {
     int rc = check_ready(c, false);
     if (rc) return rc;
-    if (c->n > SDR_SMALL_MAXN) return fail(c, QCQPMI_EUNSUPPORTED, "sdr_small_batch: n = %lld, the small-problem kernel takes n <= %d", (long long)c->n, SDR_SMALL_MAXN);
+    if (c->n > maxn) return fail(c, QCQPMI_EUNSUPPORTED, "sdr_small_batch: n = %lld, the small-problem kernel takes n <= %lld (%s)", (long long)c->n, (long long)maxn,
+                                 maxn > SDR_SMALL_MAXN ? "C_b packed, two coordinates per lane in the samples" : "the full C_b in LDS");
     if (!c->sep || c->unit_d.empty()) return fail(c, QCQPMI_EUNSUPPORTED, "sdr_small_batch: the constraints are not of the unit-diagonal family (every coordinate exactly one constraint p x_i^2 + r == 0 with -r / p > 0)");
     if (B < 1 || S < 0 || max_sweeps < 0 || !(tol >= 0.0) || !P0s || !q0s || !r0s)
         return fail(c, QCQPMI_EINVAL, "sdr_small_batch: bad B / S / max_sweeps / tol, or a missing input array");
@@ -385,14 +387,27 @@ int qcqpmi_admm_batch_run(qcqpmi_ctx *c, int64_t B, const double *P0s, const dou
 int qcqpmi_sdr_small_batch(qcqpmi_ctx *c, int64_t B, const double *P0s, const double *q0s, const double *r0s, int64_t S, int max_sweeps,
                            double tol, uint64_t seed, uint64_t seed_stride, uint64_t first_index, const double *V0s, double *V,
                            double *primal, double *y, int64_t *sweeps, double *X) {
-    return sdr_small_batch(c, false, nullptr, B, P0s, q0s, r0s, S, max_sweeps, tol, seed, seed_stride, first_index, V0s, V, primal, y, sweeps, X);
+    return sdr_small_batch(c, SDR_SMALL_MAXN, false, nullptr, B, P0s, q0s, r0s, S, max_sweeps, tol, seed, seed_stride, first_index, V0s, V, primal, y, sweeps, X);
 }
 
 // ---- the same launch with PER-PROBLEM d: ds [B][n] replaces the context's d problem by problem (the context must still be of the family)
 int qcqpmi_sdr_small_batch_pc(qcqpmi_ctx *c, int64_t B, const double *P0s, const double *q0s, const double *r0s, const double *ds, int64_t S,
                               int max_sweeps, double tol, uint64_t seed, uint64_t seed_stride, uint64_t first_index, const double *V0s,
                               double *V, double *primal, double *y, int64_t *sweeps, double *X) {
-    return sdr_small_batch(c, true, ds, B, P0s, q0s, r0s, S, max_sweeps, tol, seed, seed_stride, first_index, V0s, V, primal, y, sweeps, X);
+    return sdr_small_batch(c, SDR_SMALL_MAXN, true, ds, B, P0s, q0s, r0s, S, max_sweeps, tol, seed, seed_stride, first_index, V0s, V, primal, y, sweeps, X);
+}
+
+// ---- the same two for 1 <= n <= 128: the launches above for n <= 64, the wide kernel (sdr_small_kernel<true>) past it
+int qcqpmi_sdr_batch(qcqpmi_ctx *c, int64_t B, const double *P0s, const double *q0s, const double *r0s, int64_t S, int max_sweeps, double tol,
+                     uint64_t seed, uint64_t seed_stride, uint64_t first_index, const double *V0s, double *V, double *primal, double *y,
+                     int64_t *sweeps, double *X) {
+    return sdr_small_batch(c, SDR_WIDE_MAXN, false, nullptr, B, P0s, q0s, r0s, S, max_sweeps, tol, seed, seed_stride, first_index, V0s, V, primal, y, sweeps, X);
+}
+
+int qcqpmi_sdr_batch_pc(qcqpmi_ctx *c, int64_t B, const double *P0s, const double *q0s, const double *r0s, const double *ds, int64_t S,
+                        int max_sweeps, double tol, uint64_t seed, uint64_t seed_stride, uint64_t first_index, const double *V0s, double *V,
+                        double *primal, double *y, int64_t *sweeps, double *X) {
+    return sdr_small_batch(c, SDR_WIDE_MAXN, true, ds, B, P0s, q0s, r0s, S, max_sweeps, tol, seed, seed_stride, first_index, V0s, V, primal, y, sweeps, X);
 }
 
 }  // extern "C"

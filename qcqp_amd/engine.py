@@ -509,27 +509,37 @@ class Engine(object):
         population is not touched.
         ds (B, n), every entry > 0: PER-PROBLEM d (qcqpmi_sdr_small_batch_pc) -- problem b has the constraints x_i^2 == ds[b, i]
         instead of the context's; None: the context's d for every problem."""
+        return self._sdr_batch('sdr_small_batch', P0s, q0s, r0s, S, max_sweeps, tol, seed, seed_stride, first_index, V0s, want_V, ds)
+
+    def sdr_batch(self, P0s, q0s, r0s, S, max_sweeps=5000, tol=1e-11, seed=0, seed_stride=1, first_index=0, V0s=None, want_V=True,
+                  ds=None):
+        """sdr_small_batch for problems of up to 128 variables (qcqpmi_sdr_batch; with ds qcqpmi_sdr_batch_pc): the same arguments, the
+        same dictionary.  n <= 64 runs exactly the launch of sdr_small_batch (same kernel, same bits); 65 <= n <= 128 runs the wide
+        kernel sdr_small_kernel<true>: one wavefront per problem, C_b packed in LDS, two coordinates per lane in the samples."""
+        return self._sdr_batch('sdr_batch', P0s, q0s, r0s, S, max_sweeps, tol, seed, seed_stride, first_index, V0s, want_V, ds)
+
+    def _sdr_batch(self, name, P0s, q0s, r0s, S, max_sweeps, tol, seed, seed_stride, first_index, V0s, want_V, ds):
         P0s = np.ascontiguousarray(P0s, dtype=np.float64)
         q0s = np.ascontiguousarray(q0s, dtype=np.float64)
         r0s = np.ascontiguousarray(r0s, dtype=np.float64).ravel()
         B, S, n = int(P0s.shape[0]) if P0s.ndim == 3 else 0, int(S), self.n
         if P0s.shape != (B, n, n) or q0s.shape != (B, n) or r0s.shape != (B,):
-            raise ValueError('sdr_small_batch: expected P0s (B, n, n), q0s (B, n), r0s (B,) with n = %d' % n)
+            raise ValueError('%s: expected P0s (B, n, n), q0s (B, n), r0s (B,) with n = %d' % (name, n))
         if V0s is not None:
             V0s = np.ascontiguousarray(V0s, dtype=np.float64)
             if V0s.shape != (B, n + 1, 64):
-                raise ValueError('sdr_small_batch: expected V0s of shape (B, n + 1, 64)')
+                raise ValueError('%s: expected V0s of shape (B, n + 1, 64)' % name)
         out = dict(V=np.empty((B, n + 1, 64)) if want_V else None, primal=np.empty(B), y=np.empty((B, n + 1)),
                    sweeps=np.zeros(B, dtype=np.int64), X=np.empty((B, max(S, 0), n)))
         tail = (S, int(max_sweeps), float(tol), int(seed), int(seed_stride), int(first_index), _dp(V0s), _dp(out['V']), _dp(out['primal']),
                 _dp(out['y']), _ip(out['sweeps']), _dp(out['X']) if S > 0 else None)
         if ds is None:
-            self._chk(self.L.qcqpmi_sdr_small_batch(self.h, B, _dp(P0s), _dp(q0s), _dp(r0s), *tail))
+            self._chk(getattr(self.L, 'qcqpmi_' + name)(self.h, B, _dp(P0s), _dp(q0s), _dp(r0s), *tail))
         else:
             ds = np.ascontiguousarray(ds, dtype=np.float64)
             if ds.shape != (B, n):
-                raise ValueError('sdr_small_batch: expected ds of shape (B, n)')
-            self._chk(self.L.qcqpmi_sdr_small_batch_pc(self.h, B, _dp(P0s), _dp(q0s), _dp(r0s), _dp(ds), *tail))
+                raise ValueError('%s: expected ds of shape (B, n)' % name)
+            self._chk(getattr(self.L, 'qcqpmi_' + name + '_pc')(self.h, B, _dp(P0s), _dp(q0s), _dp(r0s), _dp(ds), *tail))
         return out
 
     # ------------------------------------------------------------------ selection

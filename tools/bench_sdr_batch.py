@@ -1,4 +1,5 @@
-"""Wall time of the batched SDR suggest (qcqpmi_sdr_small_batch) against the per-problem loop it replaces.
+"""Wall time of the batched SDR suggest (qcqpmi_sdr_small_batch; --wide: qcqpmi_sdr_batch, n up to 128) against the per-problem loop
+it replaces.
 
 Workload: problems.boolean_least_squares_batch(B, n, m), S samples per problem; both paths at their own defaults (max_sweeps = 5000,
 tol = 1e-11).
@@ -9,6 +10,8 @@ tol = 1e-11).
              cooperative launch of sdr_mixing_kernel, V to the host, the certificate, an SVD for the sampling factor, the upload of mu
              and F, the sampling and evaluation launches.  Timed on the first --loop-problems problems and SCALED LINEARLY to B (every
              problem costs the same launches; stated as such in the output).
+--wide: the batched call is Engine.sdr_batch, the entry point of QCQPBatch.suggest(SDR, wide=True) (n <= 64: the same launch; 65 <= n
+<= 128: sdr_small_kernel<true>).  Without the flag the tool runs what it always ran.
 Prints one JSON line (with how many of the timed problems both paths certify and the largest relative difference of their bounds).
 """
 import argparse
@@ -29,6 +32,7 @@ def main():
     ap.add_argument('--repeat', type=int, default=5)
     ap.add_argument('--loop-problems', type=int, default=64)
     ap.add_argument('--seed', type=int, default=1)
+    ap.add_argument('--wide', action='store_true', help='Engine.sdr_batch (qcqpmi_sdr_batch): n up to 128')
     args = ap.parse_args()
 
     import numpy as np
@@ -44,9 +48,11 @@ def main():
     d = sdr.unit_diagonal_family(qb.form)
     C = sdr.lifted_cost_batch(qb.P0s, qb.q0s, qb.r0s, d)
 
+    run = e.sdr_batch if args.wide else e.sdr_small_batch
+
     def batched():
         t0 = time.perf_counter()
-        o = e.sdr_small_batch(qb.P0s, qb.q0s, qb.r0s, args.S, seed=args.seed, want_V=False)
+        o = run(qb.P0s, qb.q0s, qb.r0s, args.S, seed=args.seed, want_V=False)
         t1 = time.perf_counter()
         cert = sdr.certify_batch(C, o['y'], o['sweeps'], 5000)
         t2 = time.perf_counter()
@@ -73,7 +79,7 @@ def main():
     both = [b for b in range(nl) if single[b][1] and single[b][0] is not None and cert['converged'][b]]
     diff = max([abs(single[b][0] - cert['bound'][b]) / (1.0 + abs(single[b][0])) for b in both] or [float('nan')])
     print(json.dumps(dict(
-        workload=dict(B=args.B, n=args.n, m=args.m, S=args.S, max_sweeps=5000, tol=1e-11), kernel='sdr_small_kernel',
+        workload=dict(B=args.B, n=args.n, m=args.m, S=args.S, max_sweeps=5000, tol=1e-11), kernel='sdr_small_kernel<true>' if args.wide and args.n > 64 else 'sdr_small_kernel',
         batched_s=t_batched, batched_call_s=t_call, batched_certify_s=t_batched - t_call, batched_all_s=[r[0] for r in runs],
         certified='%d/%d' % (int(cert['converged'].sum()), args.B), sweeps_mean=float(np.mean(o['sweeps'])), sweeps_max=int(np.max(o['sweeps'])),
         loop_problems=nl, loop_s_measured=t_loop, loop_s_scaled_to_B=t_loop * args.B / nl, loop_scaling='linear in B (not measured beyond loop_problems)',
