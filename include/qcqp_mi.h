@@ -162,6 +162,23 @@ int qcqpmi_feasible_intervals_batch(int device, int64_t count, const double *pqr
 int qcqpmi_onevar_coeffs(qcqpmi_ctx *ctx, const int64_t *coord, double *out);
 int qcqpmi_onevar_qcqp_batch(int device, int64_t count, const double *f0, const double *fs, const int *nf,
                              const double *s, uint64_t seed, double *x, int *status, double *C_out, int *nC_out);
+/*   The same onevar_qcqp by each instantiation of the set builder + minimiser that a coordinate-descent kernel runs, and one
+ *   phase-1 coordinate visit (qcqp.py:113-136) by each of its restatements.  Layouts, draws and status codes as above.
+ *        onevar variant: 0 / 1 / 2 = the end-point sweep with 4 / 2 / 1 constraint slots (0 is qcqpmi_onevar_qcqp_batch);
+ *            3 / 4 / 5 = the closed form for exactly one constraint, held in 4 / 2 / 1 slots.  C_out keeps 5 pieces per case;
+ *            those a variant cannot hold are NaN.
+ *        visit variant: 0 / 1 = the generic visit with 1 / 4 slots; 2 = the band class (one constraint p x^2 + r == 0, p > 1e-4)
+ *            resolved by hand; 3 / 4 = two band visits fused (r < -1e-3; a case shares the visit with its neighbour i ^ 1 where
+ *            that one has the same (p, r), else with a padding element), 4 with the fast first phase of the bisection.
+ *            cons = count x 4 x (p, q, r, relop as a number); xi = the coordinate's value before the visit; draws are keyed
+ *            (seed; restart = case index; coordinate 0; sweep).  x_out = the value after the visit, moved = 1 where the update was
+ *            accepted, vafter = the coordinate's largest violation afterwards, status as qcqpmi_cd_status.
+ *   QCQPMI_EINVAL for an unknown variant; QCQPMI_EUNSUPPORTED, before anything is launched, for a case outside the variant's
+ *   contract (more constraints than slots, the closed form with nf != 1, a band variant on another constraint or r >= -1e-3). */
+int qcqpmi_onevar_variant_batch(int device, int variant, int64_t count, const double *f0, const double *fs, const int *nf,
+                                const double *s, uint64_t seed, double *x, int *status, double *C_out, int *nC_out);
+int qcqpmi_p1_visit_batch(int device, int variant, int64_t count, const double *cons, const int *nf, const double *xi, double tol,
+                          double viol_tol, uint64_t seed, int64_t sweep, double *x_out, int *moved, double *vafter, int *status);
 
 /* ---- improve(ADMM) on the resident population (improve_admm qcqp.py:254-285; admm_phase1 :195-212;
  * admm_phase2 :215-251; onecons_qcqp utilities.py:149-196).  The host supplies what the reference

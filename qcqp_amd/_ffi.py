@@ -48,6 +48,10 @@ PROTOTYPES = [
     ('qcqpmi_onevar_coeffs', C.c_int, [C.c_void_p, c_ip, c_dp]),
     ('qcqpmi_onevar_qcqp_batch', C.c_int, [C.c_int, C.c_int64, c_dp, c_dp, C.POINTER(C.c_int), c_dp, C.c_uint64, c_dp,
                                            C.POINTER(C.c_int), c_dp, C.POINTER(C.c_int)]),
+    ('qcqpmi_onevar_variant_batch', C.c_int, [C.c_int, C.c_int, C.c_int64, c_dp, c_dp, C.POINTER(C.c_int), c_dp, C.c_uint64, c_dp,
+                                              C.POINTER(C.c_int), c_dp, C.POINTER(C.c_int)]),
+    ('qcqpmi_p1_visit_batch', C.c_int, [C.c_int, C.c_int, C.c_int64, c_dp, C.POINTER(C.c_int), c_dp, C.c_double, C.c_double, C.c_uint64,
+                                        C.c_int64, c_dp, C.POINTER(C.c_int), c_dp, C.POINTER(C.c_int)]),
     ('qcqpmi_admm_set_eig', C.c_int, [C.c_void_p, c_dp, c_dp]),
     ('qcqpmi_admm_setup', C.c_int, [C.c_void_p]),
     ('qcqpmi_admm_set_basis', C.c_int, [C.c_void_p, C.c_int64, c_dp, c_dp, c_dp]),

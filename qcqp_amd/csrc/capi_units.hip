@@ -6,6 +6,7 @@
 // itself and not only through whole trajectories.
 #include "capi_ctx.h"
 #include "onevar.h"
+#include "unit_variants.h"   // one case of every instantiation the kernels run: sweep / single at 1, 2, 4 slots, the phase-1 visits
 #include "cd_general.h"      // gen_onevar_t2t1, gen_onevar_t0: the two device functions only, no kernel of it is instantiated here
 
 using namespace qcqpmi;
@@ -48,6 +49,28 @@ __global__ void unit_onevar_kernel(int64_t count, const double *__restrict__ f0,
     if (Cout)
 #pragma unroll
         for (int j = 0; j <= UNIT_MAXC; j++) { Cout[(i * (UNIT_MAXC + 1) + j) * 2] = C.lo[j]; Cout[(i * (UNIT_MAXC + 1) + j) * 2 + 1] = C.hi[j]; }
+}
+
+// onevar_qcqp by the instantiation VARIANT of the set builder + minimiser, and one phase-1 coordinate visit by the restatement
+// VARIANT (unit_variants.h): one kernel per variant, chosen by the host, so that each is the straight-line code of that variant
+template <int VARIANT>
+__global__ void unit_onevar_variant_kernel(int64_t count, const double *__restrict__ f0, const double *__restrict__ fs,
+                                           const int *__restrict__ nf, const double *__restrict__ s, uint64_t seed,
+                                           double *__restrict__ x, int *__restrict__ status, double *__restrict__ Cout,
+                                           int *__restrict__ nC) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= count) return;
+    uv_onevar_case<VARIANT>(i, f0, fs, nf, s, seed, x, status, Cout, nC);
+}
+
+template <int VARIANT>
+__global__ void unit_p1_visit_kernel(int64_t count, const double *__restrict__ cons, const int *__restrict__ nf,
+                                     const double *__restrict__ xi, double tol, double viol_tol, uint64_t seed, int64_t sweep,
+                                     double *__restrict__ x_out, int *__restrict__ moved, double *__restrict__ vafter,
+                                     int *__restrict__ status) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= count) return;
+    pv_visit_case<VARIANT>(i, count, cons, nf, xi, tol, viol_tol, seed, sweep, x_out, moved, vafter, status);
 }
 
 // get_onevar_func (utilities.py:99-105) for every function of the problem at the coordinate coord[r] of restart r of the
@@ -161,6 +184,82 @@ int qcqpmi_onevar_qcqp_batch(int device, int64_t count, const double *f0, const 
     UNITCHK(hipMemcpy(status, dst.p, (size_t)count * sizeof(int), hipMemcpyDeviceToHost));
     if (C_out) UNITCHK(hipMemcpy(C_out, dC.p, (size_t)count * (UNIT_MAXC + 1) * 2 * sizeof(double), hipMemcpyDeviceToHost));
     if (nC_out) UNITCHK(hipMemcpy(nC_out, dnC.p, (size_t)count * sizeof(int), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+int qcqpmi_onevar_variant_batch(int device, int variant, int64_t count, const double *f0, const double *fs, const int *nf,
+                                const double *s, uint64_t seed, double *x, int *status, double *C_out, int *nC_out) {
+    if (count <= 0 || !f0 || !fs || !nf || !s || !x || !status) return fail(nullptr, QCQPMI_EINVAL, "onevar_variant_batch: bad arguments");
+    if (variant < 0 || variant >= UV_ONEVAR_VARIANTS) return fail(nullptr, QCQPMI_EINVAL, "onevar_variant_batch: unknown variant %d", variant);
+    for (int64_t i = 0; i < count; i++)
+        if (!uv_case_ok(variant, nf[i]))
+            return fail(nullptr, QCQPMI_EUNSUPPORTED, "onevar_variant_batch: case %lld has %d constraints, variant %d takes %s%d",
+                        (long long)i, nf[i], variant, uv_single(variant) ? "exactly 1 of its " : "at most ", uv_maxc(variant));
+    if (qcqpmi_device_count() <= 0) return fail(nullptr, QCQPMI_EHIP, "no HIP device visible (there is no CPU fallback)");
+    UNITCHK(hipSetDevice(device));
+    DevBuf<double> df0, dfs, ds, dx, dC;
+    DevBuf<int> dnf, dst, dnC;
+    UNITCHK(unit_up(df0, f0, (size_t)count * 3));
+    UNITCHK(unit_up(dfs, fs, (size_t)count * UV_SLOTS * 4));
+    UNITCHK(unit_up(dnf, nf, (size_t)count));
+    UNITCHK(unit_up(ds, s, (size_t)count));
+    UNITCHK(unit_up(dx, (const double *)nullptr, (size_t)count));
+    UNITCHK(unit_up(dst, (const int *)nullptr, (size_t)count));
+    UNITCHK(unit_up(dC, (const double *)nullptr, (size_t)count * (UV_SLOTS + 1) * 2));
+    UNITCHK(unit_up(dnC, (const int *)nullptr, (size_t)count));
+    const dim3 grid((unsigned)((count + 63) / 64)), block(64);
+#define UV_LAUNCH(V)                                                                                                            \
+    case V:                                                                                                                     \
+        hipLaunchKernelGGL(unit_onevar_variant_kernel<V>, grid, block, 0, 0, count, df0.p, dfs.p, dnf.p, ds.p, seed, dx.p, dst.p, dC.p, \
+                           dnC.p);                                                                                              \
+        break;
+    switch (variant) {
+        UV_LAUNCH(UV_SWEEP4) UV_LAUNCH(UV_SWEEP2) UV_LAUNCH(UV_SWEEP1) UV_LAUNCH(UV_SINGLE4) UV_LAUNCH(UV_SINGLE2) UV_LAUNCH(UV_SINGLE1)
+    }
+#undef UV_LAUNCH
+    UNITCHK(hipGetLastError());
+    UNITCHK(hipMemcpy(x, dx.p, (size_t)count * sizeof(double), hipMemcpyDeviceToHost));
+    UNITCHK(hipMemcpy(status, dst.p, (size_t)count * sizeof(int), hipMemcpyDeviceToHost));
+    if (C_out) UNITCHK(hipMemcpy(C_out, dC.p, (size_t)count * (UV_SLOTS + 1) * 2 * sizeof(double), hipMemcpyDeviceToHost));
+    if (nC_out) UNITCHK(hipMemcpy(nC_out, dnC.p, (size_t)count * sizeof(int), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+int qcqpmi_p1_visit_batch(int device, int variant, int64_t count, const double *cons, const int *nf, const double *xi, double tol,
+                          double viol_tol, uint64_t seed, int64_t sweep, double *x_out, int *moved, double *vafter, int *status) {
+    if (count <= 0 || !cons || !nf || !xi || !x_out || !moved || !vafter || !status)
+        return fail(nullptr, QCQPMI_EINVAL, "p1_visit_batch: bad arguments");
+    if (variant < 0 || variant >= PV_VISIT_VARIANTS) return fail(nullptr, QCQPMI_EINVAL, "p1_visit_batch: unknown variant %d", variant);
+    for (int64_t i = 0; i < count; i++)
+        if (!pv_case_ok(variant, cons + i * UV_SLOTS * 4, nf[i]))
+            return fail(nullptr, QCQPMI_EUNSUPPORTED, "p1_visit_batch: case %lld (%d constraints) is outside the contract of variant %d",
+                        (long long)i, nf[i], variant);
+    if (qcqpmi_device_count() <= 0) return fail(nullptr, QCQPMI_EHIP, "no HIP device visible (there is no CPU fallback)");
+    UNITCHK(hipSetDevice(device));
+    DevBuf<double> dcons, dxi, dx, dva;
+    DevBuf<int> dnf, dmv, dst;
+    UNITCHK(unit_up(dcons, cons, (size_t)count * UV_SLOTS * 4));
+    UNITCHK(unit_up(dnf, nf, (size_t)count));
+    UNITCHK(unit_up(dxi, xi, (size_t)count));
+    UNITCHK(unit_up(dx, (const double *)nullptr, (size_t)count));
+    UNITCHK(unit_up(dva, (const double *)nullptr, (size_t)count));
+    UNITCHK(unit_up(dmv, (const int *)nullptr, (size_t)count));
+    UNITCHK(unit_up(dst, (const int *)nullptr, (size_t)count));
+    const dim3 grid((unsigned)((count + 63) / 64)), block(64);
+#define PV_LAUNCH(V)                                                                                                             \
+    case V:                                                                                                                      \
+        hipLaunchKernelGGL(unit_p1_visit_kernel<V>, grid, block, 0, 0, count, dcons.p, dnf.p, dxi.p, tol, viol_tol, seed, sweep, dx.p, \
+                           dmv.p, dva.p, dst.p);                                                                                 \
+        break;
+    switch (variant) {
+        PV_LAUNCH(PV_CORE1) PV_LAUNCH(PV_CORE4) PV_LAUNCH(PV_BAND) PV_LAUNCH(PV_BAND_N2) PV_LAUNCH(PV_BAND_N2_FASTA)
+    }
+#undef PV_LAUNCH
+    UNITCHK(hipGetLastError());
+    UNITCHK(hipMemcpy(x_out, dx.p, (size_t)count * sizeof(double), hipMemcpyDeviceToHost));
+    UNITCHK(hipMemcpy(moved, dmv.p, (size_t)count * sizeof(int), hipMemcpyDeviceToHost));
+    UNITCHK(hipMemcpy(vafter, dva.p, (size_t)count * sizeof(double), hipMemcpyDeviceToHost));
+    UNITCHK(hipMemcpy(status, dst.p, (size_t)count * sizeof(int), hipMemcpyDeviceToHost));
     return 0;
 }
 

@@ -967,6 +967,72 @@ def test_errors_without_a_context_share_one_slot():
         call()
 
 
+def test_variant_unit_operators_check_their_arguments_before_any_launch():
+    """qcqpmi_onevar_variant_batch / qcqpmi_p1_visit_batch: bad arguments and an unknown variant are QCQPMI_EINVAL (-1), a case
+    outside the variant's contract is QCQPMI_EUNSUPPORTED (-4) -- more constraints than the variant has slots, the closed form with
+    nf != 1, a band variant handed another constraint, a fused band variant with r >= -1e-3 -- all decided on the host (no device
+    here), and an acceptable call gets as far as looking for a device."""
+    from qcqp_amd import _ffi
+    L = _ffi.lib()
+    ip = ctypes.POINTER(ctypes.c_int)
+    dp = lambda a: a.ctypes.data_as(_ffi.c_dp)
+    have_gpu = L.qcqpmi_device_count() > 0
+    f0, s, x = np.zeros((2, 3)), np.zeros(2), np.zeros(2)
+    st, nC = np.zeros(2, dtype=np.int32), np.zeros(2, dtype=np.int32)
+    Cs = np.zeros((2, 5, 2))
+    fs = np.zeros((2, 4, 4))
+    fs[:, :, 0], fs[:, :, 2], fs[:, :, 3] = 1., -1., 1.
+
+    def onevar(variant, nf, count=2):
+        nf = np.array(nf, dtype=np.int32)
+        return L.qcqpmi_onevar_variant_batch(0, variant, count, dp(f0), dp(fs), nf.ctypes.data_as(ip), dp(s), 1, dp(x), st.ctypes.data_as(ip),
+                                             dp(Cs), nC.ctypes.data_as(ip))
+
+    assert onevar(0, [1, 1], count=0) == -1 and L.qcqpmi_last_error(None) == b'onevar_variant_batch: bad arguments'
+    for v in (-1, 6):
+        assert onevar(v, [1, 1]) == -1 and L.qcqpmi_last_error(None) == ('onevar_variant_batch: unknown variant %d' % v).encode()
+    for v, nf in ((0, [1, 5]), (0, [-1, 1]), (1, [3, 1]), (2, [1, 2]), (3, [1, 2]), (3, [0, 1]), (4, [2, 1]), (5, [1, 0])):
+        assert onevar(v, nf) == -4, (v, nf)
+        assert L.qcqpmi_last_error(None).startswith(b'onevar_variant_batch: case '), (v, nf)
+    if not have_gpu:
+        for v, nf in ((0, [4, 0]), (1, [2, 0]), (2, [1, 0]), (3, [1, 1]), (4, [1, 1]), (5, [1, 1])):
+            assert onevar(v, nf) == -2 and L.qcqpmi_last_error(None).startswith(b'no HIP device'), (v, nf)
+
+    xi, va = np.ones(2), np.zeros(2)
+    mv = np.zeros(2, dtype=np.int32)
+    band = np.zeros((2, 4, 4))
+    band[:, 0] = [1., 0., -1., 2.]
+
+    def visit(variant, cons, nf, count=2):
+        nf = np.array(nf, dtype=np.int32)
+        cons = np.ascontiguousarray(cons)
+        return L.qcqpmi_p1_visit_batch(0, variant, count, dp(cons), nf.ctypes.data_as(ip), dp(xi), 1e-4, 1e-2, 1, 0, dp(x), mv.ctypes.data_as(ip),
+                                       dp(va), st.ctypes.data_as(ip))
+
+    assert visit(0, band, [1, 1], count=0) == -1 and L.qcqpmi_last_error(None) == b'p1_visit_batch: bad arguments'
+    for v in (-1, 5):
+        assert visit(v, band, [1, 1]) == -1 and L.qcqpmi_last_error(None) == ('p1_visit_batch: unknown variant %d' % v).encode()
+    bad = []
+    for v in range(5):
+        bad += [(v, band, [1, 0]), (v, band, [1, 2 if v != 1 else 5])]
+    for k, val in ((1, 1e-3), (3, 1.), (0, 1e-4), (0, -1.)):       # a linear term, an inequality, p at the threshold, p < 0
+        c = band.copy()
+        c[1, 0, k] = val
+        bad += [(v, c, [1, 1]) for v in (2, 3, 4)]
+    for r in (-1e-3, 0., .5):
+        c = band.copy()
+        c[1, 0, 2] = r
+        bad += [(v, c, [1, 1]) for v in (3, 4)]
+    for v, cons, nf in bad:
+        assert visit(v, cons, nf) == -4, (v, nf, cons[1, 0])
+        assert L.qcqpmi_last_error(None).startswith(b'p1_visit_batch: case 1 '), (v, nf)
+    if not have_gpu:
+        c = band.copy()
+        c[1, 0, 2] = -1e-3
+        for v, cons, nf in ((0, band, [1, 1]), (1, band, [4, 1]), (2, c, [1, 1]), (3, band, [1, 1]), (4, band, [1, 1])):
+            assert visit(v, cons, nf) == -2 and L.qcqpmi_last_error(None).startswith(b'no HIP device'), v
+
+
 def test_every_header_compiles_on_its_own(tmp_path):
     """A header that needs something its includer happens to provide forces every new includer to fake it (cd_phase2.h once named
     a function of the file that included it: three units carried stand-in definitions).  Each csrc/*.h is compiled alone, device

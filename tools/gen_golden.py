@@ -204,6 +204,40 @@ def g4():
          err=np.array([c['err'] for c in cases]), draws=np.array([c['draws'] for c in cases]))
 
 
+# ---------------------------------------------------------------------- G12
+def g12():
+    """onevar_qcqp of the reference on the case lattice of tests/onevar_cases.py (degenerate lists by construction).  The inputs are
+    stored as indices into that module's tables, with the length and checksum of the coefficients they stand for."""
+    sys.path.insert(0, os.path.join(REPO, 'tests'))
+    import onevar_cases as oc
+    lat = oc.onevar_lattice()
+    f0, fs, nf, s = oc.onevar_arrays(lat)
+    N = len(nf)
+    x = np.full(N, np.nan)
+    isnone = np.zeros(N, dtype=np.int8)
+    err = np.zeros(N, dtype=np.int8)
+    draws = np.zeros(N, dtype=np.int16)
+    for i in range(N):
+        np.random.seed(i)
+        pos0 = np.random.get_state()[2]
+        obj = U.OneVarQuadraticFunction(*f0[i])
+        nfs = [U.OneVarQuadraticFunction(c[0], c[1], c[2], oc.RELSTR[int(c[3])]) for c in fs[i, :nf[i]]]
+        try:
+            xi = U.onevar_qcqp(obj, nfs, float(s[i]))
+        except Exception:  # OverflowError / NameError quirks
+            err[i] = 1
+            draws[i] = -1
+            continue
+        draws[i] = (np.random.get_state()[2] - pos0) % 624
+        if xi is None:
+            isnone[i] = 1
+        else:
+            x[i] = xi
+    nbytes, crc = oc.checksum(f0, fs, nf, s)
+    save('g12_onevar_lattice', obj=lat['obj'], atom=lat['atom'], slack=lat['slack'], x=x, isnone=isnone, err=err, draws=draws,
+         nbytes=np.int64(nbytes), crc=np.int64(crc))
+
+
 # ----------------------------------------------------------------------- G5
 def g5():
     rs = np.random.RandomState(5)
@@ -404,6 +438,9 @@ def g9_g10():
 
 
 if __name__ == '__main__':
+    if '--only=g12' in sys.argv[1:]:
+        g12()
+        sys.exit(0)
     if any(a_.startswith('--only=') for a_ in sys.argv[1:]):      # --only=circle5: one family of G6 / G7
         g6_g7()
         sys.exit(0)
@@ -414,3 +451,4 @@ if __name__ == '__main__':
     g6_g7()
     g8()
     g9_g10()
+    g12()
