@@ -474,6 +474,35 @@ int qcqpmi_sdr_batch(qcqpmi_ctx *ctx, int64_t B, const double *P0s, const double
 int qcqpmi_sdr_batch_pc(qcqpmi_ctx *ctx, int64_t B, const double *P0s, const double *q0s, const double *r0s, const double *ds,
                         int64_t S, int max_sweeps, double tol, uint64_t seed, uint64_t seed_stride, uint64_t first_index,
                         const double *V0s, double *V, double *primal, double *y, int64_t *sweeps, double *X);
+/* SUGGEST(SPECTRAL) FOR MANY SMALL PROBLEMS IN ONE LAUNCH (added within ABI 6: a new symbol, nothing else changes).  B objectives
+ * P0s [B][n][n] (each symmetric), q0s [B][n], r0s [B], 1 <= n <= 64, whose constraints ALL carry one relop (relop_eq != 0: ==, else <=)
+ * and, summed as suggest(SPECTRAL) sums them (qcqp.py:41-70), give ONE constraint
+ *     c(x) = sum_i (a_i x_i^2 + beta_i x_i) + gamma  (relop)  0,   every a_i > 0,   rho^2 = sum_i beta_i^2 / (4 a_i) - gamma > 0:
+ * agg = [a (n) | beta (n) | gamma], one for all problems (agg_stride = 0) or [B][2 n + 1] (agg_stride = 2 n + 1).  The context
+ * supplies n, the device and its buffers; its own constraints are not read.  The reference's relaxation
+ *     minimise <W0, X>  s.t.  <Wc, X> (relop) 0,  X_NN = 1,  X PSD
+ * has one quadratic constraint, so it is exact and its value is that of  min f0(x) s.t. c(x) (relop) 0 -- a trust-region problem
+ * on a sphere or ball.  With s = sqrt(a), y = s o x + beta / (2 s):  c = |y|^2 - rho^2,  f0 = y'Ay + 2 g'y + const,  A = S^-1 P0 S^-1.
+ * One wavefront per problem (spectral_small_kernel, csrc/spectral_small.hip), A_b and Q_b in its LDS, no wave waits for another:
+ * A = Q diag(lam) Q' by cyclic two-sided Jacobi in a fixed round-robin order (csrc/jacobi_small.h; stop at off(A) <= tol |A|_F or
+ * max_sweeps), then in the lanes the multiplier mu >= -lam_min (and >= 0 for <=) with sum_k gh_k^2 / (lam_k + mu)^2 = rho^2,
+ * gh = Q'g, by a safeguarded Newton iteration with a fixed rule, and y = -Q (gh / (lam + mu)); for <= with lam_min > 0 and the
+ * unconstrained minimiser in the ball mu = 0; in the hard case (g without a component in the lowest eigenspace, the rest shorter
+ * than rho; threshold 2^-46, csrc/spectral_solve.h) mu = -lam_min and y = y_reg + tau q_min, tau >= 0, q_min with its entry of
+ * largest magnitude positive.  Every wave sum has one order: a problem's result depends on (P0_b, q0_b, r0_b, agg_b, relop_eq,
+ * max_sweeps, tol) alone -- not on B, the problems beside it, the workgroups or the dealing order: bit for bit.  The reference
+ * hands the relaxation to a third-party solver and reads its point off an eigenvector of arbitrary sign: parity unpinned by
+ * construction, validated by the certificate (feasibility, stationarity, lambda_min(P0_b + mu_b diag a_b) >= 0, for <= the sign of
+ * mu and complementarity: qcqp_amd.sdr.certify_spectral_batch).
+ * Outputs, any may be NULL: x [B][n] = (y - beta / (2 s)) / s; bound [B] = f0(x) recomputed from P0_b, q0_b, r0_b; mu [B];
+ * lam [B][n], the eigenvalues of A_b ascending; sweeps [B]; branch [B]: 0 interior, 1 boundary, 2 hard case; status [B]: 0, 1 if
+ * Jacobi stopped at max_sweeps, 2 if a result is not finite.
+ * QCQPMI_EUNSUPPORTED: n > 64.  QCQPMI_EINVAL: B < 1, a missing input, agg_stride other than 0 and 2 n + 1, an a_i that is not
+ * positive and finite, rho^2 <= 0, a P0_b that is not symmetric.  The call works in a buffer of its own: the resident population,
+ * its evaluation, its status codes and qcqpmi_last_cd_kernel stay as they were, whether the call succeeds or is refused. */
+int qcqpmi_spectral_small_batch(qcqpmi_ctx *ctx, int64_t B, const double *P0s, const double *q0s, const double *r0s,
+                                const double *agg, int64_t agg_stride, int relop_eq, int max_sweeps, double tol, double *x,
+                                double *bound, double *mu, double *lam, int64_t *sweeps, int *branch, int *status);
 /* IMPROVE(ADMM) FOR MANY SMALL PROBLEMS IN ONE LAUNCH (added within ABI 6: a new symbol, nothing else changes).  The batch of
  * qcqpmi_cd_small_batch_run -- B objectives P0s [B][n][n] (each symmetric), q0s [B][n], r0s [B] over this context's separable
  * constraint lists (up to four per coordinate, m >= 1 in all), 1 <= n <= 64 -- through improve_admm (qcqp.py:254-285): phase 1, x1 =

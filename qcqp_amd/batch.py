@@ -10,7 +10,10 @@ wide kernels, two coordinates per lane).  improve(ADMM) runs the reference's con
 (2 (P0_b + rho_b m I))^-1 from one batched host inverse.  suggest(SDR) -- for constraints x_i^2 == d_i -- solves the
 semidefinite relaxation of all B problems and draws their samples in one launch as well (n <= 64: ``Engine.sdr_small_batch``,
 qcqpmi_sdr_small_batch; 64 < n <= 128, asked for with wide=True: ``Engine.sdr_batch``, qcqpmi_sdr_batch, the wide kernel with C_b
-packed in LDS) and publishes the certified bounds in ``sdr_bound``; improve() then starts from the samples.  Problem b's results are those of
+packed in LDS) and publishes the certified bounds in ``sdr_bound``; improve() then starts from the samples.  suggest(SPECTRAL) --
+for constraints of ONE relop that sum to a sphere or a ball (Boolean, x_i^2 == d_i, MAXCUT, boxes), n <= 64 -- solves the reference's
+spectral relaxation of all B problems exactly in one launch (``Engine.spectral_small_batch``, qcqpmi_spectral_small_batch: one
+eigendecomposition and one secular equation per problem) and publishes ``spectral_sol`` and ``spectral_bound``.  Problem b's results are those of
 ``QCQP(Problem(funcs_b))`` with suggest(RANDOM, num_samples=R, seed=seed + b seed_stride, first_index=...) followed by
 improve(COORD_DESCENT, ..., seed=seed + b seed_stride, first_index=...).  Problems whose constraints differ in their COEFFICIENTS
 only (boxes with bounds per instance, x_i^2 == d_{b,i}: problems.per_problem_constraints_batch) run through the same launches with
@@ -152,16 +155,20 @@ class QCQPBatch(object):
         self.form = QCQPForm.from_arrays(funcs_list[0])
         self.engine = Engine(self.form, device=device)
         self._suggested = None
-        self._starts = None          # (B, R, n): the samples of suggest(SDR); None: improve() draws the keyed normals itself
+        self._starts = None          # (B, R, n): the samples of suggest(SDR), the point of suggest(SPECTRAL) (R = 1); None: improve() draws the keyed normals itself
         self.sdr_bound = None
         self.sdr_info = None
+        self.spectral_sol = None
+        self.spectral_bound = None
+        self.spectral_info = None
         self.x = None
         self.population_f = None
         self.population_v = None
         self.best_index = None
         self.last_stats = None
 
-    def suggest(self, method=s.RANDOM, num_samples=1, seed=0, first_index=0, seed_stride=1, max_sweeps=5000, tol=1e-11, wide=False):
+    def suggest(self, method=s.RANDOM, num_samples=1, seed=0, first_index=0, seed_stride=1, max_sweeps=5000, tol=1e-11, wide=False,
+                certify=False, jacobi_sweeps=30, jacobi_tol=1e-15):
         """RANDOM: R = num_samples random starts per problem: problem b draws the keyed normals (seed + b seed_stride, first_index + r).
         The points are drawn inside the launch of improve(); nothing runs here.
         SDR (constraints x_i^2 == d_i): one launch solves the relaxation of every problem (mixing method, max_sweeps / tol) and
@@ -169,11 +176,22 @@ class QCQPBatch(object):
         (sdr.certify_batch, which logs the warning for problems that are not certified).  Sets .sdr_bound (B,) -- the rigorous lower bound, NaN where the problem is not certified -- and
         .sdr_info (primal, sweeps, lambda_min, converged); the samples are the starts of improve().
         wide=True admits 65 <= n <= 128 to SDR (``Engine.sdr_batch``: the wide kernel, C_b packed, two coordinates per lane in the
-        samples); n <= 64 runs as without it.  The default refuses n > 64 as before.  RANDOM ignores it."""
-        if method not in (s.RANDOM, s.SDR):
-            raise Exception("QCQPBatch.suggest is defined for the RANDOM and SDR methods")
+        samples); n <= 64 runs as without it.  The default refuses n > 64 as before.  RANDOM ignores it.
+        SPECTRAL (n <= 64; constraints that all carry ONE relop and sum to sum_i (a_i x_i^2 + beta_i x_i) + gamma with every
+        a_i > 0 and rho^2 = sum beta_i^2 / (4 a_i) - gamma > 0: Boolean, x_i^2 == d_i, MAXCUT, boxes (x - lo)(x - hi) <= 0 or == 0,
+        shared or per problem): one launch (``Engine.spectral_small_batch``) solves the reference's spectral relaxation of every
+        problem EXACTLY -- with one aggregated constraint it is a trust-region problem: one Jacobi eigendecomposition
+        (jacobi_sweeps, jacobi_tol) and one secular equation per problem.  num_samples must be 1 (the reference's SPECTRAL yields
+        one point).  Sets .spectral_sol (B, n) and .spectral_bound (B,) -- the relaxation's value, a lower bound of every point
+        feasible for the problem; both NaN where the launch reports a status != 0 -- and .spectral_info (mu, lam_min, sweeps,
+        branch, status; with certify=True also the host certificate of sdr.certify_spectral_batch under 'certificate').  The point is
+        the single start of improve()."""
+        if method not in (s.RANDOM, s.SDR, s.SPECTRAL):
+            raise Exception("QCQPBatch.suggest is defined for the RANDOM, SDR and SPECTRAL methods")
         if int(num_samples) < 1:
             raise Exception("QCQPBatch.suggest: num_samples must be positive")
+        if method == s.SPECTRAL:
+            return self._suggest_spectral(int(num_samples), seed, first_index, seed_stride, certify, jacobi_sweeps, jacobi_tol)
         if method == s.SDR:
             if self.n > MAX_N_SMALL and not wide:      # before any launch
                 raise Exception("QCQPBatch.suggest(SDR) is defined for n <= %d (n = %d) unless wide=True is given (n <= %d: the wide "
@@ -202,6 +220,58 @@ class QCQPBatch(object):
         else:
             self._starts = None
         self._suggested = (int(num_samples), int(seed), int(first_index), int(seed_stride))
+
+    def _spectral_aggregate(self):
+        """(agg, relop) of suggest(SPECTRAL): agg = [a (n) | beta (n) | gamma], the sums of (p, q, r) over the constraints, of shape
+        (2 n + 1,) for shared constraints and (B, 2 n + 1) for per-problem coefficients; raises outside the family."""
+        name, n = "QCQPBatch.suggest(SPECTRAL)", self.n
+        entries = [_entry(f.P, f.qarray, f.r, f.relop) for f in self.form.fs]
+        if not entries:
+            raise Exception("%s: the problems have no constraint (nothing to aggregate)" % name)
+        for k, e in enumerate(entries):
+            if e is None:
+                raise Exception("%s is defined for separable constraints p x_i^2 + q x_i + r (relop) 0: constraint %d couples "
+                                "coordinates or touches none" % (name, k))
+            if e[1] != entries[0][1]:
+                raise Exception("%s is defined for constraints that all carry the same relop (all == or all <=): constraint %d is %s, "
+                                "constraint 0 is %s" % (name, k, e[1], entries[0][1]))
+        coords = np.array([e[0] for e in entries])
+        pqr = np.array([e[2:] for e in entries])[None] if self.cons is None else self.cons      # (1 or B, m, 3)
+        agg = np.zeros((pqr.shape[0], 2 * n + 1))
+        np.add.at(agg[:, :n], (slice(None), coords), pqr[:, :, 0])
+        np.add.at(agg[:, n:2 * n], (slice(None), coords), pqr[:, :, 1])
+        agg[:, 2 * n] = pqr[:, :, 2].sum(axis=1)
+        a, beta, gamma = agg[:, :n], agg[:, n:2 * n], agg[:, 2 * n]
+        where = (lambda b: " of problem %d" % b) if self.cons is not None else (lambda b: "")
+        bad = np.argwhere(~((a > 0.0) & np.isfinite(a)))
+        if bad.size:
+            b, i = int(bad[0][0]), int(bad[0][1])
+            raise Exception("%s is defined for a_i > 0 on every coordinate: coordinate %d%s has a = %g (the sum of p over its constraints; "
+                            "a coordinate with linear constraints only, or with none)" % (name, i, where(b), a[b, i]))
+        rho2 = np.sum(beta * beta / (4. * a), axis=1) - gamma
+        bad = np.nonzero(~((rho2 > 0.0) & np.isfinite(rho2)))[0]
+        if bad.size:
+            b = int(bad[0])
+            raise Exception("%s is defined for rho^2 = sum_i beta_i^2 / (4 a_i) - gamma > 0: rho^2 = %g%s (the aggregated constraint "
+                            "admits at most one point)" % (name, rho2[b], where(b)))
+        return (agg[0] if self.cons is None else agg), entries[0][1]
+
+    def _suggest_spectral(self, num_samples, seed, first_index, seed_stride, certify, jacobi_sweeps, jacobi_tol):
+        if num_samples != 1:
+            raise Exception("QCQPBatch.suggest(SPECTRAL) yields one point per problem: num_samples must be 1 (num_samples = %d)" % num_samples)
+        if self.n > MAX_N_SMALL:      # before any launch
+            raise Exception("QCQPBatch.suggest(SPECTRAL) is defined for n <= %d (n = %d): A_b and Q_b of the eigen-solver fit a wavefront's "
+                            "LDS up to there; or use suggest(RANDOM), or QCQP per problem" % (MAX_N_SMALL, self.n))
+        agg, relop = self._spectral_aggregate()
+        out = self.engine.spectral_small_batch(self.P0s, self.q0s, self.r0s, agg, relop, max_sweeps=jacobi_sweeps, tol=jacobi_tol)
+        ok = out['status'] == 0
+        self.spectral_sol = np.where(ok[:, None], out['x'], np.nan)
+        self.spectral_bound = np.where(ok, out['bound'], np.nan)
+        self.spectral_info = dict(mu=out['mu'], lam_min=out['lam'][:, 0], sweeps=out['sweeps'], branch=out['branch'], status=out['status'])
+        if certify:
+            self.spectral_info['certificate'] = _sdr.certify_spectral_batch(self.P0s, self.q0s, agg, relop, out['x'], out['mu'])
+        self._starts = np.ascontiguousarray(out['x'][:, None, :])
+        self._suggested = (1, int(seed), int(first_index), int(seed_stride))
 
     def improve(self, method=s.COORD_DESCENT, num_iters=1000, viol_tol=1e-2, tol=None, phase1=True, seed=None, viol_lim=1e4, rho=None,
                 wide=False):

@@ -1,8 +1,8 @@
 // Small-problem batch part of the C ABI: B small problems over the context's constraint structure in ONE
-// persistent launch of cd_small.hip, admm_small.hip or sdr_small.hip.  A call works in a device buffer of its own (sb_work for CD and
-// ADMM, ss_work for SDR): the resident population, its evaluation, its status codes and an installed ADMM basis are not touched,
+// persistent launch of cd_small.hip, admm_small.hip, sdr_small.hip or spectral_small.hip.  A call works in a device buffer of its own
+// (sb_work for CD and ADMM, ss_work for SDR and SPECTRAL): the resident population, its evaluation, its status codes and an installed ADMM basis are not touched,
 // whether the call succeeds or is refused.  The shared steps come first; a driver is its argument struct, its launch and its outputs.
-// Host code only: the three launcher headers, and the launch of the core's selection kernel through capi_ctx.h.
+// Host code only: the four launcher headers, and the launch of the core's selection kernel through capi_ctx.h.
 #include <cmath>
 #include <cstring>
 
@@ -10,6 +10,7 @@
 #include "cd_small.h"
 #include "admm_small.h"
 #include "sdr_small.h"
+#include "spectral_small.h"
 
 using namespace qcqpmi;
 
@@ -253,6 +254,65 @@ int sdr_small_batch(qcqpmi_ctx *c, int64_t maxn, bool per_problem, const double 
     return 0;
 }
 
+// ---- suggest(SPECTRAL) for problems whose constraints aggregate to ONE sphere (relop_eq) or ONE ball: agg = [a (n) | beta (n) | gamma]
+// per problem (agg_stride = 2 n + 1) or shared (agg_stride = 0).  The context gives n, the device and the buffer; its constraints are not read.
+int spectral_small_batch(qcqpmi_ctx *c, int64_t B, const double *P0s, const double *q0s, const double *r0s, const double *agg, int64_t agg_stride,
+                         int relop_eq, int max_sweeps, double tol, double *x, double *bound, double *mu, double *lam, int64_t *sweeps,
+                         int *branch, int *status) {
+    int rc = check_ready(c, false);
+    if (rc) return rc;
+    if (c->n > SPECTRAL_SMALL_MAXN) return fail(c, QCQPMI_EUNSUPPORTED, "spectral_small_batch: n = %lld, the small-problem kernel takes n <= %d (A_b and Q_b in LDS, one lane per eigenvalue)", (long long)c->n, SPECTRAL_SMALL_MAXN);
+    const int64_t n = c->n, na = 2 * n + 1;
+    if (B < 1 || B >= (1LL << 30) || max_sweeps < 0 || !(tol >= 0.0) || !P0s || !q0s || !r0s || !agg || (agg_stride != 0 && agg_stride != na))
+        return fail(c, QCQPMI_EINVAL, "spectral_small_batch: bad B / max_sweeps / tol / agg_stride (0 or 2 n + 1), or a missing input array");
+    const int64_t nagg = agg_stride ? B : 1;
+    for (int64_t b = 0; b < nagg; b++) {
+        const double *ab = agg + b * na;
+        double r2 = -ab[2 * n];
+        for (int64_t i = 0; i < n; i++) {
+            if (!(ab[i] > 0.0) || !std::isfinite(ab[i]) || !std::isfinite(ab[n + i]))
+                return fail(c, QCQPMI_EINVAL, "spectral_small_batch: a = %g, beta = %g of coordinate %lld of problem %lld: a must be positive, both finite", ab[i], ab[n + i], (long long)i, (long long)b);
+            r2 += ab[n + i] * ab[n + i] / (4.0 * ab[i]);
+        }
+        if (!(r2 > 0.0) || !std::isfinite(r2))
+            return fail(c, QCQPMI_EINVAL, "spectral_small_batch: rho^2 = sum beta^2 / (4 a) - gamma = %g of problem %lld is not positive and finite", r2, (long long)b);
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    Carve cv;
+    const size_t oP = cv.take((size_t)B * n * n * 8), oq = cv.take((size_t)B * n * 8), or0 = cv.take((size_t)B * 8), oa = cv.take((size_t)nagg * na * 8);
+    const size_t ox = cv.take((size_t)B * n * 8), olam = cv.take((size_t)B * n * 8), obd = cv.take((size_t)B * 8), omu = cv.take((size_t)B * 8);
+    const size_t osw = cv.take((size_t)B * 8), obr = cv.take((size_t)B * 4), ost = cv.take((size_t)B * 4);
+    const size_t oticket = cv.take(2 * sizeof(int));
+    HIPCHK(c, c->ss_work.reserve(c->stream, cv.off, false));
+    char *w = c->ss_work;
+    if ((rc = stage_in(c, w + oP, P0s, (size_t)B * n * n * 8)) || (rc = stage_in(c, w + oq, q0s, (size_t)B * n * 8)) ||
+        (rc = stage_in(c, w + or0, r0s, (size_t)B * 8)) || (rc = stage_in(c, w + oa, agg, (size_t)nagg * na * 8)))
+        return rc;
+    HIPCHK(c, hipMemsetAsync(w + oticket, 0, 2 * sizeof(int), c->stream));
+    SpectralSmallArgs a;
+    a.n = (int)n; a.B = B;
+    a.P0s = (const double *)(w + oP); a.q0s = (const double *)(w + oq); a.r0s = (const double *)(w + or0);
+    a.agg = (const double *)(w + oa); a.agg_stride = agg_stride;
+    a.relop_eq = relop_eq ? 1 : 0; a.max_sweeps = max_sweeps; a.tol = tol;
+    a.ticket = (int *)(w + oticket);
+    a.x = (double *)(w + ox); a.bound = (double *)(w + obd); a.mu = (double *)(w + omu); a.lam = (double *)(w + olam);
+    a.sweeps = (int64_t *)(w + osw); a.branch = (int *)(w + obr); a.status = (int *)(w + ost);
+    const int wgs = spectral_small_workgroups((int)n, B, c->device);
+    if (wgs < 1) return fail(c, QCQPMI_EHIP, "spectral_small_batch: occupancy query failed: %s", hipGetErrorString((hipError_t)(-wgs)));
+    const hipError_t qe = (hipError_t)spectral_small_launch(a, wgs, c->stream);
+    if (qe != hipSuccess) return fail(c, QCQPMI_EHIP, "spectral_small_batch: %s", hipGetErrorString(qe));
+    if ((rc = check_symmetric(c, w + oticket, "spectral_small_batch: an objective matrix P0_b is not symmetric (or holds a NaN)"))) return rc;
+    if (x) HIPCHK(c, hipMemcpyAsync(x, a.x, (size_t)B * n * 8, hipMemcpyDeviceToHost, c->stream));
+    if (bound) HIPCHK(c, hipMemcpyAsync(bound, a.bound, (size_t)B * 8, hipMemcpyDeviceToHost, c->stream));
+    if (mu) HIPCHK(c, hipMemcpyAsync(mu, a.mu, (size_t)B * 8, hipMemcpyDeviceToHost, c->stream));
+    if (lam) HIPCHK(c, hipMemcpyAsync(lam, a.lam, (size_t)B * n * 8, hipMemcpyDeviceToHost, c->stream));
+    if (sweeps) HIPCHK(c, hipMemcpyAsync(sweeps, a.sweeps, (size_t)B * 8, hipMemcpyDeviceToHost, c->stream));
+    if (branch) HIPCHK(c, hipMemcpyAsync(branch, a.branch, (size_t)B * 4, hipMemcpyDeviceToHost, c->stream));
+    if (status) HIPCHK(c, hipMemcpyAsync(status, a.status, (size_t)B * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, spin_sync(c->stream));
+    return 0;
+}
+
 // ---- improve(ADMM), R restarts each (admm_small.h); qcqpmi_last_cd_kernel is not touched either.  maxn: ADMM_SMALL_MAXN, or ADMM_WIDE_MAXN
 // for qcqpmi_admm_batch_run, whose problems of more than ADMM_SMALL_MAXN variables run the wide kernels
 int admm_small_batch(qcqpmi_ctx *c, int64_t maxn, int64_t B, const double *P0s, const double *q0s, const double *r0s, const double *cons,
@@ -408,6 +468,13 @@ int qcqpmi_sdr_batch_pc(qcqpmi_ctx *c, int64_t B, const double *P0s, const doubl
                         int max_sweeps, double tol, uint64_t seed, uint64_t seed_stride, uint64_t first_index, const double *V0s, double *V,
                         double *primal, double *y, int64_t *sweeps, double *X) {
     return sdr_small_batch(c, SDR_WIDE_MAXN, true, ds, B, P0s, q0s, r0s, S, max_sweeps, tol, seed, seed_stride, first_index, V0s, V, primal, y, sweeps, X);
+}
+
+// ---- suggest(SPECTRAL) for B small problems (n <= 64) whose constraints aggregate to one sphere or one ball (spectral_small.h)
+int qcqpmi_spectral_small_batch(qcqpmi_ctx *c, int64_t B, const double *P0s, const double *q0s, const double *r0s, const double *agg,
+                                int64_t agg_stride, int relop_eq, int max_sweeps, double tol, double *x, double *bound, double *mu, double *lam,
+                                int64_t *sweeps, int *branch, int *status) {
+    return spectral_small_batch(c, B, P0s, q0s, r0s, agg, agg_stride, relop_eq, max_sweeps, tol, x, bound, mu, lam, sweeps, branch, status);
 }
 
 }  // extern "C"

@@ -542,6 +542,33 @@ class Engine(object):
             self._chk(getattr(self.L, 'qcqpmi_' + name + '_pc')(self.h, B, _dp(P0s), _dp(q0s), _dp(r0s), _dp(ds), *tail))
         return out
 
+    def spectral_small_batch(self, P0s, q0s, r0s, agg, relop, max_sweeps=30, tol=1e-15):
+        """suggest(SPECTRAL) for B small problems (n <= 64) in ONE launch (qcqpmi_spectral_small_batch): P0s (B, n, n) symmetric,
+        q0s (B, n), r0s (B,); agg (2 n + 1,) = [a | beta | gamma] of the ONE constraint sum_i (a_i x_i^2 + beta_i x_i) + gamma (relop) 0
+        that every problem's constraints sum to, or (B, 2 n + 1): per problem; relop '==' or '<='.  Every problem's trust-region
+        problem is solved exactly: a Jacobi eigendecomposition (max_sweeps, tol: off(A) <= tol |A|_F) and one secular equation.
+        Returns a dictionary: x (B, n), bound (B,) = f0(x), mu (B,), lam (B, n) ascending, sweeps (B,), branch (B,) (0 interior, 1
+        boundary, 2 hard case), status (B,) (0; 1: Jacobi hit max_sweeps; 2: not finite).  The resident population is not touched."""
+        P0s = np.ascontiguousarray(P0s, dtype=np.float64)
+        q0s = np.ascontiguousarray(q0s, dtype=np.float64)
+        r0s = np.ascontiguousarray(r0s, dtype=np.float64).ravel()
+        agg = np.ascontiguousarray(agg, dtype=np.float64)
+        B, n = int(P0s.shape[0]) if P0s.ndim == 3 else 0, self.n
+        if P0s.shape != (B, n, n) or q0s.shape != (B, n) or r0s.shape != (B,):
+            raise ValueError('spectral_small_batch: expected P0s (B, n, n), q0s (B, n), r0s (B,) with n = %d' % n)
+        if agg.shape not in ((2 * n + 1,), (B, 2 * n + 1)):
+            raise ValueError('spectral_small_batch: expected agg of shape (2 n + 1,) or (B, 2 n + 1)')
+        if relop not in ('==', '<='):
+            raise ValueError("spectral_small_batch: relop must be '==' or '<='")
+        out = dict(x=np.empty((B, n)), bound=np.empty(B), mu=np.empty(B), lam=np.empty((B, n)), sweeps=np.zeros(B, dtype=np.int64),
+                   branch=np.zeros(B, dtype=np.int32), status=np.zeros(B, dtype=np.int32))
+        c_intp = C.POINTER(C.c_int)
+        self._chk(self.L.qcqpmi_spectral_small_batch(self.h, B, _dp(P0s), _dp(q0s), _dp(r0s), _dp(agg), 0 if agg.ndim == 1 else 2 * n + 1,
+                                                     1 if relop == '==' else 0, int(max_sweeps), float(tol), _dp(out['x']), _dp(out['bound']),
+                                                     _dp(out['mu']), _dp(out['lam']), _ip(out['sweeps']), out['branch'].ctypes.data_as(c_intp),
+                                                     out['status'].ctypes.data_as(c_intp)))
+        return out
+
     # ------------------------------------------------------------------ selection
     def select_best(self, tol=1e-4, want_x=True):
         idx = np.zeros(1, dtype=np.int64)

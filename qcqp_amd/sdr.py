@@ -537,6 +537,36 @@ def dual_certificate_general(form, y, yN):
 
 
 # ------------------------------------------------------------------------- spectral relaxation
+def certify_spectral_batch(P0s, q0s, agg, relop, x, mu):
+    """The optimality certificate of the batched spectral suggest (Engine.spectral_small_batch) on the host.  Problem b minimises
+    f0 = x'P0_b x + q0_b'x + r0_b subject to c_b(x) = sum_i (a_i x_i^2 + beta_i x_i) + gamma (relop) 0, agg = [a | beta | gamma] of
+    shape (2 n + 1,) (shared) or (B, 2 n + 1).  (x_b, mu_b) is a GLOBAL minimiser when c_b(x) == 0 (or <= 0), the gradient of
+    f0 + mu c vanishes, P0_b + mu_b diag(a_b) is positive semidefinite and, for '<=', mu_b >= 0 and mu_b c_b(x) == 0.  Returns a
+    dictionary of arrays of B: c (the constraint's value), feasibility (|c|, or its positive part for '<='), stationarity (max |2 P0 x +
+    q0 + mu (2 a x + beta)|), lambda_min (of P0_b + mu_b diag a_b: ONE batched eigvalsh, BLAS pools capped), and for '<=' mu_sign
+    (min(mu, 0)) and complementarity (|mu c|)."""
+    from . import _threads
+    P0s = np.asarray(P0s, dtype=np.float64)
+    q0s = np.asarray(q0s, dtype=np.float64)
+    x = np.asarray(x, dtype=np.float64)
+    mu = np.asarray(mu, dtype=np.float64)
+    B, n = q0s.shape
+    agg = np.broadcast_to(np.asarray(agg, dtype=np.float64), (B, 2 * n + 1))
+    a, beta, gamma = agg[:, :n], agg[:, n:2 * n], agg[:, 2 * n]
+    c = np.sum(a * x * x + beta * x, axis=1) + gamma
+    grad = 2. * np.einsum('bij,bj->bi', P0s, x) + q0s + mu[:, None] * (2. * a * x + beta)
+    H = 0.5 * (P0s + P0s.transpose(0, 2, 1))
+    idx = np.arange(n)
+    H[:, idx, idx] += mu[:, None] * a
+    with _threads.blas_limit():
+        lmin = np.linalg.eigvalsh(H)[:, 0]
+    out = dict(c=c, feasibility=np.abs(c) if relop == '==' else np.maximum(c, 0.), stationarity=np.max(np.abs(grad), axis=1), lambda_min=lmin)
+    if relop != '==':
+        out['mu_sign'] = np.minimum(mu, 0.)
+        out['complementarity'] = np.abs(mu * c)
+    return out
+
+
 def solve_spectral(form, device=0, seed=0):
     """solve_spectral (qcqp.py:41-70): the relaxation with ALL inequality constraints summed into one and all
     equality constraints summed into one,

@@ -1,0 +1,369 @@
+"""What tests/test_spectral_batch_cpu.py and tests/test_gpu_spectral_batch.py share (a plain module, no test in it).
+
+restate            spectral_small_kernel in NumPy, stage by stage (csrc/spectral_small.h): the same round-robin order and rotation
+                   formula (csrc/spectral_solve.h, csrc/jacobi_small.h), every wave sum in the order of wave_sum_tree, the sequential
+                   sums in ascending index order (NumPy has no fma: a sum differs from the kernel's in its last bits), the same
+                   secular rule and the same hard-case rule.
+independent        the same trust-region problem by numpy.linalg.eigh and a bracketed root (scipy's brentq), sharing nothing with
+                   the kernel but the mathematics.
+cases              the families and sizes of both test files.
+"""
+import functools
+
+import numpy as np
+import scipy.sparse as sp
+from scipy.optimize import brentq
+
+from qcqp_amd import problems
+
+HARD_THR = 2.0 ** -46
+SECULAR_RTOL = 2.0 ** -50
+SECULAR_MAX_ITERS = 200
+MAX_SWEEPS, TOL = 30, 1e-15
+SIZES = (1, 2, 3, 31, 32, 33, 63, 64)
+
+
+# ------------------------------------------------------------------ problem data
+def dense(P):
+    return np.asarray(P.toarray() if sp.issparse(P) else P, dtype=np.float64)
+
+
+def objectives(funcs_list):
+    P0s = np.stack([0.5 * (dense(f[0][0]) + dense(f[0][0]).T) for f in funcs_list])
+    q0s = np.stack([np.asarray(f[0][1], dtype=np.float64).ravel() for f in funcs_list])
+    r0s = np.array([float(f[0][2]) for f in funcs_list])
+    return P0s, q0s, r0s
+
+
+def aggregate(funcs):
+    """[a | beta | gamma] and the relop of ONE problem, straight from its constraint tuples."""
+    n = int(np.asarray(funcs[0][1]).size)
+    agg = np.zeros(2 * n + 1)
+    relops = set()
+    for P, q, r, relop in funcs[1:]:
+        agg[:n] += np.diag(dense(P))
+        agg[n:2 * n] += np.asarray(q, dtype=np.float64).ravel()
+        agg[2 * n] += float(r)
+        relops.add(relop)
+    assert len(relops) == 1
+    return agg, relops.pop()
+
+
+def scale_of(P0, q0, r0, agg):
+    """The scale of a problem as DESIGN 4.1i takes it: sum |P0| + sum |q0| + |r0|, times the largest squared end point of a
+    coordinate's feasible interval under the aggregated constraint if that is above 1."""
+    n = q0.size
+    a, beta, gamma = agg[:n], agg[n:2 * n], agg[2 * n]
+    rho = np.sqrt(np.sum(beta * beta / (4. * a)) - gamma)
+    ends = np.abs(np.concatenate([(-beta / (2. * a)) - rho / np.sqrt(a), (-beta / (2. * a)) + rho / np.sqrt(a)]))
+    return (np.abs(P0).sum() + np.abs(q0).sum() + abs(r0)) * max(1.0, float(np.max(ends)) ** 2)
+
+
+def f0(P0, q0, r0, x):
+    return float(x.dot(P0.dot(x)) + q0.dot(x) + r0)
+
+
+# ------------------------------------------------------------------ the restatement
+def tree_sum(v):
+    """wave_sum_tree over up to 64 values (the missing lanes hold 0.0): the binary tree over adjacent entries."""
+    t = np.zeros(64)
+    t[:len(v)] = v
+    while t.size > 1:
+        t = t[0::2] + t[1::2]
+    return float(t[0])
+
+
+def rotation(app, aqq, apq):
+    """jacobi_rotation for arrays of pairs: c, s, t."""
+    app, aqq, apq = (np.asarray(v, dtype=np.float64) for v in (app, aqq, apq))
+    on = apq != 0.0
+    with np.errstate(divide='ignore', invalid='ignore', over='ignore'):
+        theta = (aqq - app) / (2.0 * apq)
+        t = 1.0 / (np.abs(theta) + np.sqrt(theta * theta + 1.0))
+        t = np.where(theta < 0.0, -t, t)
+        c = 1.0 / np.sqrt(t * t + 1.0)
+        s = t * c
+    return np.where(on, c, 1.0), np.where(on, s, 0.0), np.where(on, t, 0.0)
+
+
+def round_robin_pair(n2, rnd, slot):
+    m = n2 - 1
+    a, b = (m, rnd) if slot == 0 else ((rnd + slot) % m, (rnd - slot + m) % m)
+    return (a, b) if a < b else (b, a)
+
+
+def jacobi(A, max_sweeps=MAX_SWEEPS, tol=TOL):
+    """jacobi_small on a copy of A (n x n, any n >= 1): (diagonal in the solver's order, Q with ROW k the eigenvector of entry k,
+    sweeps, converged).  The rotations of a round touch disjoint rows and columns, so they are applied at once."""
+    n = A.shape[0]
+    n2 = (n + 1) & ~1
+    As = np.zeros((n2, n2))
+    As[:n, :n] = A
+    Qs = np.eye(n2)
+    fro2 = tree_sum(_seq_colsum(As * As))
+    stop2 = tol * tol * fro2
+    rounds = [np.array([round_robin_pair(n2, r, k) for k in range(n2 // 2)]) for r in range(n2 - 1)]
+    sweeps, converged = 0, False
+    while True:
+        off = As * As
+        off[np.arange(n2), np.arange(n2)] = 0.0
+        off2 = tree_sum(_seq_colsum(off))
+        if off2 <= stop2:
+            converged = True
+            break
+        if sweeps >= max_sweeps or off2 != off2:
+            break
+        for pq in rounds:
+            p, q = pq[:, 0], pq[:, 1]
+            app, aqq, apq = As[p, p].copy(), As[q, q].copy(), As[p, q].copy()
+            c, s, t = rotation(app, aqq, apq)
+            cc, ss = c[:, None], s[:, None]
+            rp, rq = As[p, :].copy(), As[q, :].copy()
+            As[p, :], As[q, :] = cc * rp - ss * rq, ss * rp + cc * rq
+            vp, vq = Qs[p, :].copy(), Qs[q, :].copy()
+            Qs[p, :], Qs[q, :] = cc * vp - ss * vq, ss * vp + cc * vq
+            cp, cq = As[:, p].copy(), As[:, q].copy()
+            As[:, p], As[:, q] = c * cp - s * cq, s * cp + c * cq
+            on = s != 0.0
+            As[p[on], p[on]] = (app - t * apq)[on]
+            As[q[on], q[on]] = (aqq + t * apq)[on]
+            As[p[on], q[on]] = 0.0
+            As[q[on], p[on]] = 0.0
+        sweeps += 1
+    return np.diag(As)[:n].copy(), Qs[:n, :n].copy(), sweeps, converged
+
+
+def _seq_colsum(M):
+    """out[j] = sum_i M[i, j] in ascending i from 0.0 (lane = column)."""
+    out = np.zeros(M.shape[1])
+    for i in range(M.shape[0]):
+        out = out + M[i, :]
+    return out
+
+
+def _seq_matvec_rows(M, v):
+    """out[l] = sum_j M[l, j] v[j] in ascending j from 0.0, all l at once."""
+    out = np.zeros(M.shape[0])
+    for j in range(M.shape[1]):
+        out = out + M[:, j] * v[j]
+    return out
+
+
+def _w(gh, den):
+    with np.errstate(divide='ignore', invalid='ignore'):
+        return np.where(gh == 0.0, 0.0, gh / den)
+
+
+def secular_root(gh, d, rho, lo, hi):
+    rho2 = rho * rho
+    hi = max(hi, lo)
+    sigma, it = lo, 0
+    while True:
+        den = d + sigma
+        w = _w(gh, den)
+        psi = tree_sum(w * w)
+        with np.errstate(divide='ignore', invalid='ignore'):
+            T = tree_sum(np.where(w == 0.0, 0.0, w * w / den))
+        it += 1
+        sq = np.sqrt(psi)
+        if abs(sq - rho) <= SECULAR_RTOL * rho or it >= SECULAR_MAX_ITERS:
+            break
+        if psi > rho2:
+            lo = sigma
+        else:
+            hi = sigma
+        with np.errstate(divide='ignore', invalid='ignore'):
+            nxt = sigma + (psi / T) * ((sq - rho) / rho)
+        if not (nxt > lo and nxt < hi):
+            nxt = 0.5 * (lo + hi)
+        if nxt == sigma:
+            break
+        sigma = nxt
+    return sigma, it
+
+
+def restate(P0, q0, r0, agg, relop, max_sweeps=MAX_SWEEPS, tol=TOL):
+    """One problem as spectral_small_kernel solves it; a dictionary with the kernel's outputs (and y-space pieces for the tests)."""
+    n = q0.size
+    eq = relop == '=='
+    a, beta, gamma = agg[:n], agg[n:2 * n], agg[2 * n]
+    s = np.sqrt(a)
+    h = beta / (2.0 * a)
+    A = P0 / (s[:, None] * s[None, :])
+    ph = _seq_matvec_rows(P0.T, h)
+    rho2 = tree_sum(beta * beta / (4.0 * a)) - gamma
+    rho = np.sqrt(rho2)
+    g = (0.5 * q0 - ph) / s
+    lam, Q, sweeps, conv = jacobi(A, max_sweeps, tol)
+    gh = _seq_matvec_rows(Q, g)
+    order = np.lexsort((np.arange(n), lam))
+    kmin = int(order[0])
+    lam_min, lam_abs = float(lam[kmin]), float(np.max(np.abs(lam)))
+    d = lam - lam_min
+    g2 = tree_sum(gh * gh)
+    branch, sigma, tau, mu = 1, 0.0, 0.0, 0.0
+    interior = False
+    if not eq and lam_min > 0.0:
+        w = _w(gh, lam)
+        interior = tree_sum(w * w) <= rho2
+    if interior:
+        branch, w = 0, -w
+    else:
+        sigma_lo = lam_min if (not eq and lam_min > 0.0) else 0.0
+        hard = 0
+        if sigma_lo == 0.0:
+            inL = d <= HARD_THR * lam_abs
+            w0 = _w(gh, d)
+            wr = np.where(inL, 0.0, w0)
+            gL2 = tree_sum(np.where(inL, gh * gh, 0.0))
+            psi_reg, psi0 = tree_sum(wr * wr), tree_sum(w0 * w0)
+            if gL2 <= HARD_THR * HARD_THR * g2 and psi_reg <= rho2:
+                hard = 1
+            elif psi0 <= rho2:
+                hard = 2
+        if hard:
+            branch = 2
+            w = -(wr if hard == 1 else w0)
+            tau = np.sqrt(rho2 - (psi_reg if hard == 1 else psi0))
+        else:
+            lo = max(sigma_lo, float(np.max(np.abs(gh) / rho - d)))
+            sigma, _ = secular_root(gh, d, rho, lo, np.sqrt(g2) / rho)
+            w = -_w(gh, d + sigma)
+        mu = sigma - lam_min
+    y = _seq_matvec_rows(Q.T, w)
+    if branch == 2:
+        v = Q[kmin]
+        lead = v[int(np.argmax(np.abs(v)))]
+        y = y + (-tau if lead < 0.0 else tau) * v
+    x = (y - beta / (2.0 * s)) / s
+    px = _seq_matvec_rows(P0.T, x)
+    bound = tree_sum(x * (px + q0)) + r0
+    return dict(x=x, bound=bound, mu=mu, lam=lam[order], sweeps=sweeps, branch=branch, status=0 if conv else 1, y=y, rho=rho, A=A, g=g)
+
+
+# ------------------------------------------------------------------ the independent solver
+def independent(P0, q0, r0, agg, relop, eig=None):
+    """min f0(x) s.t. c(x) (relop) 0 by eigh and a bracketed root: dict(x, bound, mu, lam, branch).  eig: (lam, Q) of A = S^-1 P0 S^-1
+    where the caller has them already (tools/bench_spectral_batch.py takes them from ONE batched eigh)."""
+    n = q0.size
+    eq = relop == '=='
+    a, beta, gamma = agg[:n], agg[n:2 * n], agg[2 * n]
+    s = np.sqrt(a)
+    h = beta / (2.0 * a)
+    rho = float(np.sqrt(np.sum(beta * beta / (4.0 * a)) - gamma))
+    A = P0 / np.outer(s, s)
+    g = (0.5 * q0 - P0.dot(h)) / s
+    lam, Q = np.linalg.eigh(0.5 * (A + A.T)) if eig is None else eig
+    gh = Q.T.dot(g)
+    gn = float(np.linalg.norm(gh))
+
+    def norm_y(t, base):
+        with np.errstate(divide='ignore', invalid='ignore'):
+            return float(np.linalg.norm(np.where(gh == 0.0, 0.0, gh / (base + t))))
+
+    branch = 1
+    if not eq and lam[0] > 0.0 and norm_y(0.0, lam) <= rho:
+        branch, mu = 0, 0.0
+        yh = -gh / lam
+    else:
+        d = lam - lam[0]
+        t_min = lam[0] if (not eq and lam[0] > 0.0) else 0.0
+        t_lo = max(t_min, 1e-25 * gn / rho)
+        if gn == 0.0 or (t_min == 0.0 and norm_y(t_lo, d) <= rho):
+            branch, mu = 2, -lam[0]
+            keep = d > 1e-12 * max(1.0, float(np.max(np.abs(lam))))
+            if norm_y(t_lo, d) <= rho and gn > 0.0:
+                with np.errstate(divide='ignore', invalid='ignore'):
+                    yh = np.where(gh == 0.0, 0.0, -gh / (d + t_lo))
+            else:
+                yh = np.where(keep, -gh / np.where(keep, d, 1.0), 0.0)
+            tau = np.sqrt(max(rho * rho - float(yh.dot(yh)), 0.0))
+            e0 = np.zeros(n)
+            e0[0] = tau
+            yh = yh + e0
+        else:
+            t = brentq(lambda t: 1.0 / norm_y(t, d) - 1.0 / rho, t_lo, max(gn / rho * (1.0 + 1e-9), t_lo * 2.0), xtol=1e-300, rtol=8.9e-16, maxiter=1000)
+            mu = t - lam[0]
+            yh = -gh / (d + t)
+    y = Q.dot(yh)
+    x = (y - beta / (2.0 * s)) / s
+    return dict(x=x, bound=f0(P0, q0, r0, x), mu=mu, lam=lam, branch=branch)
+
+
+# ------------------------------------------------------------------ the families
+def _cons(n, lo, hi, relop):
+    out = []
+    for i in range(n):
+        qv = np.zeros(n)
+        qv[i] = -(lo + hi)
+        out.append((sp.csr_matrix(([1.0], ([i], [i])), shape=(n, n)), qv, float(lo * hi), relop))
+    return out
+
+
+def _pd(n, seed):
+    rs = np.random.RandomState(seed)
+    M = rs.randn(n + 2, n)
+    return M.T.dot(M) / n + 0.5 * np.eye(n)
+
+
+FAMILIES = ('bls', 'eqpp', 'maxcut', 'ident', 'nearhard', 'box11_in', 'box11_out', 'box01_in', 'box01_out', 'box11_indef', 'box01_indef',
+            'boxpp')
+# the point is unique and well conditioned: x is compared with the restatement's
+REGULAR = ('bls', 'eqpp', 'box11_in', 'box11_out', 'box01_in', 'box01_out', 'box11_indef', 'box01_indef', 'boxpp')
+
+
+def family(name, n, B, seed=3):
+    """B problems of the family: a list of funcs lists (objective first) for QCQPBatch."""
+    seeds = [seed + 17 * b for b in range(B)]
+    if name == 'bls':
+        return problems.boolean_least_squares_batch(B, n, n + n // 2 + 1, seed=seed)
+    if name in ('eqpp', 'boxpp'):
+        return problems.per_problem_constraints_batch(name, n, seeds)
+    if name == 'maxcut':      # (the complete graph up to n = 3: a graph without an edge has the objective 0, and a scale of 0)
+        p = 1.0 if n <= 3 else 0.5
+        cons = problems.maxcut(n, p, seed=seed)[0][1:]
+        return [[problems.maxcut(n, p, seed=sd)[0][0]] + cons for sd in seeds]
+    boolean = _cons(n, -1.0, 1.0, '==')
+    if name == 'ident':
+        return [[(np.eye(n), np.zeros(n), 0.25 * b, None)] + boolean for b in range(B)]
+    if name == 'nearhard':
+        out = []
+        for sd in seeds:
+            rs = np.random.RandomState(sd)
+            G = rs.randn(n, n)
+            P0 = 0.5 * (G + G.T)
+            lam, Q = np.linalg.eigh(P0)
+            q = 0.3 * rs.randn(n)
+            q = q - Q[:, 0] * Q[:, 0].dot(q) + 1e-9 * Q[:, 0]
+            out.append([(P0, q, 0.0, None)] + boolean)
+        return out
+    kind, where = name.split('_')
+    lo, hi = (-1.0, 1.0) if kind == 'box11' else (0.0, 1.0)
+    cons = _cons(n, lo, hi, '<=')
+    centre = 0.5 * (lo + hi)
+    if where == 'indef':
+        return [[problems.box_qp(n, seed=sd, lo=lo, hi=hi)[0][0]] + cons for sd in seeds]
+    out = []
+    for sd in seeds:
+        rs = np.random.RandomState(sd + 1000)
+        P0 = _pd(n, sd)
+        xs = centre + (0.2 * (hi - lo) * rs.uniform(-1.0, 1.0, size=n) if where == 'in' else 3.0 + rs.uniform(0.0, 1.0, size=n))
+        out.append([(P0, -2.0 * P0.dot(xs), float(xs.dot(P0.dot(xs))), None)] + cons)
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def case(name, n, B, seed=3):
+    """(funcs_list, P0s, q0s, r0s, aggs (B, 2 n + 1), relop, shared): shared says whether every problem has the same aggregate."""
+    fl = family(name, n, B, seed)
+    P0s, q0s, r0s = objectives(fl)
+    pairs = [aggregate(f) for f in fl]
+    aggs = np.stack([p[0] for p in pairs])
+    shared = all(np.array_equal(aggs[0], ag) for ag in aggs)
+    return fl, P0s, q0s, r0s, aggs, pairs[0][1], shared
+
+
+@functools.lru_cache(maxsize=None)
+def restated(name, n, B, seed=3):
+    fl, P0s, q0s, r0s, aggs, relop, _ = case(name, n, B, seed)
+    return [restate(P0s[b], q0s[b], r0s[b], aggs[b], relop) for b in range(B)]
