@@ -503,6 +503,18 @@ int qcqpmi_sdr_batch_pc(qcqpmi_ctx *ctx, int64_t B, const double *P0s, const dou
 int qcqpmi_spectral_small_batch(qcqpmi_ctx *ctx, int64_t B, const double *P0s, const double *q0s, const double *r0s,
                                 const double *agg, int64_t agg_stride, int relop_eq, int max_sweeps, double tol, double *x,
                                 double *bound, double *mu, double *lam, int64_t *sweeps, int *branch, int *status);
+/* THE SAME FOR 1 <= n <= 128 (added within ABI 6: a new symbol, nothing else changes): the arguments, outputs and status codes of
+ * qcqpmi_spectral_small_batch.  n <= 64 makes exactly its launch (same kernel, same bits).  65 <= n <= 128 launches
+ * spectral_wide_kernel (csrc/spectral_wide.h), still one wavefront per problem: A_b and Q_b together pass the LDS of a compute
+ * unit there, so the eigen-solver is shifted one-sided (Hestenes) Jacobi on ONE array G = A_b + 2 |A_b|_F I (csrc/jacobi_wide.h;
+ * a pair of columns is rotated where |g_p . g_q| > tol |g_p| |g_q|, the solver stops after the first sweep without a rotation
+ * or at max_sweeps; sweeps counts that last sweep), the columns of G end as Q_b, the eigenvalues are the Rayleigh quotients
+ * q_k' A_b q_k, and a lane holds two coordinates / eigen-indices.  The secular equation, the hard-case rule and the point are
+ * unchanged.  QCQPMI_EUNSUPPORTED: n > 128.  QCQPMI_EINVAL and the rest as for qcqpmi_spectral_small_batch, which still refuses
+ * n > 64. */
+int qcqpmi_spectral_batch(qcqpmi_ctx *ctx, int64_t B, const double *P0s, const double *q0s, const double *r0s, const double *agg,
+                          int64_t agg_stride, int relop_eq, int max_sweeps, double tol, double *x, double *bound, double *mu,
+                          double *lam, int64_t *sweeps, int *branch, int *status);
 /* IMPROVE(ADMM) FOR MANY SMALL PROBLEMS IN ONE LAUNCH (added within ABI 6: a new symbol, nothing else changes).  The batch of
  * qcqpmi_cd_small_batch_run -- B objectives P0s [B][n][n] (each symmetric), q0s [B][n], r0s [B] over this context's separable
  * constraint lists (up to four per coordinate, m >= 1 in all), 1 <= n <= 64 -- through improve_admm (qcqp.py:254-285): phase 1, x1 =

@@ -98,6 +98,8 @@ PROTOTYPES = [
                                       C.c_uint64, c_dp, c_dp, c_dp, c_dp, c_ip, c_dp]),
     ('qcqpmi_spectral_small_batch', C.c_int, [C.c_void_p, C.c_int64, c_dp, c_dp, c_dp, c_dp, C.c_int64, C.c_int, C.c_int, C.c_double, c_dp, c_dp,
                                               c_dp, c_dp, c_ip, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    ('qcqpmi_spectral_batch', C.c_int, [C.c_void_p, C.c_int64, c_dp, c_dp, c_dp, c_dp, C.c_int64, C.c_int, C.c_int, C.c_double, c_dp, c_dp,
+                                        c_dp, c_dp, c_ip, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     ('qcqpmi_cd_queue', C.c_int, [C.c_void_p, C.c_int]),
     ('qcqpmi_cd_life_version', C.c_int, [C.c_void_p, C.c_int]),
     ('qcqpmi_cd_set_objective_factor', C.c_int, [C.c_void_p, c_dp, C.c_int64]),

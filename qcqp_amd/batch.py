@@ -13,7 +13,8 @@ qcqpmi_sdr_small_batch; 64 < n <= 128, asked for with wide=True: ``Engine.sdr_ba
 packed in LDS) and publishes the certified bounds in ``sdr_bound``; improve() then starts from the samples.  suggest(SPECTRAL) --
 for constraints of ONE relop that sum to a sphere or a ball (Boolean, x_i^2 == d_i, MAXCUT, boxes), n <= 64 -- solves the reference's
 spectral relaxation of all B problems exactly in one launch (``Engine.spectral_small_batch``, qcqpmi_spectral_small_batch: one
-eigendecomposition and one secular equation per problem) and publishes ``spectral_sol`` and ``spectral_bound``.  Problem b's results are those of
+eigendecomposition and one secular equation per problem; 64 < n <= 128, asked for with wide=True: ``Engine.spectral_batch``,
+qcqpmi_spectral_batch, the wide kernel with ONE array of the eigen-solver in LDS) and publishes ``spectral_sol`` and ``spectral_bound``.  Problem b's results are those of
 ``QCQP(Problem(funcs_b))`` with suggest(RANDOM, num_samples=R, seed=seed + b seed_stride, first_index=...) followed by
 improve(COORD_DESCENT, ..., seed=seed + b seed_stride, first_index=...).  Problems whose constraints differ in their COEFFICIENTS
 only (boxes with bounds per instance, x_i^2 == d_{b,i}: problems.per_problem_constraints_batch) run through the same launches with
@@ -176,8 +177,10 @@ class QCQPBatch(object):
         (sdr.certify_batch, which logs the warning for problems that are not certified).  Sets .sdr_bound (B,) -- the rigorous lower bound, NaN where the problem is not certified -- and
         .sdr_info (primal, sweeps, lambda_min, converged); the samples are the starts of improve().
         wide=True admits 65 <= n <= 128 to SDR (``Engine.sdr_batch``: the wide kernel, C_b packed, two coordinates per lane in the
-        samples); n <= 64 runs as without it.  The default refuses n > 64 as before.  RANDOM ignores it.
-        SPECTRAL (n <= 64; constraints that all carry ONE relop and sum to sum_i (a_i x_i^2 + beta_i x_i) + gamma with every
+        samples) and to SPECTRAL (``Engine.spectral_batch``: the wide kernel, one-sided Jacobi on one array in LDS, two eigen-indices
+        per lane; jacobi_tol is then the relative threshold of a rotation); n <= 64 runs as without it.  The default refuses n > 64
+        as before.  RANDOM ignores it.
+        SPECTRAL (n <= 64, with wide=True n <= 128; constraints that all carry ONE relop and sum to sum_i (a_i x_i^2 + beta_i x_i) + gamma with every
         a_i > 0 and rho^2 = sum beta_i^2 / (4 a_i) - gamma > 0: Boolean, x_i^2 == d_i, MAXCUT, boxes (x - lo)(x - hi) <= 0 or == 0,
         shared or per problem): one launch (``Engine.spectral_small_batch``) solves the reference's spectral relaxation of every
         problem EXACTLY -- with one aggregated constraint it is a trust-region problem: one Jacobi eigendecomposition
@@ -191,7 +194,7 @@ class QCQPBatch(object):
         if int(num_samples) < 1:
             raise Exception("QCQPBatch.suggest: num_samples must be positive")
         if method == s.SPECTRAL:
-            return self._suggest_spectral(int(num_samples), seed, first_index, seed_stride, certify, jacobi_sweeps, jacobi_tol)
+            return self._suggest_spectral(int(num_samples), seed, first_index, seed_stride, certify, jacobi_sweeps, jacobi_tol, wide)
         if method == s.SDR:
             if self.n > MAX_N_SMALL and not wide:      # before any launch
                 raise Exception("QCQPBatch.suggest(SDR) is defined for n <= %d (n = %d) unless wide=True is given (n <= %d: the wide "
@@ -256,14 +259,16 @@ class QCQPBatch(object):
                             "admits at most one point)" % (name, rho2[b], where(b)))
         return (agg[0] if self.cons is None else agg), entries[0][1]
 
-    def _suggest_spectral(self, num_samples, seed, first_index, seed_stride, certify, jacobi_sweeps, jacobi_tol):
+    def _suggest_spectral(self, num_samples, seed, first_index, seed_stride, certify, jacobi_sweeps, jacobi_tol, wide=False):
         if num_samples != 1:
             raise Exception("QCQPBatch.suggest(SPECTRAL) yields one point per problem: num_samples must be 1 (num_samples = %d)" % num_samples)
-        if self.n > MAX_N_SMALL:      # before any launch
+        if self.n > MAX_N_SMALL and not wide:      # before any launch
             raise Exception("QCQPBatch.suggest(SPECTRAL) is defined for n <= %d (n = %d): A_b and Q_b of the eigen-solver fit a wavefront's "
-                            "LDS up to there; or use suggest(RANDOM), or QCQP per problem" % (MAX_N_SMALL, self.n))
+                            "LDS up to there, unless wide=True is given (n <= %d: the wide kernel, one array in LDS); or use "
+                            "suggest(RANDOM), or QCQP per problem" % (MAX_N_SMALL, self.n, MAX_N))
         agg, relop = self._spectral_aggregate()
-        out = self.engine.spectral_small_batch(self.P0s, self.q0s, self.r0s, agg, relop, max_sweeps=jacobi_sweeps, tol=jacobi_tol)
+        run = self.engine.spectral_small_batch if self.n <= MAX_N_SMALL else self.engine.spectral_batch
+        out = run(self.P0s, self.q0s, self.r0s, agg, relop, max_sweeps=jacobi_sweeps, tol=jacobi_tol)
         ok = out['status'] == 0
         self.spectral_sol = np.where(ok[:, None], out['x'], np.nan)
         self.spectral_bound = np.where(ok, out['bound'], np.nan)

@@ -1,5 +1,5 @@
 // Small-problem batch part of the C ABI: B small problems over the context's constraint structure in ONE
-// persistent launch of cd_small.hip, admm_small.hip, sdr_small.hip or spectral_small.hip.  A call works in a device buffer of its own
+// persistent launch of cd_small.hip, admm_small.hip, sdr_small.hip or spectral_small.hip (narrow and wide kernel).  A call works in a device buffer of its own
 // (sb_work for CD and ADMM, ss_work for SDR and SPECTRAL): the resident population, its evaluation, its status codes and an installed ADMM basis are not touched,
 // whether the call succeeds or is refused.  The shared steps come first; a driver is its argument struct, its launch and its outputs.
 // Host code only: the four launcher headers, and the launch of the core's selection kernel through capi_ctx.h.
@@ -11,6 +11,7 @@
 #include "admm_small.h"
 #include "sdr_small.h"
 #include "spectral_small.h"
+#include "spectral_wide.h"
 
 using namespace qcqpmi;
 
@@ -256,12 +257,14 @@ int sdr_small_batch(qcqpmi_ctx *c, int64_t maxn, bool per_problem, const double 
 
 // ---- suggest(SPECTRAL) for problems whose constraints aggregate to ONE sphere (relop_eq) or ONE ball: agg = [a (n) | beta (n) | gamma]
 // per problem (agg_stride = 2 n + 1) or shared (agg_stride = 0).  The context gives n, the device and the buffer; its constraints are not read.
-int spectral_small_batch(qcqpmi_ctx *c, int64_t B, const double *P0s, const double *q0s, const double *r0s, const double *agg, int64_t agg_stride,
+// maxn: SPECTRAL_SMALL_MAXN, or SPECTRAL_WIDE_MAXN for qcqpmi_spectral_batch, whose problems of more than SPECTRAL_SMALL_MAXN variables run the wide kernel
+int spectral_small_batch(qcqpmi_ctx *c, int64_t maxn, int64_t B, const double *P0s, const double *q0s, const double *r0s, const double *agg, int64_t agg_stride,
                          int relop_eq, int max_sweeps, double tol, double *x, double *bound, double *mu, double *lam, int64_t *sweeps,
                          int *branch, int *status) {
     int rc = check_ready(c, false);
     if (rc) return rc;
-    if (c->n > SPECTRAL_SMALL_MAXN) return fail(c, QCQPMI_EUNSUPPORTED, "spectral_small_batch: n = %lld, the small-problem kernel takes n <= %d (A_b and Q_b in LDS, one lane per eigenvalue)", (long long)c->n, SPECTRAL_SMALL_MAXN);
+    if (c->n > maxn) return fail(c, QCQPMI_EUNSUPPORTED, "spectral_small_batch: n = %lld, the small-problem kernel takes n <= %lld (%s)", (long long)c->n, (long long)maxn,
+                                 maxn > SPECTRAL_SMALL_MAXN ? "one array G_b in LDS, two eigenvalues per lane" : "A_b and Q_b in LDS, one lane per eigenvalue");
     const int64_t n = c->n, na = 2 * n + 1;
     if (B < 1 || B >= (1LL << 30) || max_sweeps < 0 || !(tol >= 0.0) || !P0s || !q0s || !r0s || !agg || (agg_stride != 0 && agg_stride != na))
         return fail(c, QCQPMI_EINVAL, "spectral_small_batch: bad B / max_sweeps / tol / agg_stride (0 or 2 n + 1), or a missing input array");
@@ -297,9 +300,10 @@ int spectral_small_batch(qcqpmi_ctx *c, int64_t B, const double *P0s, const doub
     a.ticket = (int *)(w + oticket);
     a.x = (double *)(w + ox); a.bound = (double *)(w + obd); a.mu = (double *)(w + omu); a.lam = (double *)(w + olam);
     a.sweeps = (int64_t *)(w + osw); a.branch = (int *)(w + obr); a.status = (int *)(w + ost);
-    const int wgs = spectral_small_workgroups((int)n, B, c->device);
+    const bool wide = n > SPECTRAL_SMALL_MAXN;
+    const int wgs = wide ? spectral_wide_workgroups((int)n, B, c->device) : spectral_small_workgroups((int)n, B, c->device);
     if (wgs < 1) return fail(c, QCQPMI_EHIP, "spectral_small_batch: occupancy query failed: %s", hipGetErrorString((hipError_t)(-wgs)));
-    const hipError_t qe = (hipError_t)spectral_small_launch(a, wgs, c->stream);
+    const hipError_t qe = (hipError_t)(wide ? spectral_wide_launch(a, wgs, c->stream) : spectral_small_launch(a, wgs, c->stream));
     if (qe != hipSuccess) return fail(c, QCQPMI_EHIP, "spectral_small_batch: %s", hipGetErrorString(qe));
     if ((rc = check_symmetric(c, w + oticket, "spectral_small_batch: an objective matrix P0_b is not symmetric (or holds a NaN)"))) return rc;
     if (x) HIPCHK(c, hipMemcpyAsync(x, a.x, (size_t)B * n * 8, hipMemcpyDeviceToHost, c->stream));
@@ -474,7 +478,14 @@ int qcqpmi_sdr_batch_pc(qcqpmi_ctx *c, int64_t B, const double *P0s, const doubl
 int qcqpmi_spectral_small_batch(qcqpmi_ctx *c, int64_t B, const double *P0s, const double *q0s, const double *r0s, const double *agg,
                                 int64_t agg_stride, int relop_eq, int max_sweeps, double tol, double *x, double *bound, double *mu, double *lam,
                                 int64_t *sweeps, int *branch, int *status) {
-    return spectral_small_batch(c, B, P0s, q0s, r0s, agg, agg_stride, relop_eq, max_sweeps, tol, x, bound, mu, lam, sweeps, branch, status);
+    return spectral_small_batch(c, SPECTRAL_SMALL_MAXN, B, P0s, q0s, r0s, agg, agg_stride, relop_eq, max_sweeps, tol, x, bound, mu, lam, sweeps, branch, status);
+}
+
+// ---- the same for 1 <= n <= 128: the launch above for n <= 64, the wide kernel (spectral_wide_kernel, spectral_wide.h) past it
+int qcqpmi_spectral_batch(qcqpmi_ctx *c, int64_t B, const double *P0s, const double *q0s, const double *r0s, const double *agg, int64_t agg_stride,
+                          int relop_eq, int max_sweeps, double tol, double *x, double *bound, double *mu, double *lam, int64_t *sweeps, int *branch,
+                          int *status) {
+    return spectral_small_batch(c, SPECTRAL_WIDE_MAXN, B, P0s, q0s, r0s, agg, agg_stride, relop_eq, max_sweeps, tol, x, bound, mu, lam, sweeps, branch, status);
 }
 
 }  // extern "C"

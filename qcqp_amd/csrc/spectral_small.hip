@@ -190,3 +190,33 @@ int spectral_small_launch(const SpectralSmallArgs &a, int wgs, hipStream_t st) {
 }
 
 }  // namespace qcqpmi
+
+// ---- the wide kernel (65 <= n <= 128, spectral_wide.h): same unit, the kernel in a file of its own
+#include "spectral_wide_kernel.h"
+
+namespace qcqpmi {
+
+size_t spectral_wide_lds_bytes(int n) {
+    const int n2 = (n + 1) & ~1;
+    return (jacobi_wide_doubles(n2) + SPW_VECS * SPW_VEC) * sizeof(double);
+}
+
+int spectral_wide_workgroups(int n, int64_t B, int device) {
+    int per = 0;
+    const size_t lds = spectral_wide_lds_bytes(n);
+    hipError_t e = hipFuncSetAttribute((const void *)spectral_wide_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return -(int)e;
+    e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, (const void *)spectral_wide_kernel, 64, lds);
+    if (e != hipSuccess) return -(int)e;
+    return small_workgroup_cap(device, per, B);
+}
+
+int spectral_wide_launch(const SpectralSmallArgs &a, int wgs, hipStream_t st) {
+    const size_t lds = spectral_wide_lds_bytes(a.n);
+    const hipError_t e = hipFuncSetAttribute((const void *)spectral_wide_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return (int)e;
+    hipLaunchKernelGGL(spectral_wide_kernel, dim3((unsigned)wgs), dim3(64), lds, st, a);
+    return (int)hipGetLastError();
+}
+
+}  // namespace qcqpmi

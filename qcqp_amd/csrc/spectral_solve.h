@@ -3,6 +3,7 @@
 // side), so that a host program can drive them: tests/host/spectral_selftest.cpp.
 //
 //   jacobi_rotation     the rotation that annihilates a_pq of a symmetric 2 x 2 block
+//   hestenes_rotation   the rotation that makes two columns orthogonal (one-sided Jacobi, jacobi_wide.h), behind its threshold
 //   round_robin_pair    the pair of (round, slot) in the cyclic ordering: n2 / 2 disjoint pairs per round, every pair once per sweep
 //   tree_sum64          the order of wave_sum_tree (dev_util.h) over an array of 64
 //   secular_root        the root of  psi(sigma) = sum_k gh_k^2 / (d_k + sigma)^2 = rho^2  by a safeguarded Newton iteration
@@ -60,6 +61,18 @@ SPS_FN JacobiRot jacobi_rotation(double app, double aqq, double apq) {
     r.s = t * r.c;
     r.t = t;
     return r;
+}
+
+// The rotation of ONE-SIDED (Hestenes) Jacobi on two columns g_p, g_q (p < q) of G, from alpha = g_p . g_p, beta = g_q . g_q and
+// gamma = g_p . g_q:  (g_p, g_q) <- (c g_p - s g_q, s g_p + c g_q) makes the columns orthogonal and keeps alpha + beta.  It is
+// jacobi_rotation of the 2 x 2 Gram block [[alpha, gamma], [gamma, beta]] (theta = (beta - alpha) / (2 gamma); theta == 0: t = 1)
+// behind a relative threshold: the pair is rotated only where |gamma| > tol sqrt(alpha) sqrt(beta) (the two roots apart: the product
+// alpha beta may overflow or underflow where its root does not).  Otherwise -- gamma == 0, or a NaN among the three -- the identity
+// with s == 0 exactly, which the caller reads as "not rotated".
+SPS_FN JacobiRot hestenes_rotation(double alpha, double beta, double gamma, double tol) {
+    const JacobiRot id = {1.0, 0.0, 0.0};
+    if (!(fabs(gamma) > tol * (sqrt(alpha) * sqrt(beta)))) return id;
+    return jacobi_rotation(alpha, beta, gamma);
 }
 
 // The circle method over n2 players (n2 even, >= 2), m = n2 - 1: in round r (0 <= r < m) slot 0 pairs player m with player r and

@@ -549,24 +549,35 @@ class Engine(object):
         problem is solved exactly: a Jacobi eigendecomposition (max_sweeps, tol: off(A) <= tol |A|_F) and one secular equation.
         Returns a dictionary: x (B, n), bound (B,) = f0(x), mu (B,), lam (B, n) ascending, sweeps (B,), branch (B,) (0 interior, 1
         boundary, 2 hard case), status (B,) (0; 1: Jacobi hit max_sweeps; 2: not finite).  The resident population is not touched."""
+        return self._spectral_batch('spectral_small_batch', P0s, q0s, r0s, agg, relop, max_sweeps, tol)
+
+    def spectral_batch(self, P0s, q0s, r0s, agg, relop, max_sweeps=30, tol=1e-15):
+        """spectral_small_batch for problems of up to 128 variables (qcqpmi_spectral_batch): the same arguments, the same dictionary.
+        n <= 64 runs exactly the launch of spectral_small_batch (same kernel, same bits); 65 <= n <= 128 runs spectral_wide_kernel:
+        one wavefront per problem, one-sided Jacobi on ONE array G_b = A_b + 2 |A_b|_F I in LDS (tol: a pair of columns rotates
+        where |g_p . g_q| > tol |g_p| |g_q|; sweeps counts the last sweep, without a rotation), the eigenvalues as Rayleigh
+        quotients, two eigen-indices per lane."""
+        return self._spectral_batch('spectral_batch', P0s, q0s, r0s, agg, relop, max_sweeps, tol)
+
+    def _spectral_batch(self, name, P0s, q0s, r0s, agg, relop, max_sweeps, tol):
         P0s = np.ascontiguousarray(P0s, dtype=np.float64)
         q0s = np.ascontiguousarray(q0s, dtype=np.float64)
         r0s = np.ascontiguousarray(r0s, dtype=np.float64).ravel()
         agg = np.ascontiguousarray(agg, dtype=np.float64)
         B, n = int(P0s.shape[0]) if P0s.ndim == 3 else 0, self.n
         if P0s.shape != (B, n, n) or q0s.shape != (B, n) or r0s.shape != (B,):
-            raise ValueError('spectral_small_batch: expected P0s (B, n, n), q0s (B, n), r0s (B,) with n = %d' % n)
+            raise ValueError('%s: expected P0s (B, n, n), q0s (B, n), r0s (B,) with n = %d' % (name, n))
         if agg.shape not in ((2 * n + 1,), (B, 2 * n + 1)):
-            raise ValueError('spectral_small_batch: expected agg of shape (2 n + 1,) or (B, 2 n + 1)')
+            raise ValueError('%s: expected agg of shape (2 n + 1,) or (B, 2 n + 1)' % name)
         if relop not in ('==', '<='):
-            raise ValueError("spectral_small_batch: relop must be '==' or '<='")
+            raise ValueError("%s: relop must be '==' or '<='" % name)
         out = dict(x=np.empty((B, n)), bound=np.empty(B), mu=np.empty(B), lam=np.empty((B, n)), sweeps=np.zeros(B, dtype=np.int64),
                    branch=np.zeros(B, dtype=np.int32), status=np.zeros(B, dtype=np.int32))
         c_intp = C.POINTER(C.c_int)
-        self._chk(self.L.qcqpmi_spectral_small_batch(self.h, B, _dp(P0s), _dp(q0s), _dp(r0s), _dp(agg), 0 if agg.ndim == 1 else 2 * n + 1,
-                                                     1 if relop == '==' else 0, int(max_sweeps), float(tol), _dp(out['x']), _dp(out['bound']),
-                                                     _dp(out['mu']), _dp(out['lam']), _ip(out['sweeps']), out['branch'].ctypes.data_as(c_intp),
-                                                     out['status'].ctypes.data_as(c_intp)))
+        self._chk(getattr(self.L, 'qcqpmi_' + name)(self.h, B, _dp(P0s), _dp(q0s), _dp(r0s), _dp(agg), 0 if agg.ndim == 1 else 2 * n + 1,
+                                                    1 if relop == '==' else 0, int(max_sweeps), float(tol), _dp(out['x']), _dp(out['bound']),
+                                                    _dp(out['mu']), _dp(out['lam']), _ip(out['sweeps']), out['branch'].ctypes.data_as(c_intp),
+                                                    out['status'].ctypes.data_as(c_intp)))
         return out
 
     # ------------------------------------------------------------------ selection

@@ -10,6 +10,8 @@ Workload: problems.boolean_least_squares_batch(B, n, m); the launch at its defau
   loop       what the library offered before: sdr.solve_spectral per problem (an auxiliary context, the general Burer-Monteiro /
              augmented-Lagrangian solver, eigh of X).  Timed on the first --loop-problems problems and SCALED LINEARLY to B (every
              problem costs the same work; stated as such in the output).
+--wide: the same three columns for 65 <= n <= 128 through Engine.spectral_batch (qcqpmi_spectral_batch, spectral_wide_kernel); the
+defaults become B = 1024, n = 128, m = 192.
 Prints one JSON line (with the sweeps per problem, the branches taken and the largest relative difference of the bounds).
 """
 import argparse
@@ -25,13 +27,17 @@ sys.path.insert(0, os.path.join(REPO, 'tests'))
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument('--B', type=int, default=4096)
-    ap.add_argument('--n', type=int, default=32)
-    ap.add_argument('--m', type=int, default=48)
+    ap.add_argument('--wide', action='store_true', help='qcqpmi_spectral_batch (n <= 128); defaults B = 1024, n = 128, m = 192')
+    ap.add_argument('--B', type=int, default=None)
+    ap.add_argument('--n', type=int, default=None)
+    ap.add_argument('--m', type=int, default=None)
     ap.add_argument('--repeat', type=int, default=5)
     ap.add_argument('--loop-problems', type=int, default=16)
     ap.add_argument('--seed', type=int, default=1)
     args = ap.parse_args()
+    for key, narrow, wide in (('B', 4096, 1024), ('n', 32, 128), ('m', 48, 192)):
+        if getattr(args, key) is None:
+            setattr(args, key, wide if args.wide else narrow)
 
     import numpy as np
     import spectral_batch_cases as sc
@@ -45,10 +51,11 @@ def main():
     fl = problems.boolean_least_squares_batch(args.B, args.n, args.m, seed=args.seed)
     qb = QCQPBatch(fl)
     agg, relop = qb._spectral_aggregate()
+    launch = qb.engine.spectral_batch if args.wide else qb.engine.spectral_small_batch
 
     def batched():
         t0 = time.perf_counter()
-        o = qb.engine.spectral_small_batch(qb.P0s, qb.q0s, qb.r0s, agg, relop)
+        o = launch(qb.P0s, qb.q0s, qb.r0s, agg, relop)
         return time.perf_counter() - t0, o
 
     batched()                                       # warm-up: code object, buffers
@@ -80,7 +87,7 @@ def main():
     t_loop, single = loop(nl)
     rel = lambda a, b: float(np.max(np.abs(np.asarray(a) - np.asarray(b)) / (1.0 + np.abs(np.asarray(b)))))
     print(json.dumps(dict(
-        workload=dict(B=args.B, n=args.n, m=args.m, max_sweeps=30, tol=1e-15), kernel='spectral_small_kernel',
+        workload=dict(B=args.B, n=args.n, m=args.m, max_sweeps=30, tol=1e-15), kernel='spectral_wide_kernel' if args.wide and args.n > 64 else 'spectral_small_kernel',
         batched_s=t_batched, batched_all_s=[r[0] for r in runs], host_s=t_host, host_eigh_s=t_eigh, host_all_s=[r[0] for r in hruns],
         speedup_over_host=t_host / t_batched, speedup_over_host_eigh_alone=t_eigh / t_batched,
         status_ok='%d/%d' % (int(np.sum(o['status'] == 0)), args.B), sweeps_mean=float(np.mean(o['sweeps'])), sweeps_max=int(np.max(o['sweeps'])),
