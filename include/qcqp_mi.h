@@ -571,6 +571,35 @@ int qcqpmi_admm_batch_run(qcqpmi_ctx *ctx, int64_t B, const double *P0s, const d
                           int64_t num_iters, double tol, double viol_lim, uint64_t seed, uint64_t seed_stride, uint64_t first_index,
                           double select_tol, int64_t *iters1, int64_t *iters2, double *f0, double *maxviol, double *X,
                           int64_t *best_index, double *best_f0, double *best_maxviol, double *best_x);
+/* THE SETUP OF THE TWO CALLS ABOVE ON THE DEVICE (added within ABI 6: a new symbol, nothing else changes).  rhos and Minvs of
+ * qcqpmi_admm_small_batch_run / qcqpmi_admm_batch_run for B problems over this context (n, m = its number of constraints, its device),
+ * 1 <= n <= 128, from ONE symmetric eigendecomposition P0_b = sum_k lam_k u_k u_k' per problem inside ONE persistent launch
+ * (csrc/admm_setup.h: admm_setup_kernel for n <= 64 -- cyclic Jacobi, A and Q in LDS --, admm_setup_wide_kernel for 65 <= n <= 128 --
+ * shifted one-sided Jacobi on one array, eigenvalues as Rayleigh quotients; one wavefront per problem, max_sweeps and tol as
+ * qcqpmi_spectral_batch passes them to the same two solvers):
+ *   lambda_min[b] = min_k lam_k;
+ *   rhos[b]       = rho == NULL: the rule of qcqp.py:270-277 applied to lambda_min[b], in the caller's order of operations --
+ *                   lambda_min < 0 ? 50 * ((2 * (1 - lambda_min)) / m) : 50 * (1 / m) -- bit for bit (so a P0_b whose eigenvalues the
+ *                   solver finds exactly, diagonal or zero, gets the bits of a host that applies the rule to LAPACK's lambda_min);
+ *                   else *rho, the caller's penalty for every problem;
+ *   Minvs[b]      = sum_k u_k u_k' / (2 (lam_k + rhos[b] m)) = (2 (P0_b + rhos[b] m I))^-1, every entry summed in ascending k of the
+ *                   solver's order with the product u_ik u_jk formed first: EXACTLY symmetric, as the two run calls require;
+ *   sweeps[b]     = Jacobi sweeps;
+ *   status[b]     = 0; 1: Jacobi stopped at max_sweeps; 2: lambda_min, rho or an entry of the inverse is not finite; 3: the given
+ *                   rho is too small (lambda_min[b] + m rho < 0: the reference's test; Minvs[b] is then all zero).  A rho that is
+ *                   too small is NOT an error of the call: the caller words the reference's message from lambda_min[b].
+ * The rule jumps by a factor of about two at lambda_min = 0; for a singular positive semidefinite P0_b rounding decides the branch,
+ * here as in LAPACK.  The contract: rhos[b] is the rule applied to the reported lambda_min[b], and lambda_min[b] agrees with LAPACK's
+ * to rounding (a small multiple of eps |P0_b|_F).
+ * A result depends on (P0_b, m, the rho argument, max_sweeps, tol) alone -- not on B, the neighbours, the order of the problems or
+ * the workgroups: bit for bit.  Any output may be NULL.
+ * Refusals, before any launch where the host can see them; the resident population, its evaluation, an installed ADMM basis,
+ * qcqpmi_last_cd_kernel and qcqpmi_last_admm_kernel stay as they were, whether the call succeeds or is refused.
+ * QCQPMI_EUNSUPPORTED: n > 128, constraints that are not separable (as the run calls).  QCQPMI_EINVAL: B < 1 (or >= 2^30), P0s
+ * missing, max_sweeps < 1, tol not positive and finite, a given rho that is not positive and finite, no constraint (m < 1), a P0_b
+ * that is not symmetric or holds a NaN (found while staging: the call fails after its launch and returns no results). */
+int qcqpmi_admm_batch_setup(qcqpmi_ctx *ctx, int64_t B, const double *P0s, const double *rho, int max_sweeps, double tol, double *rhos,
+                            double *lambda_min, double *Minvs, int64_t *sweeps, int *status);
 /* Device and pinned-host buffers for a qcqpmi_cd_stream_run(K, R) to come (population, per-restart outputs, per-population
  * winners; with an objective factor set, the buffers of the factored kernel's pre-passes: slacks and Y0 = L^T x0): allocation only, so that a timed or latency-sensitive run does not start with hipMalloc / hipHostMalloc.  A
  * resident population smaller than K R points is dropped (like any reallocation of the population). */

@@ -88,6 +88,7 @@ PROTOTYPES = [
     ('qcqpmi_admm_batch_run', C.c_int, [C.c_void_p, C.c_int64, c_dp, c_dp, c_dp, c_dp, c_dp, c_dp, C.c_int64, C.c_int, c_dp, C.c_int, C.c_int64,
                                         C.c_double, C.c_double, C.c_uint64, C.c_uint64, C.c_uint64, C.c_double, c_ip, c_ip, c_dp, c_dp, c_dp,
                                         c_ip, c_dp, c_dp, c_dp]),
+    ('qcqpmi_admm_batch_setup', C.c_int, [C.c_void_p, C.c_int64, c_dp, c_dp, C.c_int, C.c_double, c_dp, c_dp, c_dp, c_ip, C.POINTER(C.c_int)]),
     ('qcqpmi_sdr_small_batch', C.c_int, [C.c_void_p, C.c_int64, c_dp, c_dp, c_dp, C.c_int64, C.c_int, C.c_double, C.c_uint64, C.c_uint64,
                                          C.c_uint64, c_dp, c_dp, c_dp, c_dp, c_ip, c_dp]),
     ('qcqpmi_sdr_small_batch_pc', C.c_int, [C.c_void_p, C.c_int64, c_dp, c_dp, c_dp, c_dp, C.c_int64, C.c_int, C.c_double, C.c_uint64, C.c_uint64,

@@ -7,7 +7,8 @@ kernel (``Engine.cd_small_batch_run``, qcqpmi_cd_small_batch_run; for 64 < n <= 
 wide kernels, two coordinates per lane).  improve(ADMM) runs the reference's consensus ADMM for all B x R restarts in one launch too
 (n <= 64: ``Engine.admm_small_batch_run``, qcqpmi_admm_small_batch_run; 64 < n <= 128, asked for with wide=True:
 ``Engine.admm_batch_run``, qcqpmi_admm_batch_run, wide kernels again), with rho per problem by the reference's rule and
-(2 (P0_b + rho_b m I))^-1 from one batched host inverse.  suggest(SDR) -- for constraints x_i^2 == d_i -- solves the
+(2 (P0_b + rho_b m I))^-1 from one batched host inverse -- or, with setup='device', both from one eigendecomposition per problem in
+one more launch (``Engine.admm_batch_setup``, qcqpmi_admm_batch_setup).  suggest(SDR) -- for constraints x_i^2 == d_i -- solves the
 semidefinite relaxation of all B problems and draws their samples in one launch as well (n <= 64: ``Engine.sdr_small_batch``,
 qcqpmi_sdr_small_batch; 64 < n <= 128, asked for with wide=True: ``Engine.sdr_batch``, qcqpmi_sdr_batch, the wide kernel with C_b
 packed in LDS) and publishes the certified bounds in ``sdr_bound``; improve() then starts from the samples.  suggest(SPECTRAL) --
@@ -97,10 +98,14 @@ def admm_rhos(P0s, m, rho=None):
         rho = float(rho)
         bad = np.nonzero(lmin + m * rho < 0)[0]
         if bad.size:
-            raise Exception("rho parameter is too small, need at least %.3f. (problem %d: minimum possible value %.3f)"
-                            % (rho, int(bad[0]), -lmin[bad[0]] / m))
+            raise Exception(rho_too_small_message(rho, bad[0], lmin[bad[0]], m))
         return np.full(P0s.shape[0], rho)
     return 50. * np.where(lmin < 0, 2. * (1. - lmin) / m, 1. / m)
+
+
+def rho_too_small_message(rho, b, lmin_b, m):
+    """The reference's exception text for a given rho that is too small, naming problem b (lmin_b: its lambda_min)."""
+    return ("rho parameter is too small, need at least %.3f. (problem %d: minimum possible value %.3f)" % (rho, int(b), -lmin_b / m))
 
 
 def admm_minvs(P0s, rhos, m):
@@ -279,7 +284,7 @@ class QCQPBatch(object):
         self._suggested = (1, int(seed), int(first_index), int(seed_stride))
 
     def improve(self, method=s.COORD_DESCENT, num_iters=1000, viol_tol=1e-2, tol=None, phase1=True, seed=None, viol_lim=1e4, rho=None,
-                wide=False):
+                wide=False, setup='host'):
         """improve(COORD_DESCENT) or improve(ADMM) of every suggested start of every problem; returns (f (B,), v (B,)) of the best
         restart per problem (QCQPForm.better, ties -> lowest index) and sets .x (B, n), .population_f / .population_v (B, R),
         .best_index, .last_stats.  seed: the seed of suggest() (a problem's normals and its draws come from ONE keyed stream).
@@ -288,9 +293,17 @@ class QCQPBatch(object):
         improve_admm.  rho == None: the reference's rule (qcqp.py:270-277) problem by problem; a given rho that is too small for some
         problem raises the reference's message.  .last_stats holds rho (B,), iters1, iters2 (B, R) and the kernel's name.
         wide=True admits 65 <= n <= 128 to ADMM (``Engine.admm_batch_run``: the wide kernels, two coordinates per lane); n <= 64 runs
-        as without it.  The default refuses n > 64 as before.  COORD_DESCENT ignores it."""
+        as without it.  The default refuses n > 64 as before.  COORD_DESCENT ignores it.
+        setup (ADMM): where rho_b and (2 (P0_b + rho_b m I))^-1 come from.  'host' (the default): one batched eigvalsh and one batched
+        inverse (admm_rhos, admm_minvs).  'device': ``Engine.admm_batch_setup`` -- one launch, one Jacobi eigendecomposition per
+        problem -- and then the same ADMM launch with its rho and its inverse; the rule is applied to the device's lambda_min, which
+        agrees with eigvalsh to rounding (for a singular PSD P0_b rounding decides the rule's branch, here as on the host); a problem
+        whose decomposition did not converge or is not finite raises.  .last_stats gains setup, lambda_min and setup_sweeps (None
+        on the host path).  setup='device' does not admit n > 64 by itself (wide=True does).  COORD_DESCENT ignores it."""
         if method not in (s.COORD_DESCENT, s.ADMM):
             raise Exception("QCQPBatch.improve is defined for the COORD_DESCENT and ADMM methods")
+        if method == s.ADMM and setup not in ('host', 'device'):      # before any launch
+            raise Exception("QCQPBatch.improve(ADMM): setup must be 'host' or 'device' (setup = %r)" % (setup,))
         if method == s.ADMM and self.n > MAX_N_SMALL and not wide:      # before any launch
             raise Exception("QCQPBatch.improve(ADMM) is defined for n <= %d (n = %d) unless wide=True is given (n <= %d: the wide kernels, "
                             "two coordinates per lane); or use improve(COORD_DESCENT), or QCQP per problem" % (MAX_N_SMALL, self.n, MAX_N))
@@ -301,7 +314,7 @@ class QCQPBatch(object):
             raise Exception("QCQPBatch.improve: seed %d differs from the seed of suggest (%d); the batch runs one keyed stream per problem"
                             % (int(seed), sd))
         if method == s.ADMM:
-            return self._improve_admm(R, sd, first_index, stride, num_iters, 1e-2 if tol is None else tol, viol_lim, rho, phase1)
+            return self._improve_admm(R, sd, first_index, stride, num_iters, 1e-2 if tol is None else tol, viol_lim, rho, phase1, setup)
         tol = 1e-4 if tol is None else tol
         run = self.engine.cd_small_batch_run if self.n <= MAX_N_SMALL else self.engine.cd_batch_run
         out = run(self.P0s, self.q0s, self.r0s, R, X0=self._starts, phase1=phase1, num_iters=num_iters, viol_tol=viol_tol,
@@ -317,13 +330,33 @@ class QCQPBatch(object):
         self.last_stats = dict(out, method=method, num_problems=self.B, num_restarts=R, **stats)
         return out['best_f0'], out['best_maxviol']
 
-    def _improve_admm(self, R, sd, first_index, stride, num_iters, tol, viol_lim, rho, phase1):
+    def _admm_setup_device(self, m, rho):
+        """(rhos, Minvs, lambda_min, sweeps) from Engine.admm_batch_setup; raises what admm_rhos raises for a rho that is too small,
+        and for a decomposition that cannot be used."""
+        out = self.engine.admm_batch_setup(self.P0s, rho=rho)
+        short = np.nonzero(out['status'] == 3)[0]
+        if short.size:
+            raise Exception(rho_too_small_message(float(rho), short[0], out['lambda_min'][short[0]], m))
+        failed = np.nonzero(out['status'] != 0)[0]
+        if failed.size:
+            b = int(failed[0])
+            raise Exception("QCQPBatch.improve(ADMM, setup='device'): the eigendecomposition of P0 of problem %d %s (status %d, %d "
+                            "sweeps); its inverse is not used -- setup='host' takes LAPACK's"
+                            % (b, "did not converge" if out['status'][b] == 1 else "is not finite", int(out['status'][b]), int(out['sweeps'][b])))
+        return out['rho'], out['Minv'], out['lambda_min'], out['sweeps']
+
+    def _improve_admm(self, R, sd, first_index, stride, num_iters, tol, viol_lim, rho, phase1, setup='host'):
         m = self.form.m
-        rhos = admm_rhos(self.P0s, m, rho)
+        if setup == 'device':
+            rhos, minvs, lmin, sweeps = self._admm_setup_device(m, rho)
+        else:
+            rhos = admm_rhos(self.P0s, m, rho)
+            minvs, lmin, sweeps = admm_minvs(self.P0s, rhos, m), None, None
         run = self.engine.admm_small_batch_run if self.n <= MAX_N_SMALL else self.engine.admm_batch_run
-        out = run(self.P0s, self.q0s, self.r0s, R, rhos, admm_minvs(self.P0s, rhos, m), X0=self._starts, phase1=phase1, num_iters=num_iters,
+        out = run(self.P0s, self.q0s, self.r0s, R, rhos, minvs, X0=self._starts, phase1=phase1, num_iters=num_iters,
                   tol=tol, viol_lim=viol_lim, seed=sd, seed_stride=stride, first_index=first_index, want_x=False, cons=self.cons)
-        return self._publish(out, s.ADMM, R, rho=rhos, kernel=self.engine.last_admm_kernel()[0])
+        return self._publish(out, s.ADMM, R, rho=rhos, kernel=self.engine.last_admm_kernel()[0], setup=setup, lambda_min=lmin,
+                             setup_sweeps=sweeps)
 
     def close(self):
         self.engine.close()

@@ -1,8 +1,8 @@
 // Small-problem batch part of the C ABI: B small problems over the context's constraint structure in ONE
-// persistent launch of cd_small.hip, admm_small.hip, sdr_small.hip or spectral_small.hip (narrow and wide kernel).  A call works in a device buffer of its own
-// (sb_work for CD and ADMM, ss_work for SDR and SPECTRAL): the resident population, its evaluation, its status codes and an installed ADMM basis are not touched,
+// persistent launch of cd_small.hip, admm_small.hip, sdr_small.hip or spectral_small.hip (narrow and wide kernel; the ADMM setup kernels live there too).  A call works in a device buffer of its own
+// (sb_work for CD and ADMM, ss_work for SDR, SPECTRAL and the ADMM setup): the resident population, its evaluation, its status codes and an installed ADMM basis are not touched,
 // whether the call succeeds or is refused.  The shared steps come first; a driver is its argument struct, its launch and its outputs.
-// Host code only: the four launcher headers, and the launch of the core's selection kernel through capi_ctx.h.
+// Host code only: the launcher headers, and the launch of the core's selection kernel through capi_ctx.h.
 #include <cmath>
 #include <cstring>
 
@@ -12,6 +12,7 @@
 #include "sdr_small.h"
 #include "spectral_small.h"
 #include "spectral_wide.h"
+#include "admm_setup.h"
 
 using namespace qcqpmi;
 
@@ -391,6 +392,53 @@ int admm_small_batch(qcqpmi_ctx *c, int64_t maxn, int64_t B, const double *P0s, 
     return 0;
 }
 
+// ---- the setup of improve(ADMM) on the device (admm_setup.h): rho_b by the reference's rule (rho == nullptr) or the caller's, and
+// Minv_b = (2 (P0_b + rho_b m I))^-1, both from one eigendecomposition per problem.  n <= ADMM_SETUP_SMALL_MAXN runs the narrow kernel
+int admm_setup_batch(qcqpmi_ctx *c, int64_t B, const double *P0s, const double *rho, int max_sweeps, double tol, double *rhos, double *lambda_min,
+                     double *Minvs, int64_t *sweeps, int *status) {
+    const char *name = "admm_batch_setup";
+    int rc = check_batch_context(c, name);
+    if (rc) return rc;
+    if (c->n > ADMM_SETUP_MAXN) return fail(c, QCQPMI_EUNSUPPORTED, "admm_batch_setup: n = %lld, the setup kernels take n <= %lld (one array G_b in LDS, two eigenvalues per lane)",
+                                            (long long)c->n, (long long)ADMM_SETUP_MAXN);
+    if (B < 1 || B >= (1LL << 30)) return fail(c, QCQPMI_EINVAL, "admm_batch_setup: B = %lld problems, 1 to 2^30 - 1 per call", (long long)B);
+    if (!P0s) return fail(c, QCQPMI_EINVAL, "admm_batch_setup: the objective matrices P0s are missing");
+    if (max_sweeps < 1) return fail(c, QCQPMI_EINVAL, "admm_batch_setup: max_sweeps = %d, at least one sweep", max_sweeps);
+    if (!(tol > 0.0) || !std::isfinite(tol)) return fail(c, QCQPMI_EINVAL, "admm_batch_setup: tol = %g is not positive and finite", tol);
+    if (rho && (!(*rho > 0.0) || !std::isfinite(*rho))) return fail(c, QCQPMI_EINVAL, "admm_batch_setup: rho = %g is not positive and finite", *rho);
+    const int64_t n = c->n, m = c->m;
+    if (m < 1) return fail(c, QCQPMI_EINVAL, "admm_batch_setup: the context has no constraint (the rule divides by m)");
+    HIPCHK(c, hipSetDevice(c->device));
+    Carve cv;
+    const size_t oP = cv.take((size_t)B * n * n * 8), oM = cv.take((size_t)B * n * n * 8), orho = cv.take((size_t)B * 8), olm = cv.take((size_t)B * 8);
+    const size_t osw = cv.take((size_t)B * 8), ost = cv.take((size_t)B * 4), oticket = cv.take(2 * sizeof(int));
+    HIPCHK(c, c->ss_work.reserve(c->stream, cv.off, false));
+    char *w = c->ss_work;
+    if ((rc = stage_in(c, w + oP, P0s, (size_t)B * n * n * 8))) return rc;
+    HIPCHK(c, hipMemsetAsync(w + oticket, 0, 2 * sizeof(int), c->stream));
+    if (rho) HIPCHK(c, hipMemsetAsync(w + oM, 0, (size_t)B * n * n * 8, c->stream));      // a problem of status 3 is not written
+    AdmmSetupArgs a;
+    a.n = (int)n; a.B = B;
+    a.P0s = (const double *)(w + oP);
+    a.m = (double)m; a.has_rho = rho ? 1 : 0; a.rho = rho ? *rho : 0.0;
+    a.max_sweeps = max_sweeps; a.tol = tol;
+    a.ticket = (int *)(w + oticket);
+    a.rhos = (double *)(w + orho); a.lambda_min = (double *)(w + olm); a.Minvs = (double *)(w + oM);
+    a.sweeps = (int64_t *)(w + osw); a.status = (int *)(w + ost);
+    const int wgs = admm_setup_workgroups((int)n, B, c->device);
+    if (wgs < 1) return fail(c, QCQPMI_EHIP, "admm_batch_setup: occupancy query failed: %s", hipGetErrorString((hipError_t)(-wgs)));
+    const hipError_t qe = (hipError_t)admm_setup_launch(a, wgs, c->stream);
+    if (qe != hipSuccess) return fail(c, QCQPMI_EHIP, "admm_batch_setup: %s", hipGetErrorString(qe));
+    if ((rc = check_symmetric(c, w + oticket, "admm_batch_setup: an objective matrix P0_b is not symmetric (or holds a NaN)"))) return rc;
+    if (rhos) HIPCHK(c, hipMemcpyAsync(rhos, a.rhos, (size_t)B * 8, hipMemcpyDeviceToHost, c->stream));
+    if (lambda_min) HIPCHK(c, hipMemcpyAsync(lambda_min, a.lambda_min, (size_t)B * 8, hipMemcpyDeviceToHost, c->stream));
+    if (Minvs) HIPCHK(c, hipMemcpyAsync(Minvs, a.Minvs, (size_t)B * n * n * 8, hipMemcpyDeviceToHost, c->stream));
+    if (sweeps) HIPCHK(c, hipMemcpyAsync(sweeps, a.sweeps, (size_t)B * 8, hipMemcpyDeviceToHost, c->stream));
+    if (status) HIPCHK(c, hipMemcpyAsync(status, a.status, (size_t)B * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, spin_sync(c->stream));
+    return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -446,6 +494,12 @@ int qcqpmi_admm_batch_run(qcqpmi_ctx *c, int64_t B, const double *P0s, const dou
                           double *best_maxviol, double *best_x) {
     return admm_small_batch(c, ADMM_WIDE_MAXN, B, P0s, q0s, r0s, cons, rhos, Minvs, R, generate, X0, phase1, num_iters, tol, viol_lim, seed, seed_stride,
                             first_index, select_tol, iters1, iters2, f0, maxviol, X, best_index, best_f0, best_maxviol, best_x);
+}
+
+// ---- rhos and Minvs of the two calls above from one eigendecomposition per problem on the device (admm_setup.h), 1 <= n <= 128
+int qcqpmi_admm_batch_setup(qcqpmi_ctx *c, int64_t B, const double *P0s, const double *rho, int max_sweeps, double tol, double *rhos,
+                            double *lambda_min, double *Minvs, int64_t *sweeps, int *status) {
+    return admm_setup_batch(c, B, P0s, rho, max_sweeps, tol, rhos, lambda_min, Minvs, sweeps, status);
 }
 
 int qcqpmi_sdr_small_batch(qcqpmi_ctx *c, int64_t B, const double *P0s, const double *q0s, const double *r0s, int64_t S, int max_sweeps,

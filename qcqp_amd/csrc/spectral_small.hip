@@ -220,3 +220,38 @@ int spectral_wide_launch(const SpectralSmallArgs &a, int wgs, hipStream_t st) {
 }
 
 }  // namespace qcqpmi
+
+// ---- the device-side setup of batched ADMM (admm_setup.h): same unit -- it runs the two eigen-solvers --, the kernels in a file of their own
+#include "admm_setup_kernel.h"
+
+namespace qcqpmi {
+
+size_t admm_setup_lds_bytes(int n) {
+    const int n2 = (n + 1) & ~1;
+    return (n > ADMM_SETUP_SMALL_MAXN ? jacobi_wide_doubles(n2) + ASW_VECS * ASW_VEC : jacobi_small_doubles(n2) + AS_VECS * AS_VEC) * sizeof(double);
+}
+
+static const void *admm_setup_function(int n) {
+    return n > ADMM_SETUP_SMALL_MAXN ? (const void *)admm_setup_wide_kernel : (const void *)admm_setup_kernel;
+}
+
+int admm_setup_workgroups(int n, int64_t B, int device) {
+    int per = 0;
+    const size_t lds = admm_setup_lds_bytes(n);
+    hipError_t e = hipFuncSetAttribute(admm_setup_function(n), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return -(int)e;
+    e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, admm_setup_function(n), 64, lds);
+    if (e != hipSuccess) return -(int)e;
+    return small_workgroup_cap(device, per, B);
+}
+
+int admm_setup_launch(const AdmmSetupArgs &a, int wgs, hipStream_t st) {
+    const size_t lds = admm_setup_lds_bytes(a.n);
+    const hipError_t e = hipFuncSetAttribute(admm_setup_function(a.n), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return (int)e;
+    if (a.n > ADMM_SETUP_SMALL_MAXN) hipLaunchKernelGGL(admm_setup_wide_kernel, dim3((unsigned)wgs), dim3(64), lds, st, a);
+    else hipLaunchKernelGGL(admm_setup_kernel, dim3((unsigned)wgs), dim3(64), lds, st, a);
+    return (int)hipGetLastError();
+}
+
+}  // namespace qcqpmi

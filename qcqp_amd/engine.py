@@ -430,6 +430,25 @@ class Engine(object):
             out[k] = out[k].reshape(B, R)
         return out
 
+    def admm_batch_setup(self, P0s, rho=None, max_sweeps=30, tol=1e-15):
+        """The setup of admm_small_batch_run / admm_batch_run on the device (qcqpmi_admm_batch_setup, n <= 128): for P0s (B, n, n)
+        symmetric, ONE launch decomposes every P0_b (Jacobi: max_sweeps, tol as spectral_batch takes them) and returns a dictionary:
+        lambda_min (B,); rho (B,) -- the reference's rule (qcqp.py:270-277) applied to lambda_min, bit for bit, or the given rho --;
+        Minv (B, n, n) = (2 (P0_b + rho_b m I))^-1, exactly symmetric; sweeps (B,); status (B,) (0; 1: Jacobi hit max_sweeps; 2: not
+        finite; 3: the given rho is too small for the problem, lambda_min + m rho < 0, and its Minv is zero).  What
+        qcqp_amd.batch.admm_rhos and admm_minvs compute on the host.  The resident population is not touched."""
+        P0s = np.ascontiguousarray(P0s, dtype=np.float64)
+        B, n = int(P0s.shape[0]) if P0s.ndim == 3 else 0, self.n
+        if P0s.shape != (B, n, n):
+            raise ValueError('admm_batch_setup: expected P0s (B, n, n) with n = %d' % n)
+        out = dict(rho=np.empty(B), lambda_min=np.empty(B), Minv=np.empty((B, n, n)), sweeps=np.zeros(B, dtype=np.int64),
+                   status=np.zeros(B, dtype=np.int32))
+        given = None if rho is None else np.array([float(rho)])
+        self._chk(self.L.qcqpmi_admm_batch_setup(self.h, B, _dp(P0s), _dp(given), int(max_sweeps), float(tol), _dp(out['rho']),
+                                                 _dp(out['lambda_min']), _dp(out['Minv']), _ip(out['sweeps']),
+                                                 out['status'].ctypes.data_as(C.POINTER(C.c_int))))
+        return out
+
     def admm_fused(self, enable=True):
         """Fused persistent ADMM kernel on / off (off = the multi-launch path everywhere: the cross-check); 2 = the fused kernel
         with four-wave workgroups, two per compute unit (an experiment kept as a second cross-check)."""

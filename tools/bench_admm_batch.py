@@ -10,6 +10,10 @@ Workload: problems.boolean_least_squares_batch(B, n, m), R restarts per problem,
              SCALED LINEARLY to B (every problem costs the same launches).  --loop-problems 0 skips it (an A/B of the batched call alone).
 --wide passes wide=True to improve(ADMM), so that --n 128 --m 192 runs (the wide kernels); --wide-threads T sets
 QCQPMI_ADMM_WIDE_THREADS: a workgroup of T threads for the wide kernels instead of the occupancy rule (results do not depend on it).
+--setup device passes setup='device' to improve(ADMM): rho and the inverses come from one launch of the setup kernels
+(qcqpmi_admm_batch_setup) instead of the batched eigvalsh and inverse; that call alone (upload of the B objectives,
+the launch, the downloads of the B inverses) is then timed as well, next to the host part.  The default, host, is the path every
+earlier figure of this tool was taken on.
 Prints one JSON line.  The two paths agree in the median only (the iteration amplifies rounding: DESIGN.md 4.13); the line reports on how
 many of the timed problems the winners' objectives agree to 1e-6."""
 import argparse
@@ -33,6 +37,7 @@ def main():
     ap.add_argument('--seed', type=int, default=1)
     ap.add_argument('--wide', action='store_true')
     ap.add_argument('--wide-threads', type=int, default=0)
+    ap.add_argument('--setup', choices=('host', 'device'), default='host')
     args = ap.parse_args()
     if args.wide_threads:
         os.environ['QCQPMI_ADMM_WIDE_THREADS'] = str(args.wide_threads)      # read once, at the first wide launch
@@ -47,9 +52,13 @@ def main():
     qb = QCQPBatch(fl)
     qb.suggest(s.RANDOM, num_samples=args.R, seed=args.seed)
 
+    kw = dict(wide=True) if args.wide else {}
+    if args.setup != 'host':                        # (the default call carries no keyword: the path of the earlier figures)
+        kw['setup'] = args.setup
+
     def batched():
         t0 = time.perf_counter()
-        f, v = qb.improve(s.ADMM, num_iters=args.num_iters, **(dict(wide=True) if args.wide else {}))
+        f, v = qb.improve(s.ADMM, num_iters=args.num_iters, **kw)
         return time.perf_counter() - t0, f
 
     batched()                                       # warm-up: code object, buffers
@@ -62,6 +71,14 @@ def main():
     batch.admm_minvs(qb.P0s, rhos, qb.form.m)
     t_host = time.perf_counter() - t0
     st = qb.last_stats
+    t_dev = None
+    if args.setup == 'device':
+        dev = []
+        for _ in range(args.repeat + 1):            # the first call is the warm-up
+            t0 = time.perf_counter()
+            qb.engine.admm_batch_setup(qb.P0s)
+            dev.append(time.perf_counter() - t0)
+        t_dev = sorted(dev[1:])[len(dev[1:]) // 2]
     iters = int(st['iters1'].sum() + st['iters2'].sum())
 
     nl = min(args.loop_problems, args.B)
@@ -77,7 +94,7 @@ def main():
         return time.perf_counter() - t0, best
 
     out = dict(workload=dict(family='bls', B=args.B, n=args.n, m=args.m, R=args.R, num_iters=args.num_iters), kernel=st['kernel'],
-               wide_threads=args.wide_threads or 'rule', batched_s=t_batched, batched_all_s=times, host_eigvalsh_and_inverse_s=t_host,
+               wide_threads=args.wide_threads or 'rule', batched_s=t_batched, batched_all_s=times, setup=args.setup, host_eigvalsh_and_inverse_s=t_host, device_setup_call_s=t_dev,
                restart_iterations=iters, restart_iterations_per_s=iters / t_batched, loop_problems=nl)
     if nl > 0:
         loop()                                      # warm-up
