@@ -571,6 +571,51 @@ int qcqpmi_admm_batch_run(qcqpmi_ctx *ctx, int64_t B, const double *P0s, const d
                           int64_t num_iters, double tol, double viol_lim, uint64_t seed, uint64_t seed_stride, uint64_t first_index,
                           double select_tol, int64_t *iters1, int64_t *iters2, double *f0, double *maxviol, double *X,
                           int64_t *best_index, double *best_f0, double *best_maxviol, double *best_x);
+/* IMPROVE CHAINS FOR MANY SMALL PROBLEMS IN ONE LAUNCH (added within ABI 6: a new symbol and a plain struct, nothing else changes).
+ * The reference's improve takes a list of methods and runs them one after the other, each from the point the previous one left
+ * (qcqp.py:420-432).  This call does that for the batch of qcqpmi_cd_small_batch_run / qcqpmi_admm_small_batch_run -- B objectives over
+ * this context's separable constraint lists, 1 <= n <= 64, R restarts per problem; cons == NULL or [B][m][3] -- with 1 <= nstages <= 4
+ * stages, each COORD_DESCENT (method 0: phase1, num_iters, tol, viol_tol as qcqpmi_cd_small_batch_run reads them) or ADMM (method 1:
+ * phase1, num_iters, tol, viol_lim as qcqpmi_admm_small_batch_run reads them; rhos [B] and Minvs [B][n][n] as that call takes them, NULL
+ * where no stage is ADMM).  Stage 0 starts from the keyed normals (seed + b seed_stride, first_index + r) or from X0 [B][R][n]
+ * (generate = 0); stage s > 0 starts from the point stage s - 1 left, ALSO where that stage reported a failure for the restart (status
+ * != 0, f0 = maxviol = inf): its point is handed on as it is.  Every stage keys its draws with the same (seed + b seed_stride,
+ * first_index + r), as separate calls with one seed do.
+ * PARITY.  The call is DEFINED as the composition of the two single calls: restart (b, r) of stage s is bit for bit what
+ * qcqpmi_cd_small_batch_run[_pc] / qcqpmi_admm_small_batch_run return when they are called stage by stage with the X of one call as the X0
+ * (generate = 0) of the next -- the same device functions in the same order on the same inputs -- and so inherits their parity
+ * statements (the CPU oracle's improve_cd_sep term for term; 1e-9 against the reference for a few ADMM iterations per phase) and their
+ * invariances: a result depends on (problem b, rho_b, Minv_b, seed of b, global index, the stages) alone, not on B, the neighbours,
+ * the order of the problems, the workgroups or a split of the restarts over calls.
+ * One persistent launch of chain_small_kernel (csrc/chain_small.hip): a workgroup works its ticket through all stages -- per stage it
+ * replaces the LDS image (P0_b, or Minv_b), and a barrier hands the points over through global memory -- while other workgroups are
+ * wherever they are: no join between the stages, no host in the loop.
+ * Per-stage records, any may be NULL: st_* are arrays [nstages][B R] (stage-major, then problem-major); a CD stage fills its row of
+ * st_sweeps1, st_sweeps2, st_visits2, st_accepted2, st_ran_phase2, st_status1, st_status2, an ADMM stage its row of st_iters1,
+ * st_iters2, every stage its row of st_f0, st_maxviol; the rows of what a stage does not produce are zero.  f0, maxviol [B R], X
+ * [B][R][n] and best_* [B] (as qcqpmi_cd_small_batch_run reports them) are those of the LAST stage.
+ * qcqpmi_last_cd_kernel: "chain_small_kernel<1>" / "<4>" / "<1,pc>" / "<4,pc>".
+ * Refusals, all before any launch except the symmetry check; the resident population, its evaluation, its status codes and an
+ * installed ADMM basis stay as they were, whether the call succeeds or is refused.  QCQPMI_EUNSUPPORTED: n > 64, constraints that are
+ * not separable.  QCQPMI_EINVAL: nstages < 1 or > 4, stages == NULL, an unknown method, an ADMM stage with rhos or Minvs NULL, and
+ * everything the two single calls refuse with it (B < 1, R < 1, B R >= 2^30, num_iters < 0, a CD stage's tol <= 0, a missing array;
+ * with an ADMM stage no constraint or a rhos entry that is not positive and finite; a cons entry that is not finite or has p == q ==
+ * 0; a P0_b or Minv_b that is not symmetric -- found while staging: the call fails after its launch and returns no results). */
+typedef struct {
+    int method;        /* 0: COORD_DESCENT, 1: ADMM */
+    int phase1;
+    int64_t num_iters;
+    double tol;        /* CD: the acceptance threshold (1e-4 in the reference); ADMM: the exit tolerance of both phases (1e-2) */
+    double viol_tol;   /* CD only */
+    double viol_lim;   /* ADMM only */
+} qcqpmi_chain_stage;
+int qcqpmi_chain_small_batch_run(qcqpmi_ctx *ctx, int64_t B, const double *P0s, const double *q0s, const double *r0s, const double *cons,
+                                 const double *rhos, const double *Minvs, int64_t R, int generate, const double *X0, int nstages,
+                                 const qcqpmi_chain_stage *stages, uint64_t seed, uint64_t seed_stride, uint64_t first_index,
+                                 double select_tol, int64_t *st_sweeps1, int64_t *st_sweeps2, int64_t *st_visits2, int64_t *st_accepted2,
+                                 uint8_t *st_ran_phase2, int *st_status1, int *st_status2, int64_t *st_iters1, int64_t *st_iters2,
+                                 double *st_f0, double *st_maxviol, double *f0, double *maxviol, double *X, int64_t *best_index,
+                                 double *best_f0, double *best_maxviol, double *best_x);
 /* THE SETUP OF THE TWO CALLS ABOVE ON THE DEVICE (added within ABI 6: a new symbol, nothing else changes).  rhos and Minvs of
  * qcqpmi_admm_small_batch_run / qcqpmi_admm_batch_run for B problems over this context (n, m = its number of constraints, its device),
  * 1 <= n <= 128, from ONE symmetric eigendecomposition P0_b = sum_k lam_k u_k u_k' per problem inside ONE persistent launch

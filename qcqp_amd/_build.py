@@ -16,7 +16,7 @@ HEADER = os.path.join(REPO, 'include', 'qcqp_mi.h')
 # translation units; what each one includes is found by scanning its `#include "..."` lines recursively (round 4 shipped a
 # hand-kept list that missed a header: an edit to it rebuilt nothing)
 TRANSLATION_UNITS = ['capi.hip', 'capi_cd.hip', 'capi_dense.hip', 'capi_admm.hip', 'capi_small.hip', 'capi_units.hip', 'capi_comm.hip', 'capi_stream.hip',
-                     'admm_fused.hip', 'cd_queue.hip', 'cd_life.hip', 'cd_small.hip', 'sdr_small.hip', 'admm_small.hip', 'spectral_small.hip']
+                     'admm_fused.hip', 'cd_queue.hip', 'cd_life.hip', 'cd_small.hip', 'sdr_small.hip', 'admm_small.hip', 'spectral_small.hip', 'chain_small.hip']
 _INC = re.compile(r'^\s*#\s*include\s+"([^"]+)"', re.M)
 
 

@@ -14,6 +14,13 @@ c_dp = C.POINTER(C.c_double)
 c_ip = C.POINTER(C.c_int64)
 c_bp = C.POINTER(C.c_uint8)
 
+
+class ChainStage(C.Structure):
+    """qcqpmi_chain_stage: one stage of qcqpmi_chain_small_batch_run (method 0: COORD_DESCENT, 1: ADMM)."""
+    _fields_ = [('method', C.c_int), ('phase1', C.c_int), ('num_iters', C.c_int64), ('tol', C.c_double), ('viol_tol', C.c_double),
+                ('viol_lim', C.c_double)]
+
+
 # (name, restype, argtypes) -- every symbol of include/qcqp_mi.h
 PROTOTYPES = [
     ('qcqpmi_abi_version', C.c_int, []),
@@ -88,6 +95,9 @@ PROTOTYPES = [
     ('qcqpmi_admm_batch_run', C.c_int, [C.c_void_p, C.c_int64, c_dp, c_dp, c_dp, c_dp, c_dp, c_dp, C.c_int64, C.c_int, c_dp, C.c_int, C.c_int64,
                                         C.c_double, C.c_double, C.c_uint64, C.c_uint64, C.c_uint64, C.c_double, c_ip, c_ip, c_dp, c_dp, c_dp,
                                         c_ip, c_dp, c_dp, c_dp]),
+    ('qcqpmi_chain_small_batch_run', C.c_int, [C.c_void_p, C.c_int64, c_dp, c_dp, c_dp, c_dp, c_dp, c_dp, C.c_int64, C.c_int, c_dp, C.c_int, C.c_void_p,
+                                               C.c_uint64, C.c_uint64, C.c_uint64, C.c_double, c_ip, c_ip, c_ip, c_ip, c_bp, C.POINTER(C.c_int),
+                                               C.POINTER(C.c_int), c_ip, c_ip, c_dp, c_dp, c_dp, c_dp, c_dp, c_ip, c_dp, c_dp, c_dp]),
     ('qcqpmi_admm_batch_setup', C.c_int, [C.c_void_p, C.c_int64, c_dp, c_dp, C.c_int, C.c_double, c_dp, c_dp, c_dp, c_ip, C.POINTER(C.c_int)]),
     ('qcqpmi_sdr_small_batch', C.c_int, [C.c_void_p, C.c_int64, c_dp, c_dp, c_dp, C.c_int64, C.c_int, C.c_double, C.c_uint64, C.c_uint64,
                                          C.c_uint64, c_dp, c_dp, c_dp, c_dp, c_ip, c_dp]),

@@ -32,6 +32,8 @@ CU up to n = 128 once C_b is stored as its lower triangle).
     f, v = batch.improve(s.COORD_DESCENT)
     batch.suggest(s.RANDOM, num_samples=64, seed=7)
     f, v = batch.improve(s.ADMM, num_iters=100)    # batch.last_stats['rho'] (B,), ['iters1'], ['iters2'] (B, R)
+    f, v = batch.improve([s.ADMM, s.COORD_DESCENT], num_iters=100)     # a chain: ADMM, then coordinate descent from its points,
+                                                   # n <= 64 and up to 4 stages in ONE launch (Engine.chain_small_batch_run)
 """
 import numpy as np
 import scipy.sparse as sp
@@ -114,6 +116,36 @@ def admm_minvs(P0s, rhos, m):
     n = P0s.shape[1]
     Mi = np.linalg.inv(2. * (P0s + (np.asarray(rhos) * m)[:, None, None] * np.eye(n)))
     return (Mi + Mi.transpose(0, 2, 1)) / 2.
+
+
+CHAIN_STAGE_KEYS = ('num_iters', 'tol', 'viol_tol', 'viol_lim', 'phase1')
+FUSED_MAX_STAGES = 4     # qcqpmi_chain_small_batch_run: stages per launch (n <= MAX_N_SMALL)
+
+
+def chain_stages(method, num_iters=1000, viol_tol=1e-2, tol=None, phase1=True, viol_lim=1e4):
+    """The stage descriptors of QCQPBatch.improve(method, ...): ``method`` is a method or a list whose entries are a method or
+    (method, kwargs) with that stage's own num_iters / tol / viol_tol / viol_lim / phase1; the keyword arguments are the default of
+    every stage (the reference hands one **kwargs to every method of its list, qcqp.py:420-432).  tol == None stands for each method's
+    own default: 1e-4 for COORD_DESCENT, 1e-2 for ADMM.  Returns a list of dictionaries with the keys method, phase1, num_iters, tol,
+    viol_tol, viol_lim.  A pure function: no device, no library."""
+    entries = list(method) if isinstance(method, list) else [method]
+    if not entries:
+        raise Exception("QCQPBatch.improve: the list of methods is empty")
+    defaults = dict(num_iters=num_iters, tol=tol, viol_tol=viol_tol, viol_lim=viol_lim, phase1=phase1)
+    out = []
+    for k, e in enumerate(entries):
+        meth, kw = (e[0], dict(e[1])) if isinstance(e, tuple) and len(e) == 2 and isinstance(e[1], dict) else (e, {})
+        if meth not in (s.COORD_DESCENT, s.ADMM):
+            raise Exception("QCQPBatch.improve is defined for the COORD_DESCENT and ADMM methods")
+        unknown = sorted(set(kw) - set(CHAIN_STAGE_KEYS))
+        if unknown:
+            raise Exception("QCQPBatch.improve: stage %d has the argument %r; a stage takes %s" % (k, unknown[0], ', '.join(CHAIN_STAGE_KEYS)))
+        g = dict(defaults, **kw)
+        if g['tol'] is None:
+            g['tol'] = 1e-4 if meth == s.COORD_DESCENT else 1e-2
+        out.append(dict(method=meth, phase1=bool(g['phase1']), num_iters=int(g['num_iters']), tol=float(g['tol']),
+                        viol_tol=float(g['viol_tol']), viol_lim=float(g['viol_lim'])))
+    return out
 
 
 class QCQPBatch(object):
@@ -284,7 +316,7 @@ class QCQPBatch(object):
         self._suggested = (1, int(seed), int(first_index), int(seed_stride))
 
     def improve(self, method=s.COORD_DESCENT, num_iters=1000, viol_tol=1e-2, tol=None, phase1=True, seed=None, viol_lim=1e4, rho=None,
-                wide=False, setup='host'):
+                wide=False, setup='host', fused=None):
         """improve(COORD_DESCENT) or improve(ADMM) of every suggested start of every problem; returns (f (B,), v (B,)) of the best
         restart per problem (QCQPForm.better, ties -> lowest index) and sets .x (B, n), .population_f / .population_v (B, R),
         .best_index, .last_stats.  seed: the seed of suggest() (a problem's normals and its draws come from ONE keyed stream).
@@ -299,7 +331,27 @@ class QCQPBatch(object):
         problem -- and then the same ADMM launch with its rho and its inverse; the rule is applied to the device's lambda_min, which
         agrees with eigvalsh to rounding (for a singular PSD P0_b rounding decides the rule's branch, here as on the host); a problem
         whose decomposition did not converge or is not finite raises.  .last_stats gains setup, lambda_min and setup_sweeps (None
-        on the host path).  setup='device' does not admit n > 64 by itself (wide=True does).  COORD_DESCENT ignores it."""
+        on the host path).  setup='device' does not admit n > 64 by itself (wide=True does).  COORD_DESCENT ignores it.
+        A LIST of methods (the reference's improve, qcqp.py:420-432) runs them one after the other, each from the points the previous
+        one left -- also those of restarts it reported as failed --, every stage with the same keyed stream.  An entry is a method
+        or (method, kwargs) with that stage's own num_iters / tol / viol_tol / viol_lim / phase1; the keyword arguments of the call
+        are every stage's default (chain_stages): improve([COORD_DESCENT, (ADMM, dict(phase1=False))]) is the reference's
+        improve(COORD_DESCENT); improve(ADMM, phase1=False).  A list of one entry is the scalar call.  rho and setup serve every ADMM
+        stage (computed once); wide is asked for as before when a stage is ADMM and n > 64.
+        fused (lists only): None -- ONE launch (``Engine.chain_small_batch_run``, qcqpmi_chain_small_batch_run) where the chain kernel
+        takes the problem (n <= 64, at most 4 stages), else the COMPOSED path: the engine calls of the scalar methods stage by stage,
+        X of one as X0 of the next (any n <= 128, any number of stages); True -- raise, before any launch, where the chain kernel does
+        not take the problem; False -- always composed.  Both paths give the same bits.  .x, .best_index, .population_f / _v and the
+        returned (f, v) are the LAST stage's; .last_stats holds the last stage's arrays, method (the list), stages (one dictionary
+        per stage: its method, its records, f0, maxviol), fused (bool) and kernel; with an ADMM stage also rho, setup, lambda_min,
+        setup_sweeps; where the last stage is COORD_DESCENT also failed_restarts.  Two separate improve() calls still each start
+        from suggest()'s points."""
+        if isinstance(method, list):
+            stages = chain_stages(method, num_iters=num_iters, viol_tol=viol_tol, tol=tol, phase1=phase1, viol_lim=viol_lim)
+            if len(stages) > 1:
+                return self._improve_chain(stages, seed, rho, wide, setup, fused)
+            g = stages[0]      # exactly the scalar call
+            method, num_iters, viol_tol, tol, phase1, viol_lim = g['method'], g['num_iters'], g['viol_tol'], g['tol'], g['phase1'], g['viol_lim']
         if method not in (s.COORD_DESCENT, s.ADMM):
             raise Exception("QCQPBatch.improve is defined for the COORD_DESCENT and ADMM methods")
         if method == s.ADMM and setup not in ('host', 'device'):      # before any launch
@@ -357,6 +409,70 @@ class QCQPBatch(object):
                   tol=tol, viol_lim=viol_lim, seed=sd, seed_stride=stride, first_index=first_index, want_x=False, cons=self.cons)
         return self._publish(out, s.ADMM, R, rho=rhos, kernel=self.engine.last_admm_kernel()[0], setup=setup, lambda_min=lmin,
                              setup_sweeps=sweeps)
+
+    def _improve_chain(self, stages, seed, rho, wide, setup, fused):
+        """improve([method, ...]) with two or more stages (chain_stages): one launch of the chain kernel, or the composed path."""
+        any_admm = any(g['method'] == s.ADMM for g in stages)
+        can_fuse = self.n <= MAX_N_SMALL and len(stages) <= FUSED_MAX_STAGES
+        # every refusal before any launch
+        if any_admm and setup not in ('host', 'device'):
+            raise Exception("QCQPBatch.improve(ADMM): setup must be 'host' or 'device' (setup = %r)" % (setup,))
+        if any_admm and self.n > MAX_N_SMALL and not wide:
+            raise Exception("QCQPBatch.improve(ADMM) is defined for n <= %d (n = %d) unless wide=True is given (n <= %d: the wide kernels, "
+                            "two coordinates per lane); or use improve(COORD_DESCENT), or QCQP per problem" % (MAX_N_SMALL, self.n, MAX_N))
+        if fused not in (None, True, False):
+            raise Exception("QCQPBatch.improve: fused must be None, True or False (fused = %r)" % (fused,))
+        if fused is True and not can_fuse:
+            raise Exception("QCQPBatch.improve(fused=True): the chain kernel takes n <= %d and at most %d stages (n = %d, %d stages); "
+                            "fused=None runs the composed path" % (MAX_N_SMALL, FUSED_MAX_STAGES, self.n, len(stages)))
+        if self._suggested is None:
+            raise Exception("QCQPBatch.improve: call suggest(RANDOM or SDR, num_samples=R, seed=...) first")
+        R, sd, first_index, stride = self._suggested
+        if seed is not None and int(seed) != sd:
+            raise Exception("QCQPBatch.improve: seed %d differs from the seed of suggest (%d); the batch runs one keyed stream per problem"
+                            % (int(seed), sd))
+        stats = {}
+        rhos = minvs = None
+        if any_admm:      # once for every ADMM stage, as _improve_admm does
+            m = self.form.m
+            if setup == 'device':
+                rhos, minvs, lmin, sweeps = self._admm_setup_device(m, rho)
+            else:
+                rhos = admm_rhos(self.P0s, m, rho)
+                minvs, lmin, sweeps = admm_minvs(self.P0s, rhos, m), None, None
+            stats = dict(rho=rhos, setup=setup, lambda_min=lmin, setup_sweeps=sweeps)
+        E = self.engine
+        common = dict(seed=sd, seed_stride=stride, first_index=first_index, cons=self.cons)
+        use_fused = can_fuse and fused is not False
+        if use_fused:
+            code = {s.COORD_DESCENT: E.CHAIN_CD, s.ADMM: E.CHAIN_ADMM}
+            out = E.chain_small_batch_run(self.P0s, self.q0s, self.r0s, R, [dict(g, method=code[g['method']]) for g in stages], rhos=rhos,
+                                          Minvs=minvs, X0=self._starts, want_x=False, **common)
+            per_stage = [dict(d, method=g['method']) for d, g in zip(out['stages'], stages)]
+            kernel = E.last_cd_kernel()
+        else:
+            small = self.n <= MAX_N_SMALL
+            X, per_stage, kernels = self._starts, [], []
+            for k, g in enumerate(stages):
+                want_x = k + 1 < len(stages)      # the points of the last stage are not handed on
+                if g['method'] == s.ADMM:
+                    run = E.admm_small_batch_run if small else E.admm_batch_run
+                    out = run(self.P0s, self.q0s, self.r0s, R, rhos, minvs, X0=X, phase1=g['phase1'], num_iters=g['num_iters'], tol=g['tol'],
+                              viol_lim=g['viol_lim'], want_x=want_x, **common)
+                    kernels.append(E.last_admm_kernel()[0])
+                    keys = E._CHAIN_ADMM_KEYS
+                else:
+                    run = E.cd_small_batch_run if small else E.cd_batch_run
+                    out = run(self.P0s, self.q0s, self.r0s, R, X0=X, phase1=g['phase1'], num_iters=g['num_iters'], viol_tol=g['viol_tol'],
+                              tol=g['tol'], want_x=want_x, **common)
+                    kernels.append(E.last_cd_kernel())
+                    keys = E._CHAIN_CD_KEYS
+                X = out['X']
+                per_stage.append(dict(((key, out[key]) for key in keys + ('f0', 'maxviol')), method=g['method']))
+            kernel = ' + '.join(kernels)
+        if stages[-1]['method'] == s.COORD_DESCENT:
+            stats['failed_restarts'] = int(np.count_nonzero((out['status1'] != 0) | (out['status2'] != 0)))
+        return self._publish(out, [g['method'] for g in stages], R, stages=per_stage, fused=use_fused, kernel=kernel, **stats)
 
     def close(self):
         self.engine.close()

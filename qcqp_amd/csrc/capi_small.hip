@@ -1,5 +1,5 @@
 // Small-problem batch part of the C ABI: B small problems over the context's constraint structure in ONE
-// persistent launch of cd_small.hip, admm_small.hip, sdr_small.hip or spectral_small.hip (narrow and wide kernel; the ADMM setup kernels live there too).  A call works in a device buffer of its own
+// persistent launch of cd_small.hip, admm_small.hip, chain_small.hip, sdr_small.hip or spectral_small.hip (narrow and wide kernel; the ADMM setup kernels live there too).  A call works in a device buffer of its own
 // (sb_work for CD and ADMM, ss_work for SDR, SPECTRAL and the ADMM setup): the resident population, its evaluation, its status codes and an installed ADMM basis are not touched,
 // whether the call succeeds or is refused.  The shared steps come first; a driver is its argument struct, its launch and its outputs.
 // Host code only: the launcher headers, and the launch of the core's selection kernel through capi_ctx.h.
@@ -9,6 +9,7 @@
 #include "capi_ctx.h"
 #include "cd_small.h"
 #include "admm_small.h"
+#include "chain_small.h"
 #include "sdr_small.h"
 #include "spectral_small.h"
 #include "spectral_wide.h"
@@ -392,6 +393,117 @@ int admm_small_batch(qcqpmi_ctx *c, int64_t maxn, int64_t B, const double *P0s, 
     return 0;
 }
 
+// ---- improve([method, ...]): up to CHAIN_MAX_STAGES stages of CD or ADMM one after the other in ONE launch (chain_small.h).  The
+// per-stage records live in one block of the work buffer, array after array, every array [nstages][B R] and zeroed before the launch:
+// six of int64 (sweeps1, sweeps2, visits2, accepted2, iters1, iters2), two of double (f0, maxviol), two of int (status1, status2), one
+// of uint8 (ran_phase2): 73 bytes per stage and restart.  The final f0 / maxviol are the last stage's rows of the two double arrays.
+int chain_small_batch(qcqpmi_ctx *c, int64_t B, const double *P0s, const double *q0s, const double *r0s, const double *cons, const double *rhos,
+                      const double *Minvs, int64_t R, int generate, const double *X0, int nstages, const qcqpmi_chain_stage *stages, uint64_t seed,
+                      uint64_t seed_stride, uint64_t first_index, double select_tol, int64_t *st_sweeps1, int64_t *st_sweeps2,
+                      int64_t *st_visits2, int64_t *st_accepted2, uint8_t *st_ran_phase2, int *st_status1, int *st_status2,
+                      int64_t *st_iters1, int64_t *st_iters2, double *st_f0, double *st_maxviol, double *f0, double *maxviol, double *X,
+                      int64_t *best_index, double *best_f0, double *best_maxviol, double *best_x) {
+    const char *name = "chain_small_batch_run";
+    int rc = check_batch_context(c, name);
+    if (rc) return rc;
+    if (c->n > CHAIN_SMALL_MAXN) return fail(c, QCQPMI_EUNSUPPORTED, "chain_small_batch_run: n = %lld, the chain kernel takes n <= %lld (one lane per coordinate)", (long long)c->n,
+                                             (long long)CHAIN_SMALL_MAXN);
+    if (nstages < 1 || nstages > CHAIN_MAX_STAGES || !stages)
+        return fail(c, QCQPMI_EINVAL, "chain_small_batch_run: nstages = %d, 1 to %d stages per launch (and their descriptors)", nstages, CHAIN_MAX_STAGES);
+    if (B < 1 || R < 1 || !P0s || !q0s || !r0s || (!generate && !X0)) return fail(c, QCQPMI_EINVAL, "chain_small_batch_run: bad B / R, or a missing input array");
+    bool any_admm = false;
+    for (int s = 0; s < nstages; s++) {
+        const qcqpmi_chain_stage &g = stages[s];
+        if (g.method != CHAIN_CD && g.method != CHAIN_ADMM) return fail(c, QCQPMI_EINVAL, "chain_small_batch_run: stage %d has method %d (0: COORD_DESCENT, 1: ADMM)", s, g.method);
+        if (g.num_iters < 0 || (g.method == CHAIN_CD && !(g.tol > 0.0))) return fail(c, QCQPMI_EINVAL, "chain_small_batch_run: stage %d has a bad num_iters / tol", s);
+        any_admm = any_admm || g.method == CHAIN_ADMM;
+    }
+    if ((rc = check_batch_count(c, name, B, R))) return rc;
+    const int64_t m = c->m;
+    if (any_admm) {
+        if (!rhos || !Minvs) return fail(c, QCQPMI_EINVAL, "chain_small_batch_run: an ADMM stage needs rhos and Minvs");
+        if (m < 1) return fail(c, QCQPMI_EINVAL, "chain_small_batch_run: the context has no constraint (the consensus average of an ADMM stage divides by m)");
+        for (int64_t b = 0; b < B; b++)
+            if (!(rhos[b] > 0.0) || !std::isfinite(rhos[b]))
+                return fail(c, QCQPMI_EINVAL, "chain_small_batch_run: rho of problem %lld is not positive and finite", (long long)b);
+    }
+    if (cons && (rc = check_batch_cons(c, name, cons, B, m))) return rc;
+    if (m == 0) cons = nullptr;       // nothing to stage: the shared kernels
+    HIPCHK(c, hipSetDevice(c->device));
+    const int64_t n = c->n, T = B * R, ST = (int64_t)nstages * T;
+    Carve cv;
+    const size_t oP = cv.take((size_t)B * n * n * 8), oM = cv.take(any_admm ? (size_t)B * n * n * 8 : 0), oq = cv.take((size_t)B * n * 8), or0 = cv.take((size_t)B * 8);
+    const size_t orho = cv.take(any_admm ? (size_t)B * 8 : 0);
+    const size_t oX0 = cv.take(generate ? 0 : (size_t)T * n * 8), oX = cv.take((size_t)T * n * 8);
+    const size_t oout = cv.take((size_t)ST * 73);
+    const size_t oticket = cv.take(2 * sizeof(int));
+    const BatchBest best = {cv.take((size_t)B * 2 * sizeof(int64_t)), cv.take((size_t)B * 2 * sizeof(double)), cv.take((size_t)B * n * 8),
+                            best_index, best_f0, best_maxviol, best_x};
+    const size_t ocons = cv.take(cons ? (size_t)B * m * 24 : 0);
+    HIPCHK(c, c->sb_work.reserve(c->stream, cv.off, false));
+    char *w = c->sb_work;
+    if ((rc = stage_in(c, w + oP, P0s, (size_t)B * n * n * 8)) || (rc = stage_in(c, w + oM, any_admm ? Minvs : nullptr, (size_t)B * n * n * 8)) ||
+        (rc = stage_in(c, w + oq, q0s, (size_t)B * n * 8)) || (rc = stage_in(c, w + or0, r0s, (size_t)B * 8)) ||
+        (rc = stage_in(c, w + orho, any_admm ? rhos : nullptr, (size_t)B * 8)) || (rc = stage_in(c, w + oX0, generate ? nullptr : X0, (size_t)T * n * 8)) ||
+        (rc = stage_in(c, w + ocons, cons, (size_t)B * m * 24)))
+        return rc;
+    HIPCHK(c, hipMemsetAsync(w + oticket, 0, 2 * sizeof(int), c->stream));
+    HIPCHK(c, hipMemsetAsync(w + oout, 0, (size_t)ST * 73, c->stream));      // what a stage does not produce stays zero
+    ChainSmallArgs a;
+    a.P = c->dp; a.B = B; a.R = R;
+    a.P0s = (const double *)(w + oP); a.q0s = (const double *)(w + oq); a.r0s = (const double *)(w + or0);
+    a.rhos = any_admm ? (const double *)(w + orho) : nullptr; a.Minvs = any_admm ? (const double *)(w + oM) : nullptr;
+    a.X0 = generate ? nullptr : (const double *)(w + oX0);
+    a.cons = cons ? (const double *)(w + ocons) : nullptr;
+    a.generate = generate ? 1 : 0; a.nstages = nstages;
+    a.seed = seed; a.seed_stride = seed_stride; a.first_index = first_index;
+    a.ticket = (int *)(w + oticket);
+    a.X = (double *)(w + oX);
+    char *o = w + oout;
+    const size_t a8 = (size_t)ST * 8;      // one array of 8-byte entries
+    for (int s = 0; s < CHAIN_MAX_STAGES; s++) {
+        ChainStage &g = a.st[s];
+        memset(&g, 0, sizeof(g));
+        if (s >= nstages) continue;
+        g.method = stages[s].method; g.phase1 = stages[s].phase1 ? 1 : 0; g.num_iters = stages[s].num_iters;
+        g.tol = stages[s].tol; g.viol_tol = stages[s].viol_tol; g.viol_lim = stages[s].viol_lim;
+        const size_t r8 = (size_t)s * T * 8;
+        g.sweeps1 = (int64_t *)(o + r8); g.sweeps2 = (int64_t *)(o + a8 + r8); g.visits2 = (int64_t *)(o + 2 * a8 + r8);
+        g.accepted2 = (int64_t *)(o + 3 * a8 + r8); g.iters1 = (int64_t *)(o + 4 * a8 + r8); g.iters2 = (int64_t *)(o + 5 * a8 + r8);
+        g.f0 = (double *)(o + 6 * a8 + r8); g.maxviol = (double *)(o + 7 * a8 + r8);
+        g.status1 = (int *)(o + 8 * a8 + r8 / 2); g.status2 = (int *)(o + 8 * a8 + a8 / 2 + r8 / 2);
+        g.ran2 = (uint8_t *)(o + 9 * a8 + r8 / 8);
+    }
+    const int maxc = c->maxc <= 1 ? 1 : 4;
+    const int cap = chain_small_workgroups(n, maxc, cons ? m : 0, B * R, c->device);
+    if (cap < 1) return fail(c, QCQPMI_EHIP, "chain_small_batch_run: occupancy query failed: %s", hipGetErrorString((hipError_t)(-cap)));
+    const TicketPlan plan = ticket_partition(B, R, cap, 4);      // workgroups of four waves
+    a.RC = plan.RC; a.chunks = plan.chunks;
+    (void)hipEventRecord(c->timers[2].beg, c->stream);
+    const hipError_t qe = (hipError_t)chain_small_launch(a, maxc, plan.wgs, c->stream);
+    (void)hipEventRecord(c->timers[2].end, c->stream);
+    c->timers[2].valid = true;
+    if (qe != hipSuccess) return fail(c, QCQPMI_EHIP, "chain_small_batch_run: %s", hipGetErrorString(qe));
+    c->last_cd2_kernel = chain_small_name(maxc, cons != nullptr);
+    const ChainStage &last = a.st[nstages - 1];
+    if ((rc = select_batch_best(c, name, w, best, last.f0, last.maxviol, a.X, B, R, n, select_tol))) return rc;
+    std::vector<char> hout((size_t)ST * 73);      // (megabytes of fresh pages: touched while the kernel runs)
+    if ((rc = check_symmetric(c, w + oticket, "chain_small_batch_run: a matrix P0_b or Minv_b is not symmetric (or holds a NaN)"))) return rc;
+    HIPCHK(c, hipMemcpyAsync(hout.data(), o, hout.size(), hipMemcpyDeviceToHost, c->stream));
+    if (X) HIPCHK(c, hipMemcpyAsync(X, a.X, (size_t)T * n * 8, hipMemcpyDeviceToHost, c->stream));
+    if ((rc = fetch_batch_best(c, w, best, B, n))) return rc;
+    const char *h = hout.data();
+    void *const wide[8] = {st_sweeps1, st_sweeps2, st_visits2, st_accepted2, st_iters1, st_iters2, st_f0, st_maxviol};
+    for (size_t k = 0; k < 8; k++) if (wide[k]) memcpy(wide[k], h + k * a8, a8);
+    if (st_status1) memcpy(st_status1, h + 8 * a8, a8 / 2);
+    if (st_status2) memcpy(st_status2, h + 8 * a8 + a8 / 2, a8 / 2);
+    if (st_ran_phase2) memcpy(st_ran_phase2, h + 9 * a8, (size_t)ST);
+    const size_t l8 = (size_t)(nstages - 1) * T * 8;
+    if (f0) memcpy(f0, h + 6 * a8 + l8, (size_t)T * 8);
+    if (maxviol) memcpy(maxviol, h + 7 * a8 + l8, (size_t)T * 8);
+    return 0;
+}
+
 // ---- the setup of improve(ADMM) on the device (admm_setup.h): rho_b by the reference's rule (rho == nullptr) or the caller's, and
 // Minv_b = (2 (P0_b + rho_b m I))^-1, both from one eigendecomposition per problem.  n <= ADMM_SETUP_SMALL_MAXN runs the narrow kernel
 int admm_setup_batch(qcqpmi_ctx *c, int64_t B, const double *P0s, const double *rho, int max_sweeps, double tol, double *rhos, double *lambda_min,
@@ -494,6 +606,19 @@ int qcqpmi_admm_batch_run(qcqpmi_ctx *c, int64_t B, const double *P0s, const dou
                           double *best_maxviol, double *best_x) {
     return admm_small_batch(c, ADMM_WIDE_MAXN, B, P0s, q0s, r0s, cons, rhos, Minvs, R, generate, X0, phase1, num_iters, tol, viol_lim, seed, seed_stride,
                             first_index, select_tol, iters1, iters2, f0, maxviol, X, best_index, best_f0, best_maxviol, best_x);
+}
+
+// ---- improve([method, ...]) for B small problems (n <= 64): up to four stages of CD or ADMM in one launch (chain_small.h)
+int qcqpmi_chain_small_batch_run(qcqpmi_ctx *c, int64_t B, const double *P0s, const double *q0s, const double *r0s, const double *cons,
+                                 const double *rhos, const double *Minvs, int64_t R, int generate, const double *X0, int nstages,
+                                 const qcqpmi_chain_stage *stages, uint64_t seed, uint64_t seed_stride, uint64_t first_index,
+                                 double select_tol, int64_t *st_sweeps1, int64_t *st_sweeps2, int64_t *st_visits2, int64_t *st_accepted2,
+                                 uint8_t *st_ran_phase2, int *st_status1, int *st_status2, int64_t *st_iters1, int64_t *st_iters2,
+                                 double *st_f0, double *st_maxviol, double *f0, double *maxviol, double *X, int64_t *best_index,
+                                 double *best_f0, double *best_maxviol, double *best_x) {
+    return chain_small_batch(c, B, P0s, q0s, r0s, cons, rhos, Minvs, R, generate, X0, nstages, stages, seed, seed_stride, first_index, select_tol,
+                             st_sweeps1, st_sweeps2, st_visits2, st_accepted2, st_ran_phase2, st_status1, st_status2, st_iters1, st_iters2,
+                             st_f0, st_maxviol, f0, maxviol, X, best_index, best_f0, best_maxviol, best_x);
 }
 
 // ---- rhos and Minvs of the two calls above from one eigendecomposition per problem on the device (admm_setup.h), 1 <= n <= 128

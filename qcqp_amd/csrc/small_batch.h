@@ -1,4 +1,5 @@
-// Small-problem batch: what the batch kernels (cd_small.hip, admm_small.hip, sdr_small.hip) and their drivers (capi_small.hip) share.
+// Small-problem batch: what the batch kernels (cd_small.hip, admm_small.hip, chain_small.hip, sdr_small.hip) and their drivers
+// (capi_small.hip) share.  chain_small.hip runs the chain frame at the end of this file, the ticket frame with stages.
 //
 // The ticket frame.  A persistent workgroup draws a ticket -- a problem b and a chunk [r_lo, r_hi) of its R restarts -- from a global
 // counter (an ordinary atomic add), stages the problem's LDS image once
@@ -100,6 +101,60 @@ __device__ __attribute__((always_inline)) inline void small_ticket_frame(Args &a
             k = __builtin_amdgcn_readfirstlane(k);
             if (r_lo + k >= r_hi) break;
             restart(As, qs, b, r_lo + k, lane);
+        }
+    }
+}
+
+// The chain frame (chain_small.hip): the ticket of small_ticket_frame, worked through a.nstages STAGES one after the other.  Every stage
+// has an image of its own in the same LDS (its matrix, q0_b; the [3][m] coefficients are staged once per ticket) and runs every restart
+// of the chunk once; restart o of stage s > 0 starts from the point restart o of stage s - 1 wrote to global memory, perhaps by another
+// wave of this workgroup.  Per stage: barrier -- staging -- barrier -- scan -- the waves take the restarts from the LDS counter.  The
+// barrier that opens stage s > 0 is the hand-over: every wave has waited for its own stores of stage s - 1 (s_waitcnt vmcnt(0)) before
+// it arrives, and the loads of stage s are issued after it, by waves of the same workgroup through the same vector L1.
+// No flags, no spinning: a wave waits for nothing but these barriers; a workgroup moves on to the next stage of ITS ticket whatever the
+// other workgroups are doing.
+//   stage(s, off, As, nn, tid, nt)            copies stage s's matrix of problem b into the image; returns the second matrix the restarts
+//                                             read from global memory (a const double *, nullptr: none), which the scan covers too;
+//   restart(s, As, qs, cs, b, r, lane)        one restart of stage s, by one wave; cs: the staged coefficients (PC), p then q then r.
+// `a` is not written (the PC view of the lists is built by the caller from cs): its stage table stays in the kernel-argument segment.
+template <bool PC, class Args, class Stage, class Restart>
+__device__ __attribute__((always_inline)) inline void small_chain_frame(const Args &a, double *lds, int nt, Stage stage, Restart restart) {
+    const int n = (int)a.P.n, nn = n * n, m = PC ? (int)a.P.m : 0;
+    double *As = lds, *qs = lds + nn;
+    double *cs = qs + n;             // PC: [3][m] the staged coefficients, p then q then r
+    int *ctl = (int *)(cs + 3 * m);  // [0] the workgroup's ticket, [1] next restart of its chunk in the running stage
+    const int *cidx = a.P.cidx;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int64_t tickets = a.B * a.chunks;
+    for (;;) {
+        __syncthreads();             // every wave is done with the LDS image of the previous ticket
+        if (tid == 0) ctl[0] = __hip_atomic_fetch_add(a.ticket, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __syncthreads();
+        const int64_t tk = ctl[0];
+        if (tk >= tickets) break;
+        const int64_t b = tk / a.chunks, r_lo = (tk % a.chunks) * a.RC;
+        const int64_t r_hi = r_lo + a.RC < a.R ? r_lo + a.RC : a.R;
+        const int64_t bn = b * n;    // problem b's offset in q0s; bn n: in the [B][n][n] arrays
+        for (int s = 0; s < a.nstages; s++) {
+            if (s > 0) {
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // this wave's points of stage s - 1 have left it
+                __syncthreads();     // the hand-over; every wave is done with the image of stage s - 1
+            }
+            if (tid == 0) ctl[1] = 0;
+            const double *G = stage(s, bn * n, As, nn, tid, nt);
+            small_stage_q(qs, a.q0s, bn, n, tid);
+            if constexpr (PC) { if (s == 0) small_stage_cons(cs, a.cons + b * m * 3, cidx, m, tid, nt); }
+            __syncthreads();
+            bool asym = small_asym_scan(As, nullptr, n, nn, tid, nt);
+            if (G) asym = asym || small_asym_scan(G, nullptr, n, nn, tid, nt);
+            if (asym) a.ticket[1] = 1;
+            for (;;) {
+                int k = 0;
+                if (lane == 0) k = atomicAdd(&ctl[1], 1);
+                k = __builtin_amdgcn_readfirstlane(k);
+                if (r_lo + k >= r_hi) break;
+                restart(s, As, qs, cs, b, r_lo + k, lane);
+            }
         }
     }
 }

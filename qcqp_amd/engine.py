@@ -430,6 +430,57 @@ class Engine(object):
             out[k] = out[k].reshape(B, R)
         return out
 
+    CHAIN_CD, CHAIN_ADMM = 0, 1          # qcqpmi_chain_stage.method
+    CHAIN_MAX_STAGES, CHAIN_MAX_N = 4, 64
+    _CHAIN_CD_KEYS = ('sweeps1', 'sweeps2', 'visits2', 'accepted2', 'ran_phase2', 'status1', 'status2')
+    _CHAIN_ADMM_KEYS = ('iters1', 'iters2')
+
+    def chain_small_batch_run(self, P0s, q0s, r0s, R, stages, rhos=None, Minvs=None, X0=None, seed=0, seed_stride=1, first_index=0,
+                              select_tol=1e-4, want_x=True, cons=None):
+        """A chain of improve methods for B small problems (n <= 64) in ONE launch (qcqpmi_chain_small_batch_run): the arguments of
+        cd_small_batch_run, and ``stages`` -- 1 to 4 dictionaries with 'method' (Engine.CHAIN_CD or Engine.CHAIN_ADMM), 'phase1',
+        'num_iters', 'tol' and 'viol_tol' (CD) or 'viol_lim' (ADMM) -- and, where a stage is ADMM, rhos (B,) and Minvs (B, n, n) as
+        admm_small_batch_run takes them.  Stage 0 starts from the keyed normals or X0, stage s > 0 from the points of stage s - 1;
+        restart (b, r) of every stage is bit for bit what cd_small_batch_run / admm_small_batch_run give when called stage by stage
+        with X of one as X0 of the next.  Returns the dictionary of the LAST stage's kind (cd_small_batch_run's or
+        admm_small_batch_run's keys, arrays (B, R), X (B, R, n) if want_x, best_index / best_f0 / best_maxviol (B,), best_x (B, n))
+        and under 'stages' one dictionary per stage with that stage's records and its f0 / maxviol (B, R).  The resident population
+        is not touched."""
+        name = 'chain_small_batch_run'
+        stages = list(stages)
+        have = rhos is not None and Minvs is not None      # (an ADMM stage without them: the library refuses the call)
+        B, R, P0s, q0s, r0s, X0, cons, extra = self._batch_inputs(name, P0s, q0s, r0s, R, X0, cons, extra=(rhos, Minvs) if have else None)
+        rhos, Minvs = extra if have else (None, None)
+        n, T, S = self.n, max(B * R, 0), len(stages)
+        desc = (_ffi.ChainStage * max(S, 1))()
+        for s, g in enumerate(stages):
+            desc[s] = _ffi.ChainStage(int(g['method']), int(bool(g.get('phase1', True))), int(g['num_iters']), float(g['tol']),
+                                      float(g.get('viol_tol', 1e-2)), float(g.get('viol_lim', 1e4)))
+        rec = dict(sweeps1=np.zeros((S, T), dtype=np.int64), sweeps2=np.zeros((S, T), dtype=np.int64), visits2=np.zeros((S, T), dtype=np.int64),
+                   accepted2=np.zeros((S, T), dtype=np.int64), ran_phase2=np.zeros((S, T), dtype=np.uint8), status1=np.zeros((S, T), dtype=np.int32),
+                   status2=np.zeros((S, T), dtype=np.int32), iters1=np.zeros((S, T), dtype=np.int64), iters2=np.zeros((S, T), dtype=np.int64),
+                   f0=np.zeros((S, T)), maxviol=np.zeros((S, T)))
+        out = dict(f0=np.empty(T), maxviol=np.empty(T), X=np.empty((B, max(R, 0), n)) if want_x else None,
+                   best_index=np.zeros(B, dtype=np.int64), best_f0=np.empty(B), best_maxviol=np.empty(B), best_x=np.zeros((B, n)))
+        c_intp = C.POINTER(C.c_int)
+        self._chk(self.L.qcqpmi_chain_small_batch_run(
+            self.h, B, _dp(P0s), _dp(q0s), _dp(r0s), _dp(cons), _dp(rhos), _dp(Minvs), R, 0 if X0 is not None else 1, _dp(X0), S,
+            C.cast(desc, C.c_void_p), int(seed), int(seed_stride), int(first_index), float(select_tol), _ip(rec['sweeps1']),
+            _ip(rec['sweeps2']), _ip(rec['visits2']), _ip(rec['accepted2']), _bp(rec['ran_phase2']), rec['status1'].ctypes.data_as(c_intp),
+            rec['status2'].ctypes.data_as(c_intp), _ip(rec['iters1']), _ip(rec['iters2']), _dp(rec['f0']), _dp(rec['maxviol']),
+            _dp(out['f0']), _dp(out['maxviol']), _dp(out['X']), _ip(out['best_index']), _dp(out['best_f0']), _dp(out['best_maxviol']),
+            _dp(out['best_x'])))
+        per_stage = []
+        for s, g in enumerate(stages):
+            keys = self._CHAIN_ADMM_KEYS if int(g['method']) == self.CHAIN_ADMM else self._CHAIN_CD_KEYS
+            per_stage.append(dict(((k, rec[k][s].reshape(B, R)) for k in keys + ('f0', 'maxviol')), method=int(g['method'])))
+        out['f0'], out['maxviol'] = out['f0'].reshape(B, R), out['maxviol'].reshape(B, R)
+        for k, v in per_stage[-1].items():
+            if k not in ('f0', 'maxviol', 'method'):
+                out[k] = v
+        out['stages'] = per_stage
+        return out
+
     def admm_batch_setup(self, P0s, rho=None, max_sweeps=30, tol=1e-15):
         """The setup of admm_small_batch_run / admm_batch_run on the device (qcqpmi_admm_batch_setup, n <= 128): for P0s (B, n, n)
         symmetric, ONE launch decomposes every P0_b (Jacobi: max_sweeps, tol as spectral_batch takes them) and returns a dictionary:
