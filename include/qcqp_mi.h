@@ -496,7 +496,13 @@ int qcqpmi_sdr_batch_pc(qcqpmi_ctx *ctx, int64_t B, const double *P0s, const dou
  * mu and complementarity: qcqp_amd.sdr.certify_spectral_batch).
  * Outputs, any may be NULL: x [B][n] = (y - beta / (2 s)) / s; bound [B] = f0(x) recomputed from P0_b, q0_b, r0_b; mu [B];
  * lam [B][n], the eigenvalues of A_b ascending; sweeps [B]; branch [B]: 0 interior, 1 boundary, 2 hard case; status [B]: 0, 1 if
- * Jacobi stopped at max_sweeps, 2 if a result is not finite.
+ * Jacobi stopped at max_sweeps, 2 if a result is not finite or the eigen-solver had no norm to measure against: A_b has a nonzero
+ * entry but |A_b|_F^2 evaluates to 0.0 or is not finite (the point is then NOT a solution; an all-zero A_b is status 0).
+ * Supported magnitudes: the squares of the entries of A_b must neither underflow nor overflow (more precisely, 2^-120 tol^2 |A_b|_F^2
+ * must be a normal number and |A_b|_F^2 finite).  Inside that range multiplying (P0_b, q0_b, r0_b) by a power of two is exact: x,
+ * sweeps, branch and status keep their bits, lam, mu and bound are scaled exactly (an a_pq with a_pq^2 <= 2^-120 tol^2 |A_b|_F^2 is not
+ * rotated, csrc/jacobi_small.h: nothing depends on where an entry underflows).  Repeated eigenvalues slow the sweeps down to linear
+ * convergence (up to 56 sweeps at n = 64 for tol = 1e-15): status 1 at max_sweeps = 30 with lam already exact to rounding.
  * QCQPMI_EUNSUPPORTED: n > 64.  QCQPMI_EINVAL: B < 1, a missing input, agg_stride other than 0 and 2 n + 1, an a_i that is not
  * positive and finite, rho^2 <= 0, a P0_b that is not symmetric.  The call works in a buffer of its own: the resident population,
  * its evaluation, its status codes and qcqpmi_last_cd_kernel stay as they were, whether the call succeeds or is refused. */
@@ -510,7 +516,11 @@ int qcqpmi_spectral_small_batch(qcqpmi_ctx *ctx, int64_t B, const double *P0s, c
  * a pair of columns is rotated where |g_p . g_q| > tol |g_p| |g_q|, the solver stops after the first sweep without a rotation
  * or at max_sweeps; sweeps counts that last sweep), the columns of G end as Q_b, the eigenvalues are the Rayleigh quotients
  * q_k' A_b q_k, and a lane holds two coordinates / eigen-indices.  The secular equation, the hard-case rule and the point are
- * unchanged.  QCQPMI_EUNSUPPORTED: n > 128.  QCQPMI_EINVAL and the rest as for qcqpmi_spectral_small_batch, which still refuses
+ * unchanged.  The supported magnitudes and status 2 are those of qcqpmi_spectral_small_batch (the rotation threshold is relative:
+ * power-of-two scaling is exact wherever the squares of the entries neither underflow nor overflow).  PAST n = 64 AN EXACT HARD CASE
+ * MAY BE REPORTED AS branch == 1: the rounding of gh = Q'g, about n eps |g|, reaches the 2^-46 threshold there, so a g exactly
+ * orthogonal to the lowest eigenspace keeps a component in it; mu is then within rounding of -lam_min and the value is right to
+ * rounding.  QCQPMI_EUNSUPPORTED: n > 128.  QCQPMI_EINVAL and the rest as for qcqpmi_spectral_small_batch, which still refuses
  * n > 64. */
 int qcqpmi_spectral_batch(qcqpmi_ctx *ctx, int64_t B, const double *P0s, const double *q0s, const double *r0s, const double *agg,
                           int64_t agg_stride, int relop_eq, int max_sweeps, double tol, double *x, double *bound, double *mu,
@@ -630,7 +640,10 @@ int qcqpmi_chain_small_batch_run(qcqpmi_ctx *ctx, int64_t B, const double *P0s, 
  *   Minvs[b]      = sum_k u_k u_k' / (2 (lam_k + rhos[b] m)) = (2 (P0_b + rhos[b] m I))^-1, every entry summed in ascending k of the
  *                   solver's order with the product u_ik u_jk formed first: EXACTLY symmetric, as the two run calls require;
  *   sweeps[b]     = Jacobi sweeps;
- *   status[b]     = 0; 1: Jacobi stopped at max_sweeps; 2: lambda_min, rho or an entry of the inverse is not finite; 3: the given
+ *   status[b]     = 0; 1: Jacobi stopped at max_sweeps; 2: lambda_min, rho or an entry of the inverse is not finite (a given rho with
+ *                   lambda_min[b] + m rho == 0 exactly: 1 / 0), or P0_b has a nonzero entry but |P0_b|_F^2 evaluates to 0.0 or is not
+ *                   finite -- the squares of the entries of P0_b must neither underflow nor overflow; inside that range a
+ *                   power-of-two scaling of P0_b scales lambda_min exactly --; 3: the given
  *                   rho is too small (lambda_min[b] + m rho < 0: the reference's test; Minvs[b] is then all zero).  A rho that is
  *                   too small is NOT an error of the call: the caller words the reference's message from lambda_min[b].
  * The rule jumps by a factor of about two at lambda_min = 0; for a singular positive semidefinite P0_b rounding decides the branch,

@@ -97,7 +97,7 @@ __device__ inline void as_problem(const AdmmSetupArgs &a, double *lds, int64_t b
         a.rhos[b] = rho;
         a.lambda_min[b] = lmin;
         a.sweeps[b] = jr.sweeps;
-        a.status[b] = !form ? 3 : (bad ? 2 : (jr.converged ? 0 : 1));
+        a.status[b] = !form ? 3 : ((bad || jr.degenerate) ? 2 : (jr.converged ? 0 : 1));
     }
 }
 
@@ -207,7 +207,7 @@ __device__ inline void asw_problem(const AdmmSetupArgs &a, double *lds, int64_t 
         a.rhos[b] = rho;
         a.lambda_min[b] = lmin;
         a.sweeps[b] = jr.sweeps;
-        a.status[b] = !form ? 3 : (bad ? 2 : (jr.converged ? 0 : 1));
+        a.status[b] = !form ? 3 : ((bad || jr.degenerate) ? 2 : (jr.converged ? 0 : 1));
     }
 }
 

@@ -9,6 +9,9 @@
 // at G J = U diag(mu): the columns, normalised, are the eigenvectors.  c = 2 |A|_F puts every eigenvalue of G into [c / 2, 3 c / 2]
 // (|lam_k(A)| <= |A|_F): G is never singular and its condition number is at most 3, so the number of sweeps does not depend on the
 // spectrum of A.  |A|_F == 0 (fro2 == 0.0) is a case of its own: Q = I, no sweep (G would be 0 and the normalisation 0 / 0).
+// Magnitude: the squares of the entries must neither all underflow nor overflow.  A matrix with a nonzero entry whose fro2 comes out
+// as 0.0 takes that exit too, and one whose fro2 is not finite gets c = inf: `degenerate` reports both, and the callers turn it
+// into status 2 (what comes back in G is NOT a set of eigenvectors).
 // The eigenvalues are NOT read off the column norms (|g_k| - c carries the rounding of c, measured 1e-13 of max |lam| at n = 128 in
 // the NumPy restatement): the caller forms Rayleigh quotients u_k' A u_k from its own copy of A.
 //
@@ -43,7 +46,7 @@ constexpr int JACOBI_WIDE_BLOCK = 8;         // rows whose LDS reads are in flig
 __host__ __device__ inline int jacobi_wide_stride(int n2) { return n2 | 1; }
 __host__ __device__ inline size_t jacobi_wide_doubles(int n2) { return (size_t)n2 * jacobi_wide_stride(n2); }
 
-struct JacobiWideResult { int sweeps; bool converged; double fro2; };
+struct JacobiWideResult { int sweeps; bool converged; bool degenerate; double fro2; };
 
 // Called by all 64 lanes of a one-wave workgroup; the caller's writes to G are ordered by the barrier at the top.
 __device__ inline JacobiWideResult jacobi_wide(double *G, int n2, int str, int lane, int max_sweeps, double tol) {
@@ -53,11 +56,13 @@ __device__ inline JacobiWideResult jacobi_wide(double *G, int n2, int str, int l
     res.converged = false;
     __syncthreads();
     double f[2] = {0.0, 0.0};
+    bool nz = false;
     for (int h = 0; h < 2; h++) {
         const int k = lane + 64 * h;
-        if (k < n2) for (int i = 0; i < n2; i++) { const double a = G[k * str + i]; f[h] += a * a; }
+        if (k < n2) for (int i = 0; i < n2; i++) { const double a = G[k * str + i]; f[h] += a * a; nz = nz || a != 0.0; }
     }
     res.fro2 = wave_sum_tree(f[0] + f[1]);
+    res.degenerate = !(res.fro2 < __builtin_huge_val()) || (res.fro2 == 0.0 && __ballot(nz) != 0);
     if (res.fro2 == 0.0) {
         for (int h = 0; h < 2; h++) {
             const int k = lane + 64 * h;

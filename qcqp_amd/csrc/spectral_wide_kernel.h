@@ -199,7 +199,7 @@ __device__ inline void spw_problem(const SpectralSmallArgs &a, double *lds, int6
         a.mu[b] = mu;
         a.sweeps[b] = jr.sweeps;
         a.branch[b] = branch;
-        a.status[b] = bad ? 2 : (jr.converged ? 0 : 1);
+        a.status[b] = (bad || jr.degenerate) ? 2 : (jr.converged ? 0 : 1);
     }
 }
 

@@ -486,7 +486,7 @@ class Engine(object):
         symmetric, ONE launch decomposes every P0_b (Jacobi: max_sweeps, tol as spectral_batch takes them) and returns a dictionary:
         lambda_min (B,); rho (B,) -- the reference's rule (qcqp.py:270-277) applied to lambda_min, bit for bit, or the given rho --;
         Minv (B, n, n) = (2 (P0_b + rho_b m I))^-1, exactly symmetric; sweeps (B,); status (B,) (0; 1: Jacobi hit max_sweeps; 2: not
-        finite; 3: the given rho is too small for the problem, lambda_min + m rho < 0, and its Minv is zero).  What
+        finite, or |P0_b|_F^2 underflows to 0.0 or overflows for a nonzero P0_b; 3: the given rho is too small for the problem, lambda_min + m rho < 0, and its Minv is zero).  What
         qcqp_amd.batch.admm_rhos and admm_minvs compute on the host.  The resident population is not touched."""
         P0s = np.ascontiguousarray(P0s, dtype=np.float64)
         B, n = int(P0s.shape[0]) if P0s.ndim == 3 else 0, self.n
@@ -618,7 +618,8 @@ class Engine(object):
         that every problem's constraints sum to, or (B, 2 n + 1): per problem; relop '==' or '<='.  Every problem's trust-region
         problem is solved exactly: a Jacobi eigendecomposition (max_sweeps, tol: off(A) <= tol |A|_F) and one secular equation.
         Returns a dictionary: x (B, n), bound (B,) = f0(x), mu (B,), lam (B, n) ascending, sweeps (B,), branch (B,) (0 interior, 1
-        boundary, 2 hard case), status (B,) (0; 1: Jacobi hit max_sweeps; 2: not finite).  The resident population is not touched."""
+        boundary, 2 hard case), status (B,) (0; 1: Jacobi hit max_sweeps -- repeated eigenvalues can need up to 60 sweeps at n = 64 --;
+        2: not finite, or |A_b|_F^2 underflows to 0.0 or overflows for a nonzero A_b).  The resident population is not touched."""
         return self._spectral_batch('spectral_small_batch', P0s, q0s, r0s, agg, relop, max_sweeps, tol)
 
     def spectral_batch(self, P0s, q0s, r0s, agg, relop, max_sweeps=30, tol=1e-15):

@@ -99,6 +99,7 @@ def restate(P0, m, rho=None, max_sweeps=MAX_SWEEPS, tol=TOL):
         Minv = Minv + (U[:, k][:, None] * U[:, k][None, :]) * w[k]
     out['Minv'] = Minv
     finite = np.isfinite(lmin) and np.isfinite(rho_b) and np.all(np.isfinite(w)) and np.all(np.isfinite(Minv))
+    finite = finite and not (sc.degenerate_norm(P0) if n <= 64 else wc.degenerate_norm(P0))      # (the solvers' `degenerate`: status 2)
     out['status'] = 0 if (finite and conv) else (2 if not finite else 1)
     return out
 

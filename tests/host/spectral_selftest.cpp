@@ -114,7 +114,8 @@ static int host_jacobi(std::vector<double> &A, std::vector<double> &Q, int n2, i
             for (int k = 0; k < n2 / 2; k++) {
                 round_robin_pair(n2, round, k, &P[k], &Qi[k]);
                 app[k] = A[P[k] * n2 + P[k]]; aqq[k] = A[Qi[k] * n2 + Qi[k]]; apq[k] = A[P[k] * n2 + Qi[k]];
-                rot[k] = jacobi_rotation(app[k], aqq[k], apq[k]);
+                const JacobiRot id = {1.0, 0.0, 0.0};      // (a negligible a_pq is not rotated: JACOBI_NEGLIGIBLE2 of jacobi_small.h)
+                rot[k] = apq[k] * apq[k] <= 0x1p-120 * (tol * tol * fro2) ? id : jacobi_rotation(app[k], aqq[k], apq[k]);
             }
             for (int k = 0; k < n2 / 2; k++) {
                 const double c = rot[k].c, s = rot[k].s;

@@ -20,6 +20,7 @@ HARD_THR = 2.0 ** -46
 SECULAR_RTOL = 2.0 ** -50
 SECULAR_MAX_ITERS = 200
 MAX_SWEEPS, TOL = 30, 1e-15
+NEGLIGIBLE2 = 2.0 ** -120
 SIZES = (1, 2, 3, 31, 32, 33, 63, 64)
 
 
@@ -116,6 +117,8 @@ def jacobi(A, max_sweeps=MAX_SWEEPS, tol=TOL):
         for pq in rounds:
             p, q = pq[:, 0], pq[:, 1]
             app, aqq, apq = As[p, p].copy(), As[q, q].copy(), As[p, q].copy()
+            with np.errstate(under='ignore', over='ignore'):      # (a negligible a_pq is not rotated: JACOBI_NEGLIGIBLE2 of jacobi_small.h)
+                apq = np.where(apq * apq <= NEGLIGIBLE2 * stop2, 0.0, apq)
             c, s, t = rotation(app, aqq, apq)
             cc, ss = c[:, None], s[:, None]
             rp, rq = As[p, :].copy(), As[q, :].copy()
@@ -131,6 +134,14 @@ def jacobi(A, max_sweeps=MAX_SWEEPS, tol=TOL):
             As[q[on], p[on]] = 0.0
         sweeps += 1
     return np.diag(As)[:n].copy(), Qs[:n, :n].copy(), sweeps, converged
+
+
+def degenerate_norm(A):
+    """JacobiResult::degenerate of csrc/jacobi_small.h: A has a nonzero entry but |A|_F^2, summed as the solver sums it, comes out as
+    0.0 (every square underflows) or is not finite.  The stop test of the solver means nothing then: status 2."""
+    with np.errstate(over='ignore', under='ignore'):
+        fro2 = tree_sum(_seq_colsum(A * A))
+    return bool(not fro2 < np.inf or (fro2 == 0.0 and np.any(A != 0.0)))
 
 
 def _seq_colsum(M):
@@ -238,7 +249,8 @@ def restate(P0, q0, r0, agg, relop, max_sweeps=MAX_SWEEPS, tol=TOL):
     x = (y - beta / (2.0 * s)) / s
     px = _seq_matvec_rows(P0.T, x)
     bound = tree_sum(x * (px + q0)) + r0
-    return dict(x=x, bound=bound, mu=mu, lam=lam[order], sweeps=sweeps, branch=branch, status=0 if conv else 1, y=y, rho=rho, A=A, g=g)
+    status = 2 if degenerate_norm(A) else (0 if conv else 1)
+    return dict(x=x, bound=bound, mu=mu, lam=lam[order], sweeps=sweeps, branch=branch, status=status, y=y, rho=rho, A=A, g=g)
 
 
 # ------------------------------------------------------------------ the independent solver

@@ -68,6 +68,14 @@ def jacobi_wide(A, max_sweeps=MAX_SWEEPS, tol=TOL):
     return G / np.sqrt(np.einsum('ij,ij->j', G, G)), sweeps, converged, c
 
 
+def degenerate_norm(A):
+    """JacobiWideResult::degenerate of csrc/jacobi_wide.h: A has a nonzero entry but fro2, summed as the solver sums it, comes out as
+    0.0 (the solver's zero-matrix exit, taken wrongly) or is not finite (c = inf).  Status 2."""
+    with np.errstate(over='ignore', under='ignore'):
+        fro2 = wave_sum2(np.sum(A * A, axis=0))
+    return bool(not fro2 < np.inf or (fro2 == 0.0 and np.any(A != 0.0)))
+
+
 def secular_root(gh, d, rho, lo, hi):
     """secular_root of csrc/spectral_solve.h with the sums of the wide kernel."""
     rho2 = rho * rho
@@ -154,7 +162,8 @@ def restate(P0, q0, r0, agg, relop, max_sweeps=MAX_SWEEPS, tol=TOL):
         y = y + (-tau if lead < 0.0 else tau) * v
     x = (y - beta / (2.0 * s)) / s
     bound = wave_sum2(x * (P0.T.dot(x) + q0)) + r0
-    return dict(x=x, bound=bound, mu=mu, lam=lam[order], sweeps=sweeps, branch=branch, status=0 if conv else 1, y=y, rho=rho, A=A, g=g, U=U2)
+    status = 2 if degenerate_norm(A) else (0 if conv else 1)
+    return dict(x=x, bound=bound, mu=mu, lam=lam[order], sweeps=sweeps, branch=branch, status=status, y=y, rho=rho, A=A, g=g, U=U2)
 
 
 @functools.lru_cache(maxsize=None)
