@@ -57,64 +57,22 @@ AdmmSmallKernel admm_small_pick(int64_t n, int maxc, bool pc) {
 
 }  // namespace
 
-// QCQPMI_ADMM_WIDE_THREADS = 64 .. 512 (a multiple of 64): that workgroup size for the wide kernels instead of the rule below -- for
-// measuring the rule (tools/bench_admm_batch.py --wide-threads); results do not depend on it
-static int admm_wide_threads_asked() {
-    static const int asked = [] {
-        const char *v = getenv("QCQPMI_ADMM_WIDE_THREADS");
-        const int t = v ? atoi(v) : 0;
-        return (t >= 64 && t <= ADMM_WIDE_THREADS && t % 64 == 0) ? t : 0;
-    }();
+static int admm_wide_threads_asked() {      // read once
+    static const int asked = small_threads_asked("QCQPMI_ADMM_WIDE_THREADS", ADMM_WIDE_THREADS);
     return asked;
 }
 
 int admm_small_workgroups(int64_t n, int maxc, int64_t pc_entries, int64_t tickets, int device, int *threads) {
-    int per = 0;
-    hipError_t e;
-    const size_t lds = small_image_bytes(n, pc_entries);
-    const AdmmSmallKernel k = admm_small_pick(n, maxc, pc_entries > 0);
-    *threads = 256;
-    if (n > ADMM_SMALL_MAXN) {      // the image passes 64 KB from n = 91
-        e = hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return -(int)e;
-        // the workgroup that puts more waves on a CU (cd_small_workgroups has the same rule)
-        const int asked = admm_wide_threads_asked();
-        int per_small = 0, per_large = 0;
-        e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_small, k, asked ? asked : 256, lds);
-        if (e != hipSuccess) return -(int)e;
-        per = per_small;
-        *threads = asked ? asked : 256;
-        if (!asked) {
-            e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_large, k, ADMM_WIDE_THREADS, lds);
-            if (e != hipSuccess) return -(int)e;
-            if (per_large * ADMM_WIDE_THREADS >= per_small * 256) { per = per_large; *threads = ADMM_WIDE_THREADS; }
-        }
-    } else {
-        e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, k, 256, lds);
-        if (e != hipSuccess) return -(int)e;
-    }
-    return small_workgroup_cap(device, per, tickets);
+    const bool wide = n > ADMM_SMALL_MAXN;
+    return small_ticket_workgroups((const void *)admm_small_pick(n, maxc, pc_entries > 0), small_image_bytes(n, pc_entries), tickets, device,
+                                   wide ? ADMM_WIDE_THREADS : 0, wide ? admm_wide_threads_asked() : 0, threads);
 }
 
 int admm_small_launch(const AdmmSmallArgs &a, int maxc, int wgs, int threads, hipStream_t st) {
     const bool pc = a.cons != nullptr;
-    const size_t lds = small_image_bytes(a.P.n, pc ? a.P.m : 0);
-    const AdmmSmallKernel k = admm_small_pick(a.P.n, maxc, pc);
-    if (a.P.n > ADMM_SMALL_MAXN) {
-        const hipError_t e = hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return (int)e;
-    }
-    hipLaunchKernelGGL(k, dim3((unsigned)wgs), dim3((unsigned)threads), lds, st, a);
-    return (int)hipGetLastError();
+    return small_launch(admm_small_pick(a.P.n, maxc, pc), small_image_bytes(a.P.n, pc ? a.P.m : 0), a, wgs, threads, a.P.n > ADMM_SMALL_MAXN, st);
 }
 
-const char *admm_small_name(int maxc, bool pc, bool wide) {
-    if (wide) {
-        if (pc) return maxc <= 1 ? "admm_small_kernel<1,pc,w2>" : "admm_small_kernel<4,pc,w2>";
-        return maxc <= 1 ? "admm_small_kernel<1,w2>" : "admm_small_kernel<4,w2>";
-    }
-    if (pc) return maxc <= 1 ? "admm_small_kernel<1,pc>" : "admm_small_kernel<4,pc>";
-    return maxc <= 1 ? "admm_small_kernel<1>" : "admm_small_kernel<4>";
-}
+const char *admm_small_name(int maxc, bool pc, bool wide) { return batch_kernel_name<AdmmSmallArgs>("admm_small_kernel", maxc, pc, wide); }
 
 }  // namespace qcqpmi

@@ -1,12 +1,17 @@
 // Small-problem batch part of the C ABI: B small problems over the context's constraint structure in ONE
 // persistent launch of cd_small.hip, admm_small.hip, chain_small.hip, sdr_small.hip or spectral_small.hip (narrow and wide kernel; the ADMM setup kernels live there too).  A call works in a device buffer of its own
 // (sb_work for CD and ADMM, ss_work for SDR, SPECTRAL and the ADMM setup): the resident population, its evaluation, its status codes and an installed ADMM basis are not touched,
-// whether the call succeeds or is refused.  The shared steps come first; a driver is its argument struct, its launch and its outputs.
+// whether the call succeeds or is refused.
+// A driver is: its argument checks, in their order, with their texts; ONE declaration of every array of the call on a BatchCall
+// (batch_call.h: the layout of the work buffer, the copies, the ticket, the per-restart records and the ticket arithmetic, all run on
+// the CPU by tests/host/batch_call_selftest.cpp); the scalars of its argument struct; its launch through the unit that owns the
+// kernel (launchers: small_batch.h).  What the drivers share comes first.
 // Host code only: the launcher headers, and the launch of the core's selection kernel through capi_ctx.h.
 #include <cmath>
 #include <cstring>
 
 #include "capi_ctx.h"
+#include "batch_call.h"
 #include "cd_small.h"
 #include "admm_small.h"
 #include "chain_small.h"
@@ -18,18 +23,6 @@
 using namespace qcqpmi;
 
 namespace {
-
-// offsets into a work buffer, every piece 256-byte aligned
-struct Carve {
-    size_t off = 0;
-    size_t take(size_t bytes) { const size_t o = off; off += (bytes + 255) / 256 * 256; return o; }
-};
-
-// host -> work buffer; a missing array or an empty piece is skipped
-int stage_in(qcqpmi_ctx *c, void *dst, const void *src, size_t bytes) {
-    if (src && bytes) HIPCHK(c, hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, c->stream));
-    return 0;
-}
 
 int check_batch_context(qcqpmi_ctx *c, const char *name) {
     const int rc = check_ready(c, false);
@@ -55,59 +48,91 @@ int check_batch_cons(qcqpmi_ctx *c, const char *name, const double *cons, int64_
     return 0;
 }
 
-// Tickets of a launch over B problems with R restarts each on `wgs` resident workgroups of `waves` wavefronts: whole problems when
-// there are enough of them to fill the device, else chunks of RC consecutive restarts, at least one restart per wave of a workgroup.
-struct TicketPlan { int64_t RC, chunks; int wgs; };      // restarts per ticket, tickets per problem, workgroups (at most one per ticket)
-
-TicketPlan ticket_partition(int64_t B, int64_t R, int wgs, int64_t waves) {
-    int64_t chunks = B >= wgs ? 1 : (wgs + B - 1) / B;
-    if (chunks > (R + waves - 1) / waves) chunks = (R + waves - 1) / waves;
-    TicketPlan t;
-    t.RC = (R + chunks - 1) / chunks;
-    t.chunks = (R + t.RC - 1) / t.RC;
-    t.wgs = wgs > B * t.chunks ? (int)(B * t.chunks) : wgs;
-    return t;
+int check_batch_rhos(qcqpmi_ctx *c, const char *name, const double *rhos, int64_t B) {
+    for (int64_t b = 0; b < B; b++)
+        if (!(rhos[b] > 0.0) || !std::isfinite(rhos[b])) return fail(c, QCQPMI_EINVAL, "%s: rho of problem %lld is not positive and finite", name, (long long)b);
+    return 0;
 }
 
-// waits for the launch that has just been enqueued and fails with `what` if its ticket[1] is set: a matrix was not symmetric
-int check_symmetric(qcqpmi_ctx *c, const char *ticket, const char *what) {
+// the objectives of the B problems at the head of the work buffer: P0_b, q0_b, r0_b -- and behind P0_b the second matrix of the ADMM
+// paths, Minv_b (Mslot set; Minvs == nullptr: no ADMM stage, no room)
+template <class Args>
+void declare_objectives(BatchCall &f, Args &a, int64_t B, int64_t n, const double *P0s, const double *q0s, const double *r0s,
+                        const double *Minvs = nullptr, const double **Mslot = nullptr) {
+    f.in(P0s, (size_t)B * n * n * 8, &a.P0s);
+    if (Mslot) f.in(Minvs, (size_t)B * n * n * 8, Mslot);
+    f.in(q0s, (size_t)B * n * 8, &a.q0s);
+    f.in(r0s, (size_t)B * 8, &a.r0s);
+}
+
+// cap < 1 from a *_workgroups: -hipError_t
+int occupancy_failed(qcqpmi_ctx *c, const char *name, int cap) {
+    return fail(c, QCQPMI_EHIP, "%s: occupancy query failed: %s", name, hipGetErrorString((hipError_t)(-cap)));
+}
+
+int launch_failed(qcqpmi_ctx *c, const char *name, hipError_t e) { return fail(c, QCQPMI_EHIP, "%s: %s", name, hipGetErrorString(e)); }
+
+// waits for the launch that has just been enqueued and fails if its ticket[1] is set: a matrix was not symmetric (with_minv: the
+// kernel scans Minv_b too)
+int check_symmetric(qcqpmi_ctx *c, const char *name, const int *ticket, bool with_minv) {
     int flags[2] = {0, 0};
     HIPCHK(c, hipMemcpyAsync(flags, ticket, sizeof(flags), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, spin_sync(c->stream));
-    return flags[1] ? fail(c, QCQPMI_EINVAL, "%s", what) : 0;
+    return flags[1] ? fail(c, QCQPMI_EINVAL, "%s: %s is not symmetric (or holds a NaN)", name, with_minv ? "a matrix P0_b or Minv_b" : "an objective matrix P0_b") : 0;
 }
 
-// The best restart of every problem (QCQPForm.better folded over its R restarts, ties -> lowest index): where its pieces lie in the
-// work buffer w, and where the caller wants them (any pointer may be null; none: nothing runs)
+// The best restart of every problem (QCQPForm.better folded over its R restarts, ties -> lowest index): where the caller wants its
+// pieces (any pointer may be null; none: nothing runs), and where they lie in the work buffer
 struct BatchBest {
-    size_t oidx, okey, ox;       // [B][2] int64, [B][2] double, [B][n] double
     int64_t *index;
     double *f0, *maxviol, *x;
+    int64_t *didx = nullptr;                 // [B][2] as select_best_kernel leaves it
+    double *dkey = nullptr, *dx = nullptr;   // [B][2], [B][n]
     bool wanted() const { return index || f0 || maxviol || x; }
+    void declare(BatchCall &f, int64_t B, int64_t n) {
+        f.room((size_t)B * 2 * sizeof(int64_t), &didx);
+        f.room((size_t)B * 2 * sizeof(double), &dkey);
+        f.room((size_t)B * n * 8, &dx);
+    }
 };
 
+// what the three restart calls declare behind their objectives -- the starts, the points, the record block, the ticket, the winners,
+// the per-problem coefficients -- and the scalars their argument structs share
+template <class Args>
+void declare_restarts(qcqpmi_ctx *c, BatchCall &f, Args &a, BatchBest &best, char **records, size_t record_bytes, int64_t B, int64_t R, int generate,
+                      const double *X0, double *X, const double *cons, uint64_t seed, uint64_t seed_stride, uint64_t first_index) {
+    f.in(generate ? nullptr : X0, (size_t)B * R * c->n * 8, &a.X0);
+    f.out(X, (size_t)B * R * c->n * 8, &a.X);
+    f.room(record_bytes, records);
+    f.ticket(&a.ticket);
+    best.declare(f, B, c->n);
+    f.in(cons, (size_t)B * c->m * 24, &a.cons);
+    a.P = c->dp; a.B = B; a.R = R; a.generate = generate ? 1 : 0;
+    a.seed = seed; a.seed_stride = seed_stride; a.first_index = first_index;
+}
+
 // enqueue: one workgroup per problem selects, then one gather of the winners' points
-int select_batch_best(qcqpmi_ctx *c, const char *name, char *w, const BatchBest &b, const double *f0, const double *maxviol, const double *X,
+int select_batch_best(qcqpmi_ctx *c, const char *name, const BatchBest &b, const double *f0, const double *maxviol, const double *X,
                       int64_t B, int64_t R, int64_t n, double select_tol) {
     if (!b.wanted()) return 0;
-    launch_select_best(c, B, f0, maxviol, R, select_tol, (int64_t *)(w + b.oidx), (double *)(w + b.okey));
+    launch_select_best(c, B, f0, maxviol, R, select_tol, b.didx, b.dkey);
     HIPCHK(c, hipGetLastError());
     if (b.x) {
-        HIPCHK(c, hipMemsetAsync(w + b.ox, 0, (size_t)B * n * 8, c->stream));
-        const hipError_t qe = (hipError_t)small_gather_launch(X, n, R, B, (const int64_t *)(w + b.oidx), (double *)(w + b.ox), c->stream);
-        if (qe != hipSuccess) return fail(c, QCQPMI_EHIP, "%s: %s", name, hipGetErrorString(qe));
+        HIPCHK(c, hipMemsetAsync(b.dx, 0, (size_t)B * n * 8, c->stream));
+        const hipError_t qe = (hipError_t)small_gather_launch(X, n, R, B, b.didx, b.dx, c->stream);
+        if (qe != hipSuccess) return launch_failed(c, name, qe);
     }
     return 0;
 }
 
 // fetch (waits for the stream, so for every copy the driver has enqueued before) and hand out
-int fetch_batch_best(qcqpmi_ctx *c, const char *w, const BatchBest &b, int64_t B, int64_t n) {
+int fetch_batch_best(qcqpmi_ctx *c, const BatchBest &b, int64_t B, int64_t n) {
     std::vector<int64_t> bidx(b.wanted() ? (size_t)B * 2 : 0);
     std::vector<double> bkey(bidx.size());
     if (b.wanted()) {
-        HIPCHK(c, hipMemcpyAsync(bidx.data(), w + b.oidx, bidx.size() * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipMemcpyAsync(bkey.data(), w + b.okey, bkey.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-        if (b.x) HIPCHK(c, hipMemcpyAsync(b.x, w + b.ox, (size_t)B * n * 8, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(bidx.data(), b.didx, bidx.size() * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(bkey.data(), b.dkey, bkey.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        if (b.x) HIPCHK(c, hipMemcpyAsync(b.x, b.dx, (size_t)B * n * 8, hipMemcpyDeviceToHost, c->stream));
     }
     HIPCHK(c, spin_sync(c->stream));
     for (int64_t p = 0; p < B && b.wanted(); p++) {
@@ -115,6 +140,38 @@ int fetch_batch_best(qcqpmi_ctx *c, const char *w, const BatchBest &b, int64_t B
         if (b.f0) b.f0[p] = bkey[(size_t)2 * p];
         if (b.maxviol) b.maxviol[p] = bkey[(size_t)2 * p + 1];
     }
+    return 0;
+}
+
+// the end of a call without restarts (SDR, SPECTRAL, the ADMM setup), its launch enqueued: the symmetry check, the outputs, the wait
+int finish_problems(qcqpmi_ctx *c, const char *name, const BatchCall &f, const int *ticket) {
+    const int rc = check_symmetric(c, name, ticket, false);
+    if (rc) return rc;
+    HIPCHK(c, f.download(c->stream));
+    HIPCHK(c, spin_sync(c->stream));
+    return 0;
+}
+
+// The end of a restart call (CD, ADMM, chain), its launch enqueued: the best restart per problem is selected from f0 / maxviol / X on
+// the device; the host copy of the record block is allocated NOW, while the kernels run (megabytes of fresh pages: 18.2 ms against
+// 16.0 when it came after the wait, profiles/r15_small_batch_refactor.md); the first wait is the symmetry check; then the records, the
+// frame's outputs (the points) and the winners come down, and the records (arrays of `count` entries) go to `out`; of the chain's last
+// stage, `last_row` on, f0 / maxviol go to final_f0 / final_maxviol as well.
+template <int WHICH>
+int finish_restarts(qcqpmi_ctx *c, const char *name, const BatchCall &f, const BatchBest &best, const int *ticket, const double *f0, const double *maxviol,
+                    const double *X, int64_t B, int64_t R, int64_t n, double select_tol, const char *records, size_t count, const RecordsOut &out,
+                    size_t last_row = 0, double *final_f0 = nullptr, double *final_maxviol = nullptr) {
+    int rc = select_batch_best(c, name, best, f0, maxviol, X, B, R, n, select_tol);
+    if (rc) return rc;
+    std::vector<char> hout(record_block_bytes<WHICH>(count));
+    if ((rc = check_symmetric(c, name, ticket, (WHICH & REC_ADMM) != 0))) return rc;
+    HIPCHK(c, hipMemcpyAsync(hout.data(), records, hout.size(), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, f.download(c->stream));
+    if ((rc = fetch_batch_best(c, best, B, n))) return rc;
+    unpack_records<WHICH>(out, hout.data(), count, 0, count);
+    RecordsOut final_rows = {};
+    final_rows.f0 = final_f0; final_rows.maxviol = final_maxviol;
+    unpack_records<WHICH>(final_rows, hout.data(), count, last_row, (size_t)(B * R));
     return 0;
 }
 
@@ -141,60 +198,29 @@ int cd_small_batch(qcqpmi_ctx *c, int64_t maxn, bool per_problem, const double *
     }
     HIPCHK(c, hipSetDevice(c->device));
     const int64_t n = c->n, T = B * R;
-    Carve cv;
-    const size_t oP = cv.take((size_t)B * n * n * 8), oq = cv.take((size_t)B * n * 8), or0 = cv.take((size_t)B * 8);
-    const size_t oX0 = cv.take(generate ? 0 : (size_t)T * n * 8), oX = cv.take((size_t)T * n * 8);
-    const size_t oout = cv.take((size_t)T * 57);      // 4 x int64, 2 x double, 2 x int, 1 x uint8 per restart, array after array
-    const size_t oticket = cv.take(2 * sizeof(int));
-    const BatchBest best = {cv.take((size_t)B * 2 * sizeof(int64_t)), cv.take((size_t)B * 2 * sizeof(double)), cv.take((size_t)B * n * 8),
-                            best_index, best_f0, best_maxviol, best_x};
-    const size_t ocons = cv.take(cons ? (size_t)B * m * 24 : 0);
-    HIPCHK(c, c->sb_work.reserve(c->stream, cv.off, false));
-    char *w = c->sb_work;
-    if ((rc = stage_in(c, w + oP, P0s, (size_t)B * n * n * 8)) || (rc = stage_in(c, w + oq, q0s, (size_t)B * n * 8)) ||
-        (rc = stage_in(c, w + or0, r0s, (size_t)B * 8)) || (rc = stage_in(c, w + oX0, generate ? nullptr : X0, (size_t)T * n * 8)) ||
-        (rc = stage_in(c, w + ocons, cons, (size_t)B * m * 24)))
-        return rc;
-    HIPCHK(c, hipMemsetAsync(w + oticket, 0, 2 * sizeof(int), c->stream));
     CdSmallArgs a;
-    a.P = c->dp; a.B = B; a.R = R;
-    a.P0s = (const double *)(w + oP); a.q0s = (const double *)(w + oq); a.r0s = (const double *)(w + or0);
-    a.X0 = generate ? nullptr : (const double *)(w + oX0);
-    a.cons = cons ? (const double *)(w + ocons) : nullptr;
-    a.generate = generate ? 1 : 0; a.phase1 = phase1 ? 1 : 0; a.num_iters = num_iters; a.viol_tol = viol_tol; a.tol = tol;
-    a.seed = seed; a.seed_stride = seed_stride; a.first_index = first_index;
-    a.ticket = (int *)(w + oticket);
-    char *o = w + oout;
-    a.sweeps1 = (int64_t *)o; a.sweeps2 = (int64_t *)(o + 8 * T); a.visits2 = (int64_t *)(o + 16 * T); a.accepted2 = (int64_t *)(o + 24 * T);
-    a.f0 = (double *)(o + 32 * T); a.maxviol = (double *)(o + 40 * T);
-    a.status1 = (int *)(o + 48 * T); a.status2 = (int *)(o + 52 * T); a.ran2 = (uint8_t *)(o + 56 * T);
-    a.X = (double *)(w + oX);
+    BatchCall f;
+    BatchBest best = {best_index, best_f0, best_maxviol, best_x};
+    char *records = nullptr;
+    declare_objectives(f, a, B, n, P0s, q0s, r0s);
+    declare_restarts(c, f, a, best, &records, record_block_bytes<REC_CD>((size_t)T), B, R, generate, X0, X, cons, seed, seed_stride, first_index);
+    HIPCHK(c, f.reserve(c->sb_work, c->stream));
+    HIPCHK(c, f.upload(c->stream));
+    a.phase1 = phase1 ? 1 : 0; a.num_iters = num_iters; a.viol_tol = viol_tol; a.tol = tol;
+    bind_records<REC_CD>(a, records, (size_t)T);
     const int maxc = c->maxc <= 1 ? 1 : 4;
     int threads = 0;
     const int cap = cd_small_workgroups(n, maxc, cons ? m : 0, B * R, c->device, &threads);
-    if (cap < 1) return fail(c, QCQPMI_EHIP, "cd_small_batch_run: occupancy query failed: %s", hipGetErrorString((hipError_t)(-cap)));
+    if (cap < 1) return occupancy_failed(c, name, cap);
     const TicketPlan plan = ticket_partition(B, R, cap, threads / 64);
     a.RC = plan.RC; a.chunks = plan.chunks;
-    (void)hipEventRecord(c->timers[2].beg, c->stream);
+    tic(c, 2);
     const hipError_t qe = (hipError_t)cd_small_launch(a, maxc, plan.wgs, threads, c->stream);
-    (void)hipEventRecord(c->timers[2].end, c->stream);
-    c->timers[2].valid = true;
-    if (qe != hipSuccess) return fail(c, QCQPMI_EHIP, "cd_small_batch_run: %s", hipGetErrorString(qe));
+    toc(c, 2);
+    if (qe != hipSuccess) return launch_failed(c, name, qe);
     c->last_cd2_kernel = cd_small_name(maxc, cons != nullptr, n > CD_SMALL_MAXN);
-    if ((rc = select_batch_best(c, name, w, best, a.f0, a.maxviol, a.X, B, R, n, select_tol))) return rc;
-    std::vector<char> hout((size_t)T * 57);      // (megabytes of fresh pages: touched while the kernel runs)
-    if ((rc = check_symmetric(c, w + oticket, "cd_small_batch_run: an objective matrix P0_b is not symmetric (or holds a NaN)"))) return rc;
-    HIPCHK(c, hipMemcpyAsync(hout.data(), o, hout.size(), hipMemcpyDeviceToHost, c->stream));
-    if (X) HIPCHK(c, hipMemcpyAsync(X, a.X, (size_t)T * n * 8, hipMemcpyDeviceToHost, c->stream));
-    if ((rc = fetch_batch_best(c, w, best, B, n))) return rc;
-    const char *h = hout.data();
-    const size_t n8 = (size_t)T * 8;
-    void *const wide[6] = {sweeps1, sweeps2, visits2, accepted2, f0, maxviol};
-    for (size_t k = 0; k < 6; k++) if (wide[k]) memcpy(wide[k], h + k * n8, n8);
-    if (status1) memcpy(status1, h + 6 * n8, (size_t)T * 4);
-    if (status2) memcpy(status2, h + 6 * n8 + (size_t)T * 4, (size_t)T * 4);
-    if (ran_phase2) memcpy(ran_phase2, h + 7 * n8, (size_t)T);
-    return 0;
+    return finish_restarts<REC_CD>(c, name, f, best, a.ticket, a.f0, a.maxviol, a.X, B, R, n, select_tol, records, (size_t)T,
+                                   {sweeps1, sweeps2, visits2, accepted2, nullptr, nullptr, f0, maxviol, status1, status2, ran_phase2});
 }
 
 // ---- suggest(SDR) for problems of the unit-diagonal family that share the context's constraints x_i^2 == d_i: the relaxation (mixing
@@ -203,6 +229,7 @@ int cd_small_batch(qcqpmi_ctx *c, int64_t maxn, bool per_problem, const double *
 int sdr_small_batch(qcqpmi_ctx *c, int64_t maxn, bool per_problem, const double *ds, int64_t B, const double *P0s, const double *q0s, const double *r0s,
                     int64_t S, int max_sweeps, double tol, uint64_t seed, uint64_t seed_stride, uint64_t first_index, const double *V0s,
                     double *V, double *primal, double *y, int64_t *sweeps, double *X) {
+    const char *name = "sdr_small_batch";
     int rc = check_ready(c, false);
     if (rc) return rc;
     if (c->n > maxn) return fail(c, QCQPMI_EUNSUPPORTED, "sdr_small_batch: n = %lld, the small-problem kernel takes n <= %lld (%s)", (long long)c->n, (long long)maxn,
@@ -221,40 +248,29 @@ int sdr_small_batch(qcqpmi_ctx *c, int64_t maxn, bool per_problem, const double 
     HIPCHK(c, hipSetDevice(c->device));
     const int64_t ns = ds ? B * n : n;      // entries of s
     const size_t vbytes = (size_t)B * N * SDR_SMALL_K * 8;
-    Carve cv;
-    const size_t oP = cv.take((size_t)B * n * n * 8), oq = cv.take((size_t)B * n * 8), or0 = cv.take((size_t)B * 8), os = cv.take((size_t)ns * 8);
-    const size_t oV0 = cv.take(V0s ? vbytes : 0), oV = cv.take(vbytes);
-    const size_t opr = cv.take((size_t)B * 8), oy = cv.take((size_t)B * N * 8), osw = cv.take((size_t)B * 8), oX = cv.take((size_t)B * S * n * 8);
-    const size_t oticket = cv.take(2 * sizeof(int));
-    HIPCHK(c, c->ss_work.reserve(c->stream, cv.off, false));
-    char *w = c->ss_work;
     std::vector<double> sv((size_t)ns);
     for (int64_t i = 0; i < ns; i++) sv[(size_t)i] = sqrt(ds ? ds[i] : c->unit_d[(size_t)i]);
-    if ((rc = stage_in(c, w + oP, P0s, (size_t)B * n * n * 8)) || (rc = stage_in(c, w + oq, q0s, (size_t)B * n * 8)) ||
-        (rc = stage_in(c, w + or0, r0s, (size_t)B * 8)) || (rc = stage_in(c, w + os, sv.data(), (size_t)ns * 8)) ||
-        (rc = stage_in(c, w + oV0, V0s, vbytes)))
-        return rc;
-    HIPCHK(c, hipMemsetAsync(w + oticket, 0, 2 * sizeof(int), c->stream));
-    HIPCHK(c, spin_sync(c->stream));      // sv goes out of scope; the pageable copies above have been staged
     SdrSmallArgs a;
-    a.n = (int)n; a.B = B; a.S = S;
-    a.s = (const double *)(w + os); a.s_stride = ds ? n : 0; a.P0s = (const double *)(w + oP); a.q0s = (const double *)(w + oq); a.r0s = (const double *)(w + or0);
-    a.V0s = V0s ? (const double *)(w + oV0) : nullptr;
+    BatchCall f;
+    declare_objectives(f, a, B, n, P0s, q0s, r0s);
+    f.in(sv.data(), (size_t)ns * 8, &a.s);
+    f.in(V0s, vbytes, &a.V0s);
+    f.out(V, vbytes, &a.V);
+    f.out(primal, (size_t)B * 8, &a.primal);
+    f.out(y, (size_t)B * N * 8, &a.y);
+    f.out(sweeps, (size_t)B * 8, &a.sweeps);
+    f.out(X, (size_t)B * S * n * 8, &a.X);      // S == 0: no room, no copy, and the kernel does not write it
+    f.ticket(&a.ticket);
+    HIPCHK(c, f.reserve(c->ss_work, c->stream));
+    HIPCHK(c, f.upload(c->stream));
+    HIPCHK(c, spin_sync(c->stream));      // sv goes out of scope; the pageable copies above have been staged
+    a.n = (int)n; a.B = B; a.S = S; a.s_stride = ds ? n : 0;
     a.max_sweeps = max_sweeps; a.tol = tol; a.seed = seed; a.seed_stride = seed_stride; a.first_index = first_index;
-    a.ticket = (int *)(w + oticket);
-    a.V = (double *)(w + oV); a.primal = (double *)(w + opr); a.y = (double *)(w + oy); a.sweeps = (int64_t *)(w + osw); a.X = (double *)(w + oX);
     const int wgs = sdr_small_workgroups((int)n, B, c->device);
-    if (wgs < 1) return fail(c, QCQPMI_EHIP, "sdr_small_batch: occupancy query failed: %s", hipGetErrorString((hipError_t)(-wgs)));
+    if (wgs < 1) return occupancy_failed(c, name, wgs);
     const hipError_t qe = (hipError_t)sdr_small_launch(a, wgs, c->stream);
-    if (qe != hipSuccess) return fail(c, QCQPMI_EHIP, "sdr_small_batch: %s", hipGetErrorString(qe));
-    if ((rc = check_symmetric(c, w + oticket, "sdr_small_batch: an objective matrix P0_b is not symmetric (or holds a NaN)"))) return rc;
-    if (V) HIPCHK(c, hipMemcpyAsync(V, a.V, vbytes, hipMemcpyDeviceToHost, c->stream));
-    if (primal) HIPCHK(c, hipMemcpyAsync(primal, a.primal, (size_t)B * 8, hipMemcpyDeviceToHost, c->stream));
-    if (y) HIPCHK(c, hipMemcpyAsync(y, a.y, (size_t)B * N * 8, hipMemcpyDeviceToHost, c->stream));
-    if (sweeps) HIPCHK(c, hipMemcpyAsync(sweeps, a.sweeps, (size_t)B * 8, hipMemcpyDeviceToHost, c->stream));
-    if (X && S > 0) HIPCHK(c, hipMemcpyAsync(X, a.X, (size_t)B * S * n * 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, spin_sync(c->stream));
-    return 0;
+    if (qe != hipSuccess) return launch_failed(c, name, qe);
+    return finish_problems(c, name, f, a.ticket);
 }
 
 // ---- suggest(SPECTRAL) for problems whose constraints aggregate to ONE sphere (relop_eq) or ONE ball: agg = [a (n) | beta (n) | gamma]
@@ -263,6 +279,7 @@ int sdr_small_batch(qcqpmi_ctx *c, int64_t maxn, bool per_problem, const double 
 int spectral_small_batch(qcqpmi_ctx *c, int64_t maxn, int64_t B, const double *P0s, const double *q0s, const double *r0s, const double *agg, int64_t agg_stride,
                          int relop_eq, int max_sweeps, double tol, double *x, double *bound, double *mu, double *lam, int64_t *sweeps,
                          int *branch, int *status) {
+    const char *name = "spectral_small_batch";
     int rc = check_ready(c, false);
     if (rc) return rc;
     if (c->n > maxn) return fail(c, QCQPMI_EUNSUPPORTED, "spectral_small_batch: n = %lld, the small-problem kernel takes n <= %lld (%s)", (long long)c->n, (long long)maxn,
@@ -283,40 +300,29 @@ int spectral_small_batch(qcqpmi_ctx *c, int64_t maxn, int64_t B, const double *P
             return fail(c, QCQPMI_EINVAL, "spectral_small_batch: rho^2 = sum beta^2 / (4 a) - gamma = %g of problem %lld is not positive and finite", r2, (long long)b);
     }
     HIPCHK(c, hipSetDevice(c->device));
-    Carve cv;
-    const size_t oP = cv.take((size_t)B * n * n * 8), oq = cv.take((size_t)B * n * 8), or0 = cv.take((size_t)B * 8), oa = cv.take((size_t)nagg * na * 8);
-    const size_t ox = cv.take((size_t)B * n * 8), olam = cv.take((size_t)B * n * 8), obd = cv.take((size_t)B * 8), omu = cv.take((size_t)B * 8);
-    const size_t osw = cv.take((size_t)B * 8), obr = cv.take((size_t)B * 4), ost = cv.take((size_t)B * 4);
-    const size_t oticket = cv.take(2 * sizeof(int));
-    HIPCHK(c, c->ss_work.reserve(c->stream, cv.off, false));
-    char *w = c->ss_work;
-    if ((rc = stage_in(c, w + oP, P0s, (size_t)B * n * n * 8)) || (rc = stage_in(c, w + oq, q0s, (size_t)B * n * 8)) ||
-        (rc = stage_in(c, w + or0, r0s, (size_t)B * 8)) || (rc = stage_in(c, w + oa, agg, (size_t)nagg * na * 8)))
-        return rc;
-    HIPCHK(c, hipMemsetAsync(w + oticket, 0, 2 * sizeof(int), c->stream));
     SpectralSmallArgs a;
-    a.n = (int)n; a.B = B;
-    a.P0s = (const double *)(w + oP); a.q0s = (const double *)(w + oq); a.r0s = (const double *)(w + or0);
-    a.agg = (const double *)(w + oa); a.agg_stride = agg_stride;
+    BatchCall f;
+    declare_objectives(f, a, B, n, P0s, q0s, r0s);
+    f.in(agg, (size_t)nagg * na * 8, &a.agg);
+    f.out(x, (size_t)B * n * 8, &a.x);
+    const int ilam = f.room((size_t)B * n * 8, &a.lam);      // lies behind x, comes down behind mu
+    f.out(bound, (size_t)B * 8, &a.bound);
+    f.out(mu, (size_t)B * 8, &a.mu);
+    f.fetch(ilam, lam);
+    f.out(sweeps, (size_t)B * 8, &a.sweeps);
+    f.out(branch, (size_t)B * 4, &a.branch);
+    f.out(status, (size_t)B * 4, &a.status);
+    f.ticket(&a.ticket);
+    HIPCHK(c, f.reserve(c->ss_work, c->stream));
+    HIPCHK(c, f.upload(c->stream));
+    a.n = (int)n; a.B = B; a.agg_stride = agg_stride;
     a.relop_eq = relop_eq ? 1 : 0; a.max_sweeps = max_sweeps; a.tol = tol;
-    a.ticket = (int *)(w + oticket);
-    a.x = (double *)(w + ox); a.bound = (double *)(w + obd); a.mu = (double *)(w + omu); a.lam = (double *)(w + olam);
-    a.sweeps = (int64_t *)(w + osw); a.branch = (int *)(w + obr); a.status = (int *)(w + ost);
     const bool wide = n > SPECTRAL_SMALL_MAXN;
     const int wgs = wide ? spectral_wide_workgroups((int)n, B, c->device) : spectral_small_workgroups((int)n, B, c->device);
-    if (wgs < 1) return fail(c, QCQPMI_EHIP, "spectral_small_batch: occupancy query failed: %s", hipGetErrorString((hipError_t)(-wgs)));
+    if (wgs < 1) return occupancy_failed(c, name, wgs);
     const hipError_t qe = (hipError_t)(wide ? spectral_wide_launch(a, wgs, c->stream) : spectral_small_launch(a, wgs, c->stream));
-    if (qe != hipSuccess) return fail(c, QCQPMI_EHIP, "spectral_small_batch: %s", hipGetErrorString(qe));
-    if ((rc = check_symmetric(c, w + oticket, "spectral_small_batch: an objective matrix P0_b is not symmetric (or holds a NaN)"))) return rc;
-    if (x) HIPCHK(c, hipMemcpyAsync(x, a.x, (size_t)B * n * 8, hipMemcpyDeviceToHost, c->stream));
-    if (bound) HIPCHK(c, hipMemcpyAsync(bound, a.bound, (size_t)B * 8, hipMemcpyDeviceToHost, c->stream));
-    if (mu) HIPCHK(c, hipMemcpyAsync(mu, a.mu, (size_t)B * 8, hipMemcpyDeviceToHost, c->stream));
-    if (lam) HIPCHK(c, hipMemcpyAsync(lam, a.lam, (size_t)B * n * 8, hipMemcpyDeviceToHost, c->stream));
-    if (sweeps) HIPCHK(c, hipMemcpyAsync(sweeps, a.sweeps, (size_t)B * 8, hipMemcpyDeviceToHost, c->stream));
-    if (branch) HIPCHK(c, hipMemcpyAsync(branch, a.branch, (size_t)B * 4, hipMemcpyDeviceToHost, c->stream));
-    if (status) HIPCHK(c, hipMemcpyAsync(status, a.status, (size_t)B * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, spin_sync(c->stream));
-    return 0;
+    if (qe != hipSuccess) return launch_failed(c, name, qe);
+    return finish_problems(c, name, f, a.ticket);
 }
 
 // ---- improve(ADMM), R restarts each (admm_small.h); qcqpmi_last_cd_kernel is not touched either.  maxn: ADMM_SMALL_MAXN, or ADMM_WIDE_MAXN
@@ -336,67 +342,38 @@ int admm_small_batch(qcqpmi_ctx *c, int64_t maxn, int64_t B, const double *P0s, 
     if ((rc = check_batch_count(c, name, B, R))) return rc;
     const int64_t m = c->m;
     if (m < 1) return fail(c, QCQPMI_EINVAL, "admm_small_batch_run: the context has no constraint (the consensus average divides by m)");
-    for (int64_t b = 0; b < B; b++)
-        if (!(rhos[b] > 0.0) || !std::isfinite(rhos[b]))
-            return fail(c, QCQPMI_EINVAL, "admm_small_batch_run: rho of problem %lld is not positive and finite", (long long)b);
+    if ((rc = check_batch_rhos(c, name, rhos, B))) return rc;
     if (cons && (rc = check_batch_cons(c, name, cons, B, m))) return rc;
     HIPCHK(c, hipSetDevice(c->device));
     const int64_t n = c->n, T = B * R;
-    Carve cv;
-    const size_t oP = cv.take((size_t)B * n * n * 8), oM = cv.take((size_t)B * n * n * 8), oq = cv.take((size_t)B * n * 8), or0 = cv.take((size_t)B * 8);
-    const size_t orho = cv.take((size_t)B * 8);
-    const size_t oX0 = cv.take(generate ? 0 : (size_t)T * n * 8), oX = cv.take((size_t)T * n * 8);
-    const size_t oout = cv.take((size_t)T * 32);      // 2 x int64, 2 x double per restart, array after array
-    const size_t oticket = cv.take(2 * sizeof(int));
-    const BatchBest best = {cv.take((size_t)B * 2 * sizeof(int64_t)), cv.take((size_t)B * 2 * sizeof(double)), cv.take((size_t)B * n * 8),
-                            best_index, best_f0, best_maxviol, best_x};
-    const size_t ocons = cv.take(cons ? (size_t)B * m * 24 : 0);
-    HIPCHK(c, c->sb_work.reserve(c->stream, cv.off, false));
-    char *w = c->sb_work;
-    if ((rc = stage_in(c, w + oP, P0s, (size_t)B * n * n * 8)) || (rc = stage_in(c, w + oM, Minvs, (size_t)B * n * n * 8)) ||
-        (rc = stage_in(c, w + oq, q0s, (size_t)B * n * 8)) || (rc = stage_in(c, w + or0, r0s, (size_t)B * 8)) ||
-        (rc = stage_in(c, w + orho, rhos, (size_t)B * 8)) || (rc = stage_in(c, w + oX0, generate ? nullptr : X0, (size_t)T * n * 8)) ||
-        (rc = stage_in(c, w + ocons, cons, (size_t)B * m * 24)))
-        return rc;
-    HIPCHK(c, hipMemsetAsync(w + oticket, 0, 2 * sizeof(int), c->stream));
     AdmmSmallArgs a;
-    a.P = c->dp; a.B = B; a.R = R;
-    a.P0s = (const double *)(w + oP); a.Minvs = (const double *)(w + oM); a.q0s = (const double *)(w + oq); a.r0s = (const double *)(w + or0);
-    a.rhos = (const double *)(w + orho);
-    a.X0 = generate ? nullptr : (const double *)(w + oX0);
-    a.cons = cons ? (const double *)(w + ocons) : nullptr;
-    a.generate = generate ? 1 : 0; a.phase1 = phase1 ? 1 : 0; a.num_iters = num_iters; a.tol = tol; a.viol_lim = viol_lim;
-    a.seed = seed; a.seed_stride = seed_stride; a.first_index = first_index;
-    a.ticket = (int *)(w + oticket);
-    char *o = w + oout;
-    a.iters1 = (int64_t *)o; a.iters2 = (int64_t *)(o + 8 * T); a.f0 = (double *)(o + 16 * T); a.maxviol = (double *)(o + 24 * T);
-    a.X = (double *)(w + oX);
+    BatchCall f;
+    BatchBest best = {best_index, best_f0, best_maxviol, best_x};
+    char *records = nullptr;
+    declare_objectives(f, a, B, n, P0s, q0s, r0s, Minvs, &a.Minvs);
+    f.in(rhos, (size_t)B * 8, &a.rhos);
+    declare_restarts(c, f, a, best, &records, record_block_bytes<REC_ADMM>((size_t)T), B, R, generate, X0, X, cons, seed, seed_stride, first_index);
+    HIPCHK(c, f.reserve(c->sb_work, c->stream));
+    HIPCHK(c, f.upload(c->stream));
+    a.phase1 = phase1 ? 1 : 0; a.num_iters = num_iters; a.tol = tol; a.viol_lim = viol_lim;
+    bind_records<REC_ADMM>(a, records, (size_t)T);
     const int maxc = c->maxc <= 1 ? 1 : 4;
     int threads = 0;
     const int cap = admm_small_workgroups(n, maxc, cons ? m : 0, B * R, c->device, &threads);
-    if (cap < 1) return fail(c, QCQPMI_EHIP, "admm_small_batch_run: occupancy query failed: %s", hipGetErrorString((hipError_t)(-cap)));
+    if (cap < 1) return occupancy_failed(c, name, cap);
     const TicketPlan plan = ticket_partition(B, R, cap, threads / 64);      // workgroups of four waves; four or eight in the wide kernels
     a.RC = plan.RC; a.chunks = plan.chunks;
     const hipError_t qe = (hipError_t)admm_small_launch(a, maxc, plan.wgs, threads, c->stream);
-    if (qe != hipSuccess) return fail(c, QCQPMI_EHIP, "admm_small_batch_run: %s", hipGetErrorString(qe));
+    if (qe != hipSuccess) return launch_failed(c, name, qe);
     c->last_admm_kernel = admm_small_name(maxc, cons != nullptr, n > ADMM_SMALL_MAXN);
     c->last_admm_C = 0;
-    if ((rc = select_batch_best(c, name, w, best, a.f0, a.maxviol, a.X, B, R, n, select_tol))) return rc;
-    std::vector<char> hout((size_t)T * 32);      // (megabytes of fresh pages: touched while the kernel runs)
-    if ((rc = check_symmetric(c, w + oticket, "admm_small_batch_run: a matrix P0_b or Minv_b is not symmetric (or holds a NaN)"))) return rc;
-    HIPCHK(c, hipMemcpyAsync(hout.data(), o, hout.size(), hipMemcpyDeviceToHost, c->stream));
-    if (X) HIPCHK(c, hipMemcpyAsync(X, a.X, (size_t)T * n * 8, hipMemcpyDeviceToHost, c->stream));
-    if ((rc = fetch_batch_best(c, w, best, B, n))) return rc;
-    const size_t n8 = (size_t)T * 8;
-    void *const outs[4] = {iters1, iters2, f0, maxviol};
-    for (size_t k = 0; k < 4; k++) if (outs[k]) memcpy(outs[k], hout.data() + k * n8, n8);
-    return 0;
+    return finish_restarts<REC_ADMM>(c, name, f, best, a.ticket, a.f0, a.maxviol, a.X, B, R, n, select_tol, records, (size_t)T,
+                                     {nullptr, nullptr, nullptr, nullptr, iters1, iters2, f0, maxviol, nullptr, nullptr, nullptr});
 }
 
 // ---- improve([method, ...]): up to CHAIN_MAX_STAGES stages of CD or ADMM one after the other in ONE launch (chain_small.h).  The
-// per-stage records live in one block of the work buffer, array after array, every array [nstages][B R] and zeroed before the launch:
-// six of int64 (sweeps1, sweeps2, visits2, accepted2, iters1, iters2), two of double (f0, maxviol), two of int (status1, status2), one
-// of uint8 (ran_phase2): 73 bytes per stage and restart.  The final f0 / maxviol are the last stage's rows of the two double arrays.
+// per-stage records live in one block of the work buffer (restart_records, batch_call.h: the CD and the ADMM arrays, 73 bytes per stage
+// and restart), every array [nstages][B R] and zeroed before the launch.  The final f0 / maxviol are the last stage's rows.
 int chain_small_batch(qcqpmi_ctx *c, int64_t B, const double *P0s, const double *q0s, const double *r0s, const double *cons, const double *rhos,
                       const double *Minvs, int64_t R, int generate, const double *X0, int nstages, const qcqpmi_chain_stage *stages, uint64_t seed,
                       uint64_t seed_stride, uint64_t first_index, double select_tol, int64_t *st_sweeps1, int64_t *st_sweeps2,
@@ -423,85 +400,47 @@ int chain_small_batch(qcqpmi_ctx *c, int64_t B, const double *P0s, const double 
     if (any_admm) {
         if (!rhos || !Minvs) return fail(c, QCQPMI_EINVAL, "chain_small_batch_run: an ADMM stage needs rhos and Minvs");
         if (m < 1) return fail(c, QCQPMI_EINVAL, "chain_small_batch_run: the context has no constraint (the consensus average of an ADMM stage divides by m)");
-        for (int64_t b = 0; b < B; b++)
-            if (!(rhos[b] > 0.0) || !std::isfinite(rhos[b]))
-                return fail(c, QCQPMI_EINVAL, "chain_small_batch_run: rho of problem %lld is not positive and finite", (long long)b);
+        if ((rc = check_batch_rhos(c, name, rhos, B))) return rc;
     }
     if (cons && (rc = check_batch_cons(c, name, cons, B, m))) return rc;
     if (m == 0) cons = nullptr;       // nothing to stage: the shared kernels
     HIPCHK(c, hipSetDevice(c->device));
     const int64_t n = c->n, T = B * R, ST = (int64_t)nstages * T;
-    Carve cv;
-    const size_t oP = cv.take((size_t)B * n * n * 8), oM = cv.take(any_admm ? (size_t)B * n * n * 8 : 0), oq = cv.take((size_t)B * n * 8), or0 = cv.take((size_t)B * 8);
-    const size_t orho = cv.take(any_admm ? (size_t)B * 8 : 0);
-    const size_t oX0 = cv.take(generate ? 0 : (size_t)T * n * 8), oX = cv.take((size_t)T * n * 8);
-    const size_t oout = cv.take((size_t)ST * 73);
-    const size_t oticket = cv.take(2 * sizeof(int));
-    const BatchBest best = {cv.take((size_t)B * 2 * sizeof(int64_t)), cv.take((size_t)B * 2 * sizeof(double)), cv.take((size_t)B * n * 8),
-                            best_index, best_f0, best_maxviol, best_x};
-    const size_t ocons = cv.take(cons ? (size_t)B * m * 24 : 0);
-    HIPCHK(c, c->sb_work.reserve(c->stream, cv.off, false));
-    char *w = c->sb_work;
-    if ((rc = stage_in(c, w + oP, P0s, (size_t)B * n * n * 8)) || (rc = stage_in(c, w + oM, any_admm ? Minvs : nullptr, (size_t)B * n * n * 8)) ||
-        (rc = stage_in(c, w + oq, q0s, (size_t)B * n * 8)) || (rc = stage_in(c, w + or0, r0s, (size_t)B * 8)) ||
-        (rc = stage_in(c, w + orho, any_admm ? rhos : nullptr, (size_t)B * 8)) || (rc = stage_in(c, w + oX0, generate ? nullptr : X0, (size_t)T * n * 8)) ||
-        (rc = stage_in(c, w + ocons, cons, (size_t)B * m * 24)))
-        return rc;
-    HIPCHK(c, hipMemsetAsync(w + oticket, 0, 2 * sizeof(int), c->stream));
-    HIPCHK(c, hipMemsetAsync(w + oout, 0, (size_t)ST * 73, c->stream));      // what a stage does not produce stays zero
+    const size_t record_bytes = record_block_bytes<REC_CD | REC_ADMM>((size_t)ST);
     ChainSmallArgs a;
-    a.P = c->dp; a.B = B; a.R = R;
-    a.P0s = (const double *)(w + oP); a.q0s = (const double *)(w + oq); a.r0s = (const double *)(w + or0);
-    a.rhos = any_admm ? (const double *)(w + orho) : nullptr; a.Minvs = any_admm ? (const double *)(w + oM) : nullptr;
-    a.X0 = generate ? nullptr : (const double *)(w + oX0);
-    a.cons = cons ? (const double *)(w + ocons) : nullptr;
-    a.generate = generate ? 1 : 0; a.nstages = nstages;
-    a.seed = seed; a.seed_stride = seed_stride; a.first_index = first_index;
-    a.ticket = (int *)(w + oticket);
-    a.X = (double *)(w + oX);
-    char *o = w + oout;
-    const size_t a8 = (size_t)ST * 8;      // one array of 8-byte entries
+    BatchCall f;
+    BatchBest best = {best_index, best_f0, best_maxviol, best_x};
+    char *records = nullptr;
+    declare_objectives(f, a, B, n, P0s, q0s, r0s, any_admm ? Minvs : nullptr, &a.Minvs);
+    f.in(any_admm ? rhos : nullptr, (size_t)B * 8, &a.rhos);
+    declare_restarts(c, f, a, best, &records, record_bytes, B, R, generate, X0, X, cons, seed, seed_stride, first_index);
+    HIPCHK(c, f.reserve(c->sb_work, c->stream));
+    HIPCHK(c, f.upload(c->stream));
+    HIPCHK(c, hipMemsetAsync(records, 0, record_bytes, c->stream));      // what a stage does not produce stays zero
+    a.nstages = nstages;
     for (int s = 0; s < CHAIN_MAX_STAGES; s++) {
         ChainStage &g = a.st[s];
         memset(&g, 0, sizeof(g));
         if (s >= nstages) continue;
         g.method = stages[s].method; g.phase1 = stages[s].phase1 ? 1 : 0; g.num_iters = stages[s].num_iters;
         g.tol = stages[s].tol; g.viol_tol = stages[s].viol_tol; g.viol_lim = stages[s].viol_lim;
-        const size_t r8 = (size_t)s * T * 8;
-        g.sweeps1 = (int64_t *)(o + r8); g.sweeps2 = (int64_t *)(o + a8 + r8); g.visits2 = (int64_t *)(o + 2 * a8 + r8);
-        g.accepted2 = (int64_t *)(o + 3 * a8 + r8); g.iters1 = (int64_t *)(o + 4 * a8 + r8); g.iters2 = (int64_t *)(o + 5 * a8 + r8);
-        g.f0 = (double *)(o + 6 * a8 + r8); g.maxviol = (double *)(o + 7 * a8 + r8);
-        g.status1 = (int *)(o + 8 * a8 + r8 / 2); g.status2 = (int *)(o + 8 * a8 + a8 / 2 + r8 / 2);
-        g.ran2 = (uint8_t *)(o + 9 * a8 + r8 / 8);
+        bind_records<REC_CD | REC_ADMM>(g, records, (size_t)T, (size_t)nstages, (size_t)s);
     }
     const int maxc = c->maxc <= 1 ? 1 : 4;
     const int cap = chain_small_workgroups(n, maxc, cons ? m : 0, B * R, c->device);
-    if (cap < 1) return fail(c, QCQPMI_EHIP, "chain_small_batch_run: occupancy query failed: %s", hipGetErrorString((hipError_t)(-cap)));
+    if (cap < 1) return occupancy_failed(c, name, cap);
     const TicketPlan plan = ticket_partition(B, R, cap, 4);      // workgroups of four waves
     a.RC = plan.RC; a.chunks = plan.chunks;
-    (void)hipEventRecord(c->timers[2].beg, c->stream);
+    tic(c, 2);
     const hipError_t qe = (hipError_t)chain_small_launch(a, maxc, plan.wgs, c->stream);
-    (void)hipEventRecord(c->timers[2].end, c->stream);
-    c->timers[2].valid = true;
-    if (qe != hipSuccess) return fail(c, QCQPMI_EHIP, "chain_small_batch_run: %s", hipGetErrorString(qe));
+    toc(c, 2);
+    if (qe != hipSuccess) return launch_failed(c, name, qe);
     c->last_cd2_kernel = chain_small_name(maxc, cons != nullptr);
     const ChainStage &last = a.st[nstages - 1];
-    if ((rc = select_batch_best(c, name, w, best, last.f0, last.maxviol, a.X, B, R, n, select_tol))) return rc;
-    std::vector<char> hout((size_t)ST * 73);      // (megabytes of fresh pages: touched while the kernel runs)
-    if ((rc = check_symmetric(c, w + oticket, "chain_small_batch_run: a matrix P0_b or Minv_b is not symmetric (or holds a NaN)"))) return rc;
-    HIPCHK(c, hipMemcpyAsync(hout.data(), o, hout.size(), hipMemcpyDeviceToHost, c->stream));
-    if (X) HIPCHK(c, hipMemcpyAsync(X, a.X, (size_t)T * n * 8, hipMemcpyDeviceToHost, c->stream));
-    if ((rc = fetch_batch_best(c, w, best, B, n))) return rc;
-    const char *h = hout.data();
-    void *const wide[8] = {st_sweeps1, st_sweeps2, st_visits2, st_accepted2, st_iters1, st_iters2, st_f0, st_maxviol};
-    for (size_t k = 0; k < 8; k++) if (wide[k]) memcpy(wide[k], h + k * a8, a8);
-    if (st_status1) memcpy(st_status1, h + 8 * a8, a8 / 2);
-    if (st_status2) memcpy(st_status2, h + 8 * a8 + a8 / 2, a8 / 2);
-    if (st_ran_phase2) memcpy(st_ran_phase2, h + 9 * a8, (size_t)ST);
-    const size_t l8 = (size_t)(nstages - 1) * T * 8;
-    if (f0) memcpy(f0, h + 6 * a8 + l8, (size_t)T * 8);
-    if (maxviol) memcpy(maxviol, h + 7 * a8 + l8, (size_t)T * 8);
-    return 0;
+    return finish_restarts<REC_CD | REC_ADMM>(
+        c, name, f, best, a.ticket, last.f0, last.maxviol, a.X, B, R, n, select_tol, records, (size_t)ST,
+        {st_sweeps1, st_sweeps2, st_visits2, st_accepted2, st_iters1, st_iters2, st_f0, st_maxviol, st_status1, st_status2, st_ran_phase2},
+        (size_t)(nstages - 1) * T, f0, maxviol);
 }
 
 // ---- the setup of improve(ADMM) on the device (admm_setup.h): rho_b by the reference's rule (rho == nullptr) or the caller's, and
@@ -521,37 +460,31 @@ int admm_setup_batch(qcqpmi_ctx *c, int64_t B, const double *P0s, const double *
     const int64_t n = c->n, m = c->m;
     if (m < 1) return fail(c, QCQPMI_EINVAL, "admm_batch_setup: the context has no constraint (the rule divides by m)");
     HIPCHK(c, hipSetDevice(c->device));
-    Carve cv;
-    const size_t oP = cv.take((size_t)B * n * n * 8), oM = cv.take((size_t)B * n * n * 8), orho = cv.take((size_t)B * 8), olm = cv.take((size_t)B * 8);
-    const size_t osw = cv.take((size_t)B * 8), ost = cv.take((size_t)B * 4), oticket = cv.take(2 * sizeof(int));
-    HIPCHK(c, c->ss_work.reserve(c->stream, cv.off, false));
-    char *w = c->ss_work;
-    if ((rc = stage_in(c, w + oP, P0s, (size_t)B * n * n * 8))) return rc;
-    HIPCHK(c, hipMemsetAsync(w + oticket, 0, 2 * sizeof(int), c->stream));
-    if (rho) HIPCHK(c, hipMemsetAsync(w + oM, 0, (size_t)B * n * n * 8, c->stream));      // a problem of status 3 is not written
     AdmmSetupArgs a;
+    BatchCall f;
+    f.in(P0s, (size_t)B * n * n * 8, &a.P0s);
+    const int iM = f.room((size_t)B * n * n * 8, &a.Minvs);      // lies behind P0s, comes down behind lambda_min
+    f.out(rhos, (size_t)B * 8, &a.rhos);
+    f.out(lambda_min, (size_t)B * 8, &a.lambda_min);
+    f.fetch(iM, Minvs);
+    f.out(sweeps, (size_t)B * 8, &a.sweeps);
+    f.out(status, (size_t)B * 4, &a.status);
+    f.ticket(&a.ticket);
+    HIPCHK(c, f.reserve(c->ss_work, c->stream));
+    HIPCHK(c, f.upload(c->stream));
+    if (rho) HIPCHK(c, hipMemsetAsync(a.Minvs, 0, (size_t)B * n * n * 8, c->stream));      // a problem of status 3 is not written
     a.n = (int)n; a.B = B;
-    a.P0s = (const double *)(w + oP);
     a.m = (double)m; a.has_rho = rho ? 1 : 0; a.rho = rho ? *rho : 0.0;
     a.max_sweeps = max_sweeps; a.tol = tol;
-    a.ticket = (int *)(w + oticket);
-    a.rhos = (double *)(w + orho); a.lambda_min = (double *)(w + olm); a.Minvs = (double *)(w + oM);
-    a.sweeps = (int64_t *)(w + osw); a.status = (int *)(w + ost);
     const int wgs = admm_setup_workgroups((int)n, B, c->device);
-    if (wgs < 1) return fail(c, QCQPMI_EHIP, "admm_batch_setup: occupancy query failed: %s", hipGetErrorString((hipError_t)(-wgs)));
+    if (wgs < 1) return occupancy_failed(c, name, wgs);
     const hipError_t qe = (hipError_t)admm_setup_launch(a, wgs, c->stream);
-    if (qe != hipSuccess) return fail(c, QCQPMI_EHIP, "admm_batch_setup: %s", hipGetErrorString(qe));
-    if ((rc = check_symmetric(c, w + oticket, "admm_batch_setup: an objective matrix P0_b is not symmetric (or holds a NaN)"))) return rc;
-    if (rhos) HIPCHK(c, hipMemcpyAsync(rhos, a.rhos, (size_t)B * 8, hipMemcpyDeviceToHost, c->stream));
-    if (lambda_min) HIPCHK(c, hipMemcpyAsync(lambda_min, a.lambda_min, (size_t)B * 8, hipMemcpyDeviceToHost, c->stream));
-    if (Minvs) HIPCHK(c, hipMemcpyAsync(Minvs, a.Minvs, (size_t)B * n * n * 8, hipMemcpyDeviceToHost, c->stream));
-    if (sweeps) HIPCHK(c, hipMemcpyAsync(sweeps, a.sweeps, (size_t)B * 8, hipMemcpyDeviceToHost, c->stream));
-    if (status) HIPCHK(c, hipMemcpyAsync(status, a.status, (size_t)B * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, spin_sync(c->stream));
-    return 0;
+    if (qe != hipSuccess) return launch_failed(c, name, qe);
+    return finish_problems(c, name, f, a.ticket);
 }
 
 }  // namespace
+
 
 extern "C" {
 

@@ -33,8 +33,6 @@
 // out (slot 0, then slot 1 under if constexpr) instead of looped over: with loops the W = 1 kernels came out as other code.
 #include "cd_small.h"
 
-#include <stdlib.h>
-
 #include "sm_restart.h"    // the restart: sm_restart<MAXC, PC, W> and its helpers
 
 namespace qcqpmi {
@@ -71,66 +69,23 @@ CdSmallKernel cd_small_pick(int64_t n, int maxc, bool pc) {
 
 }  // namespace
 
-// QCQPMI_CD_WIDE_THREADS = 64 .. 512 (a multiple of 64): that workgroup size for the wide kernels instead of the rule below -- for
-// measuring the rule (tools/bench_small_batch.py --wide-threads); results do not depend on it
-static int cd_wide_threads_asked() {
-    static const int asked = [] {
-        const char *v = getenv("QCQPMI_CD_WIDE_THREADS");
-        const int t = v ? atoi(v) : 0;
-        return (t >= 64 && t <= CD_WIDE_THREADS && t % 64 == 0) ? t : 0;
-    }();
+static int cd_wide_threads_asked() {      // read once
+    static const int asked = small_threads_asked("QCQPMI_CD_WIDE_THREADS", CD_WIDE_THREADS);
     return asked;
 }
 
 int cd_small_workgroups(int64_t n, int maxc, int64_t pc_entries, int64_t tickets, int device, int *threads) {
-    int per = 0;
-    hipError_t e;
-    const size_t lds = small_image_bytes(n, pc_entries);
-    const CdSmallKernel k = cd_small_pick(n, maxc, pc_entries > 0);
-    *threads = 256;
-    if (n > CD_SMALL_MAXN) {      // the image passes 64 KB from n = 91
-        e = hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return -(int)e;
-        // the workgroup that puts more waves on a CU: while three images fit a CU (n = 72: 41 KB each) four waves of each beat the eight
-        // of one workgroup; from n = 101 there is one image and eight waves beat four (measured: profiles/r12_wide_batch.md)
-        const int asked = cd_wide_threads_asked();
-        int per_small = 0, per_large = 0;
-        e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_small, k, asked ? asked : 256, lds);
-        if (e != hipSuccess) return -(int)e;
-        per = per_small;
-        *threads = asked ? asked : 256;
-        if (!asked) {
-            e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_large, k, CD_WIDE_THREADS, lds);
-            if (e != hipSuccess) return -(int)e;
-            if (per_large * CD_WIDE_THREADS >= per_small * 256) { per = per_large; *threads = CD_WIDE_THREADS; }
-        }
-    } else {
-        e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, k, 256, lds);
-        if (e != hipSuccess) return -(int)e;
-    }
-    return small_workgroup_cap(device, per, tickets);
+    const bool wide = n > CD_SMALL_MAXN;
+    return small_ticket_workgroups((const void *)cd_small_pick(n, maxc, pc_entries > 0), small_image_bytes(n, pc_entries), tickets, device,
+                                   wide ? CD_WIDE_THREADS : 0, wide ? cd_wide_threads_asked() : 0, threads);
 }
 
 int cd_small_launch(const CdSmallArgs &a, int maxc, int wgs, int threads, hipStream_t st) {
     const bool pc = a.cons != nullptr;
-    const size_t lds = small_image_bytes(a.P.n, pc ? a.P.m : 0);
-    const CdSmallKernel k = cd_small_pick(a.P.n, maxc, pc);
-    if (a.P.n > CD_SMALL_MAXN) {
-        const hipError_t e = hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return (int)e;
-    }
-    hipLaunchKernelGGL(k, dim3((unsigned)wgs), dim3((unsigned)threads), lds, st, a);
-    return (int)hipGetLastError();
+    return small_launch(cd_small_pick(a.P.n, maxc, pc), small_image_bytes(a.P.n, pc ? a.P.m : 0), a, wgs, threads, a.P.n > CD_SMALL_MAXN, st);
 }
 
-const char *cd_small_name(int maxc, bool pc, bool wide) {
-    if (wide) {
-        if (pc) return maxc <= 1 ? "cd_small_kernel<1,pc,w2>" : "cd_small_kernel<4,pc,w2>";
-        return maxc <= 1 ? "cd_small_kernel<1,w2>" : "cd_small_kernel<4,w2>";
-    }
-    if (pc) return maxc <= 1 ? "cd_small_kernel<1,pc>" : "cd_small_kernel<4,pc>";
-    return maxc <= 1 ? "cd_small_kernel<1>" : "cd_small_kernel<4>";
-}
+const char *cd_small_name(int maxc, bool pc, bool wide) { return batch_kernel_name<CdSmallArgs>("cd_small_kernel", maxc, pc, wide); }
 
 int small_gather_launch(const double *X, int64_t n, int64_t R, int64_t B, const int64_t *idx, double *out, hipStream_t st) {
     hipLaunchKernelGGL(small_gather_kernel, dim3((unsigned)B), dim3(64), 0, st, X, n, R, idx, out);

@@ -76,14 +76,9 @@ int chain_small_workgroups(int64_t n, int maxc, int64_t pc_entries, int64_t tick
 
 int chain_small_launch(const ChainSmallArgs &a, int maxc, int wgs, hipStream_t st) {
     const bool pc = a.cons != nullptr;
-    const size_t lds = small_image_bytes(a.P.n, pc ? a.P.m : 0);
-    hipLaunchKernelGGL(chain_small_pick(maxc, pc), dim3((unsigned)wgs), dim3(256), lds, st, a);
-    return (int)hipGetLastError();
+    return small_launch(chain_small_pick(maxc, pc), small_image_bytes(a.P.n, pc ? a.P.m : 0), a, wgs, 256, false, st);
 }
 
-const char *chain_small_name(int maxc, bool pc) {
-    if (pc) return maxc <= 1 ? "chain_small_kernel<1,pc>" : "chain_small_kernel<4,pc>";
-    return maxc <= 1 ? "chain_small_kernel<1>" : "chain_small_kernel<4>";
-}
+const char *chain_small_name(int maxc, bool pc) { return batch_kernel_name<ChainSmallArgs>("chain_small_kernel", maxc, pc, false); }
 
 }  // namespace qcqpmi

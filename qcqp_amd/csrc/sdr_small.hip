@@ -21,7 +21,7 @@
 
 #include "philox.h"
 #include "dev_util.h"
-#include "small_batch.h"    // small_workgroup_cap
+#include "small_batch.h"    // the launchers: small_wave_workgroups, small_launch
 
 namespace qcqpmi {
 namespace {
@@ -211,8 +211,10 @@ __global__ __launch_bounds__(64) void sdr_small_kernel(SdrSmallArgs a) {
     }
 }
 
+typedef void (*SdrSmallKernel)(SdrSmallArgs);
+
 // n <= SDR_SMALL_MAXN: the kernel with the full C_b; past it the wide one
-const void *ss_kernel(int n) { return n > SDR_SMALL_MAXN ? (const void *)sdr_small_kernel<true> : (const void *)sdr_small_kernel<false>; }
+SdrSmallKernel ss_kernel(int n) { return n > SDR_SMALL_MAXN ? sdr_small_kernel<true> : sdr_small_kernel<false>; }
 
 }  // namespace
 
@@ -221,23 +223,8 @@ size_t sdr_small_lds_bytes(int n) {
     return (N * SDR_SMALL_VSTR + (n > SDR_SMALL_MAXN ? N * (N + 1) / 2 : N * N) + SDR_SMALL_K) * sizeof(double);
 }
 
-int sdr_small_workgroups(int n, int64_t B, int device) {
-    int per = 0;
-    const size_t lds = sdr_small_lds_bytes(n);
-    hipError_t e = hipFuncSetAttribute(ss_kernel(n), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return -(int)e;
-    e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, ss_kernel(n), 64, lds);
-    if (e != hipSuccess) return -(int)e;
-    return small_workgroup_cap(device, per, B);
-}
+int sdr_small_workgroups(int n, int64_t B, int device) { return small_wave_workgroups((const void *)ss_kernel(n), sdr_small_lds_bytes(n), B, device); }
 
-int sdr_small_launch(const SdrSmallArgs &a, int wgs, hipStream_t st) {
-    const size_t lds = sdr_small_lds_bytes(a.n);
-    hipError_t e = hipFuncSetAttribute(ss_kernel(a.n), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return (int)e;
-    if (a.n > SDR_SMALL_MAXN) hipLaunchKernelGGL(sdr_small_kernel<true>, dim3((unsigned)wgs), dim3(64), lds, st, a);
-    else hipLaunchKernelGGL(sdr_small_kernel<false>, dim3((unsigned)wgs), dim3(64), lds, st, a);
-    return (int)hipGetLastError();
-}
+int sdr_small_launch(const SdrSmallArgs &a, int wgs, hipStream_t st) { return small_launch(ss_kernel(a.n), sdr_small_lds_bytes(a.n), a, wgs, 64, true, st); }
 
 }  // namespace qcqpmi

@@ -7,11 +7,17 @@
 // and its waves take the chunk's restarts one by one from a counter in LDS: ONE WAVEFRONT PER (problem, restart).  After the barrier
 // that follows the staging a wave never waits for another one: no flags, no spinning; the next barrier is the one before the image
 // is replaced.  The restarts read column i of A_b as ROW i of the image, so a matrix that is not symmetric (or holds a NaN) sets
-// ticket[1] and the call fails.  sdr_small_kernel has a loop of its own (one wave per problem) and shares the host helpers only.
+// ticket[1] and the call fails.  sdr_small_kernel, the spectral kernels and the ADMM setup kernels have a loop of their own (one wave
+// per problem) and share the host helpers only: the launchers below (workgroups, launch), one pair for them and one for the ticket
+// kernels.  What needs no device code -- the call frame of the drivers, ticket_partition, the workgroup-size rule, the kernel names
+// -- is in batch_call.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdlib.h>
 #include <type_traits>
+
+#include "batch_call.h"      // batch_wide_threads, batch_kernel_name
 
 namespace qcqpmi {
 
@@ -30,6 +36,49 @@ inline int small_workgroup_cap(int device, int per, int64_t tickets) {
 
 // the winners' points: out[b][0..n) = X[b][idx[2 b]][0..n)  (idx as select_best_kernel leaves it; < 0: row left as it is); cd_small.hip
 int small_gather_launch(const double *X, int64_t n, int64_t R, int64_t B, const int64_t *idx, double *out, hipStream_t st);
+
+// ---- the launchers of the persistent batch kernels: a unit keeps its LDS formula and its "which kernel for this n" and calls these
+// with the kernel's address.  Workgroups: what the device holds at once, at most one per ticket, or < 0: -hipError_t.
+
+// a ONE-WAVE-PER-PROBLEM kernel (sdr_small, spectral_small / _wide, admm_setup / _wide): 64 threads, dynamic LDS past 64 KB allowed
+inline int small_wave_workgroups(const void *fn, size_t lds, int64_t B, int device) {
+    int per = 0;
+    hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e == hipSuccess) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, fn, 64, lds);
+    return e != hipSuccess ? -(int)e : small_workgroup_cap(device, per, B);
+}
+
+// a TICKET kernel (cd_small, admm_small) and *threads, the size of its workgroups: 256 -- or, for a wide kernel (large > 0: its
+// largest workgroup; the image passes 64 KB from n = 91), what batch_wide_threads picks from two occupancy queries, or `asked`
+inline int small_ticket_workgroups(const void *fn, size_t lds, int64_t tickets, int device, int large, int asked, int *threads) {
+    int per = 0, per_large = 0;
+    hipError_t e = large ? hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) : hipSuccess;
+    *threads = large && asked ? asked : 256;
+    if (e == hipSuccess) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, fn, *threads, lds);
+    if (e == hipSuccess && large && !asked) {
+        e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_large, fn, large, lds);
+        if (e == hipSuccess && batch_wide_threads(per, per_large, large) == large) { per = per_large; *threads = large; }
+    }
+    return e != hipSuccess ? -(int)e : small_workgroup_cap(device, per, tickets);
+}
+
+// QCQPMI_CD_WIDE_THREADS / QCQPMI_ADMM_WIDE_THREADS = 64 .. large (a multiple of 64): that workgroup size for the wide kernels instead
+// of the rule, for measuring the rule (tools/bench_small_batch.py, bench_admm_batch.py --wide-threads); results do not depend on it.
+// 0: not set, or not such a number.  The units read theirs once.
+inline int small_threads_asked(const char *variable, int large) {
+    const char *v = getenv(variable);
+    const int t = v ? atoi(v) : 0;
+    return (t >= 64 && t <= large && t % 64 == 0) ? t : 0;
+}
+
+// the launch (a template: instantiated in the unit that owns the kernel); big_lds: more than 64 KB of dynamic LDS may be needed
+template <class Args>
+inline int small_launch(void (*fn)(Args), size_t lds, const Args &a, int wgs, int threads, bool big_lds, hipStream_t st) {
+    const hipError_t e = big_lds ? hipFuncSetAttribute((const void *)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) : hipSuccess;
+    if (e != hipSuccess) return (int)e;
+    hipLaunchKernelGGL(fn, dim3((unsigned)wgs), dim3((unsigned)threads), lds, st, a);
+    return (int)hipGetLastError();
+}
 
 // ---- staging, by the nt threads of the workgroup (nn = n n entries; off: problem b's offset b n in q0s)
 __device__ __attribute__((always_inline)) inline void small_stage_matrix(double *As, const double *Ag, int nn, int tid, int nt) {

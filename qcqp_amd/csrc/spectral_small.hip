@@ -10,7 +10,7 @@
 
 #include "dev_util.h"
 #include "jacobi_small.h"
-#include "small_batch.h"     // small_workgroup_cap
+#include "small_batch.h"     // the launchers: small_wave_workgroups, small_launch
 #include "spectral_solve.h"
 
 namespace qcqpmi {
@@ -172,21 +172,11 @@ size_t spectral_small_lds_bytes(int n) {
 }
 
 int spectral_small_workgroups(int n, int64_t B, int device) {
-    int per = 0;
-    const size_t lds = spectral_small_lds_bytes(n);
-    hipError_t e = hipFuncSetAttribute((const void *)spectral_small_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return -(int)e;
-    e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, (const void *)spectral_small_kernel, 64, lds);
-    if (e != hipSuccess) return -(int)e;
-    return small_workgroup_cap(device, per, B);
+    return small_wave_workgroups((const void *)spectral_small_kernel, spectral_small_lds_bytes(n), B, device);
 }
 
 int spectral_small_launch(const SpectralSmallArgs &a, int wgs, hipStream_t st) {
-    const size_t lds = spectral_small_lds_bytes(a.n);
-    const hipError_t e = hipFuncSetAttribute((const void *)spectral_small_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(spectral_small_kernel, dim3((unsigned)wgs), dim3(64), lds, st, a);
-    return (int)hipGetLastError();
+    return small_launch(spectral_small_kernel, spectral_small_lds_bytes(a.n), a, wgs, 64, true, st);
 }
 
 }  // namespace qcqpmi
@@ -202,21 +192,11 @@ size_t spectral_wide_lds_bytes(int n) {
 }
 
 int spectral_wide_workgroups(int n, int64_t B, int device) {
-    int per = 0;
-    const size_t lds = spectral_wide_lds_bytes(n);
-    hipError_t e = hipFuncSetAttribute((const void *)spectral_wide_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return -(int)e;
-    e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, (const void *)spectral_wide_kernel, 64, lds);
-    if (e != hipSuccess) return -(int)e;
-    return small_workgroup_cap(device, per, B);
+    return small_wave_workgroups((const void *)spectral_wide_kernel, spectral_wide_lds_bytes(n), B, device);
 }
 
 int spectral_wide_launch(const SpectralSmallArgs &a, int wgs, hipStream_t st) {
-    const size_t lds = spectral_wide_lds_bytes(a.n);
-    const hipError_t e = hipFuncSetAttribute((const void *)spectral_wide_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(spectral_wide_kernel, dim3((unsigned)wgs), dim3(64), lds, st, a);
-    return (int)hipGetLastError();
+    return small_launch(spectral_wide_kernel, spectral_wide_lds_bytes(a.n), a, wgs, 64, true, st);
 }
 
 }  // namespace qcqpmi
@@ -231,27 +211,16 @@ size_t admm_setup_lds_bytes(int n) {
     return (n > ADMM_SETUP_SMALL_MAXN ? jacobi_wide_doubles(n2) + ASW_VECS * ASW_VEC : jacobi_small_doubles(n2) + AS_VECS * AS_VEC) * sizeof(double);
 }
 
-static const void *admm_setup_function(int n) {
-    return n > ADMM_SETUP_SMALL_MAXN ? (const void *)admm_setup_wide_kernel : (const void *)admm_setup_kernel;
-}
+typedef void (*AdmmSetupKernel)(AdmmSetupArgs);
+
+static AdmmSetupKernel admm_setup_function(int n) { return n > ADMM_SETUP_SMALL_MAXN ? admm_setup_wide_kernel : admm_setup_kernel; }
 
 int admm_setup_workgroups(int n, int64_t B, int device) {
-    int per = 0;
-    const size_t lds = admm_setup_lds_bytes(n);
-    hipError_t e = hipFuncSetAttribute(admm_setup_function(n), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return -(int)e;
-    e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, admm_setup_function(n), 64, lds);
-    if (e != hipSuccess) return -(int)e;
-    return small_workgroup_cap(device, per, B);
+    return small_wave_workgroups((const void *)admm_setup_function(n), admm_setup_lds_bytes(n), B, device);
 }
 
 int admm_setup_launch(const AdmmSetupArgs &a, int wgs, hipStream_t st) {
-    const size_t lds = admm_setup_lds_bytes(a.n);
-    const hipError_t e = hipFuncSetAttribute(admm_setup_function(a.n), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return (int)e;
-    if (a.n > ADMM_SETUP_SMALL_MAXN) hipLaunchKernelGGL(admm_setup_wide_kernel, dim3((unsigned)wgs), dim3(64), lds, st, a);
-    else hipLaunchKernelGGL(admm_setup_kernel, dim3((unsigned)wgs), dim3(64), lds, st, a);
-    return (int)hipGetLastError();
+    return small_launch(admm_setup_function(a.n), admm_setup_lds_bytes(a.n), a, wgs, 64, true, st);
 }
 
 }  // namespace qcqpmi

@@ -1070,7 +1070,9 @@ def test_shared_device_helpers_are_defined_once():
     fix had to be made in two or three places and nothing failed when one was missed)."""
     from qcqp_amd import _build
     names = ['block_rows_times_X', 'keyed_normal_pair', 'ordered_key', 'ordered_unkey', 'wave_max', 'p1_class_visit',
-             'small_ticket_frame', 'small_stage_matrix', 'small_stage_q', 'small_stage_cons', 'small_asym_scan', 'chain_share']
+             'small_ticket_frame', 'small_stage_matrix', 'small_stage_q', 'small_stage_cons', 'small_asym_scan', 'chain_share',
+             'ticket_partition', 'batch_wide_threads', 'batch_kernel_name', 'restart_records', 'small_wave_workgroups',
+             'small_ticket_workgroups', 'small_threads_asked', 'small_launch']
     text = {f: open(os.path.join(_build.SRC, f)).read() for f in os.listdir(_build.SRC) if f.endswith(('.hip', '.h', '.inc'))}
     for name in names:
         # a line that starts the definition: qualifiers and a return type at the start of the line, then NAME( -- a call sits
@@ -1171,6 +1173,26 @@ def test_dev_buf_selftest_under_sanitizers(tmp_path):
     exe = str(tmp_path / 'dev_buf_selftest')
     p = subprocess.run([cxx, '-std=c++17', '-D__HIP_PLATFORM_AMD__', '-I' + inc, '-fsanitize=address,undefined', '-o', exe,
                         os.path.join(REPO, 'tests', 'host', 'dev_buf_selftest.cpp')], stdout=subprocess.PIPE, stderr=subprocess.STDOUT)
+    assert p.returncode == 0, p.stdout.decode()
+    r = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT)
+    assert r.returncode == 0 and r.stdout.decode().strip() == 'ok', r.stdout.decode()
+
+
+def test_batch_call_selftest_under_sanitizers(tmp_path):
+    """tests/host/batch_call_selftest.cpp: batch_call.h, the host frame of the small-problem batch drivers, against a stand-in runtime
+    that backs device memory with host memory and logs every call -- the layout of the work buffer (declaration order, 256-byte
+    pieces, the worked CD example), no copy for a missing input or an unwanted output, one 8-byte memset for the ticket, no pointer
+    before the reserve and none after a refused one, the record table round trip (CD, ADMM, chain of 1 and 3 stages; odd counts; absent
+    destinations), ticket_partition against the drivers' former arithmetic and its invariants, the workgroup-size rule with ties, the
+    kernel names.  Host compiler, AddressSanitizer + UBSan; not linked against the HIP runtime."""
+    import shutil
+    cxx = os.environ.get('CXX') or shutil.which('g++') or shutil.which('clang++')
+    inc = '/opt/rocm/include'
+    if not cxx or not os.path.exists(os.path.join(inc, 'hip', 'hip_runtime_api.h')):
+        pytest.skip('no host compiler / HIP headers')
+    exe = str(tmp_path / 'batch_call_selftest')
+    p = subprocess.run([cxx, '-std=c++17', '-D__HIP_PLATFORM_AMD__', '-I' + inc, '-fsanitize=address,undefined', '-o', exe,
+                        os.path.join(REPO, 'tests', 'host', 'batch_call_selftest.cpp')], stdout=subprocess.PIPE, stderr=subprocess.STDOUT)
     assert p.returncode == 0, p.stdout.decode()
     r = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT)
     assert r.returncode == 0 and r.stdout.decode().strip() == 'ok', r.stdout.decode()
